@@ -1,11 +1,17 @@
 """Headline benchmark: U-Net-CA training throughput (tiles/s) on synthetic 256x256x2 InSAR tiles.
 
-python bench.py --gpus N --steps K --warmup W
+python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   N > 1 is launched by the driver as  python -m torch.distributed.run --nproc-per-node N ... bench.py
 A step = one pass of the hot path over one batch: zero_grad -> forward -> Dice+CE loss -> backward
 (-> RCCL gradient all-reduce when N > 1) -> Adam step, exactly the loop of
 Unet-ChannalAttention.py:342-346. Inputs are resident in HBM before the timed region.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, runs the settling and warm-up steps, times K steps and prints the line. --full adds what takes runs
+of its own: the two per-kernel event passes (gemm_kernels, roofline), configs 4 and 5 (other_configs) and the CPU oracle's
+baseline (cpu_baseline); --no-kernel-timing, --no-other-configs and --no-cpu-baseline drop single legs of it.
+--dump-outputs DIR writes what the last timed step handed its caller (see dump_outputs) as DIR/<name>.npy; the inputs and
+the initial weights are seeded, the same in every run with the same arguments.
 """
 from __future__ import annotations
 
@@ -26,6 +32,7 @@ FLOP_PER_TILE_256 = 288.7e9           # forward + backward, 2x256x256 tile
 PEAK_BF16_TFLOPS = 2500.0             # dense MFMA peak, MI355X_MICROARCH.md
 PEAK_F32_TFLOPS = 157.3               # fp32 MFMA = fp32 vector rate
 PEAK_HBM_GBS = 8000.0
+DUMP_SAMPLE = 1 << 22                 # elements of a sampled --dump-outputs array (16 MB in float32)
 
 
 def cpu_baseline(size: int = 256):
@@ -71,6 +78,34 @@ def cpu_baseline(size: int = 256):
             "sample": f"{nsteps} timed fp32 train steps (fwd + CE + bwd + Adam, Unet-ChannalAttention.py:342-346) of the CPU "
                       f"oracle on {batch} synthetic {size}x{size}x2 tiles each ({dt:.2f} s), and 10 timed eval forwards of one "
                       f"tile (config 1); torch {torch.__version__} CPU/oneDNN, {cores} threads"}
+
+
+def dump_outputs(dirname: str, loss, net) -> None:
+    """--dump-outputs: what the last timed step handed its caller, as float32 / float64 .npy files:
+      loss.npy  - the step's loss (float64 scalar);
+      state.npy - the trained model: every floating-point entry of net.state_dict() (parameters after the Adam step,
+                  BatchNorm running statistics), flattened and concatenated in state_dict order;
+      grads.npy - the parameter gradients of the step, flattened and concatenated in parameters() order.
+    An array above DUMP_SAMPLE elements is replaced by a fixed sample of it: DUMP_SAMPLE positions of a permutation drawn
+    by torch.Generator().manual_seed(0), in increasing order (the same positions in every run of the same model)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+
+    def save(name, vec):
+        n = vec.numel()
+        if n > DUMP_SAMPLE:
+            idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            vec = vec[idx.to(vec.device)]
+        np.save(os.path.join(dirname, name + ".npy"), vec.float().cpu().numpy())
+
+    np.save(os.path.join(dirname, "loss.npy"), np.array(float(loss.detach()), dtype=np.float64))
+    save("state", torch.cat([v.detach().reshape(-1).float() for v in net.state_dict().values() if v.is_floating_point()]))
+    params = list(net.parameters())
+    if all(p.grad is not None for p in params):
+        save("grads", torch.cat([p.grad.detach().reshape(-1).float() for p in params]))
+    else:
+        print("dump-outputs: some parameters have no gradient after the step; grads.npy not written", file=sys.stderr)
 
 
 def _traffic_files():
@@ -229,14 +264,16 @@ def measure(args, world: int, rank: int, dev, dist, iu, engine, make_batch):
                    "rank_ms_per_step_min": round(1e3 * float(tmin.item()) / args.steps, 3),
                    "rank_ms_per_step_max": round(1e3 * float(tmax.item()) / args.steps, 3)}
         model.record_exposed = False
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, net)        # before the event passes below train the model further
 
-    # Roofline leg: the same K steps twice more, in the same process, with a HIP-event pair around every GEMM-class
+    # Roofline leg (--full): the same K steps twice more, in the same process, with a HIP-event pair around every GEMM-class
     # launch, recorded on the stream the kernel is launched on (main or side). Pass 1 keeps the launch configuration
     # of the timed region (weight gradients on the side stream beside the dgrad chain, split-K for engine.WGRAD_FILL of the work-group slots);
     # pass 2 runs everything on ONE stream (each kernel alone on the chip, split-K that fills it). Both are kept out
     # of the timed region above because ~130 event records per step cost host time and perturb the overlap.
     timers = {}
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         for mode in ("timed_config", "alone"):
             timer = engine.KernelTimer(alone=(mode == "alone"))
             engine.PROFILER = timer
@@ -410,7 +447,7 @@ def other_configs(args, dev, dist, iu, engine, make_batch) -> dict:
         a = copy.copy(args)
         for k, v in over.items():
             setattr(a, k, v)
-        a.no_kernel_timing, a.graph, a.stream_input = True, "off", False
+        a.no_kernel_timing, a.graph, a.stream_input, a.dump_outputs = True, "off", False, None
         a.settle = min(args.settle, 20)
         gc.collect()
         torch.cuda.empty_cache()
@@ -450,10 +487,16 @@ def main() -> int:
                          "side stream as soon as the stage's gradients are enqueued (same arithmetic, bitwise the plain step). Measured "
                          "SLOWER (7.77 -> 8.29 ms/step: 875 MB of optimizer traffic beside the dgrad chain costs more than the 0.17 ms "
                          "it hides), so off by default: optimizer.step() after backward does all of it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the per-kernel event passes (gemm_kernels, roofline), "
+                         "configs 4 and 5 (other_configs) and the CPU baseline (cpu_baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full: skip the per-kernel event passes")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip configs 4 and 5 (the default 1-GPU run of config 2 reports them under `other_configs`)")
+                    help="--full: skip configs 4 and 5 (a --full 1-GPU run of config 2 reports them under `other_configs`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's loss, trained state and gradients as DIR/<name>.npy "
+                         "(bench.dump_outputs; bench_outputs/ is ignored by git)")
     ap.add_argument("--bucket-mb", type=float, default=16.0, help="N > 1: minimum size of a gradient-exchange bucket (MiB)")
     ap.add_argument("--allow-switches", action="store_true",
                     help="measure although INSAR_* environment switches that select kernels / launch paths are set to non-default "
@@ -515,9 +558,9 @@ def main() -> int:
     if rank == 0 and isinstance(out, dict):
         out["switches"] = {k: v["value"] for k, v in sw.items()}
         out["wgrad_fill"] = {"conv3x3": engine.WGRAD_FILL, "conv3x3_small_tiles": engine.WGRAD_FILL_SMALL, "conv_transpose": engine.WGRAD_FILL_T, "deeplab": engine.WGRAD_FILL_DL}
-        if world == 1 and not args.no_other_configs and args.model == "unet" and args.dtype == "bf16" and args.size == 256:
+        if world == 1 and args.full and not args.no_other_configs and args.model == "unet" and args.dtype == "bf16" and args.size == 256:
             out["other_configs"] = other_configs(args, dev, dist, iu, engine, make_batch)
-        if world == 1 and not args.no_cpu_baseline and args.model == "unet":
+        if world == 1 and args.full and not args.no_cpu_baseline and args.model == "unet":
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -96,25 +96,49 @@ def test_history_file_schema(tmp_path):
     assert back == [{"epoch": 1, "train_loss": pytest.approx(0.7), "train_miou": 0.4, "val_loss": 0.6, "val_miou": 0.5}]
 
 
+def _reference_checkpoint(contract, seed=5):
+    """A state_dict laid out as `torch.save(model.state_dict())` of the reference writes it (G10: keys in order,
+    shapes, dtypes, per-module `_metadata` versions), filled with seeded values."""
+    import collections
+    g = torch.Generator().manual_seed(seed)
+    sd = collections.OrderedDict()
+    for k, shape, dt in zip(contract["keys"], contract["shapes"], contract["dtypes"]):
+        if dt == "int64":
+            sd[k] = torch.randint(0, 1000, shape, dtype=torch.int64, generator=g)
+        else:
+            sd[k] = torch.randn(shape, generator=g).to(getattr(torch, dt))
+    sd._metadata = collections.OrderedDict((k, dict(v)) for k, v in contract["metadata"].items())
+    return sd
+
+
+def _assert_matches_contract(sd, contract):
+    assert list(sd.keys()) == contract["keys"]
+    assert [list(v.shape) for v in sd.values()] == contract["shapes"]
+    assert [str(v.dtype).replace("torch.", "") for v in sd.values()] == contract["dtypes"]
+    assert {k: dict(v) for k, v in sd._metadata.items()} == contract["metadata"]
+
+
 def test_checkpoint_interchange_with_the_reference(tmp_path):
     """`.pth` files written by `torch.save(model.state_dict())` (the reference's checkpoint, :382-387) load
-    into the other implementation with strict=True, in both directions, key order included. In-container
-    only: the reference tree is not present on the GPU box."""
-    from oracle import ref_loader
-    if not ref_loader.reference_available():
-        pytest.skip("reference tree not mounted")
+    into the other implementation with strict=True, in both directions, key order included. The reference's
+    side is its recorded checkpoint contract (tests/golden/g10_checkpoint_contract.json, oracle/gen_golden_ckpt.py):
+    what a strict load into its UNet checks — keys, shapes — plus dtypes and module versions."""
     import insar_unet_ca_amd as iu
-    ref = ref_loader.load_reference_unet_ca()
-    theirs = ref.UNet(in_channels=1, num_classes=2, use_se=True)
+    g10 = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g10_checkpoint_contract.json")))
+    contract = g10["unet_ca_in1_se"]
     ours = iu.UNet(in_channels=1, num_classes=2, use_se=True)
-    assert list(theirs.state_dict().keys()) == list(ours.state_dict().keys())
+    _assert_matches_contract(ours.state_dict(), contract)
+    theirs = _reference_checkpoint(contract)
     p1 = os.path.join(str(tmp_path), "theirs.pth")
-    torch.save(theirs.state_dict(), p1)
+    torch.save(theirs, p1)
     ours.load_state_dict(torch.load(p1), strict=True)
-    for (k, a), (_, b) in zip(theirs.state_dict().items(), ours.state_dict().items()):
+    for (k, a), (_, b) in zip(theirs.items(), ours.state_dict().items()):
         assert a.dtype == b.dtype and torch.equal(a, b), k
     p2 = os.path.join(str(tmp_path), "ours.pth")
     torch.save(ours.state_dict(), p2)
-    theirs.load_state_dict(torch.load(p2), strict=True)
+    back = torch.load(p2)
+    _assert_matches_contract(back, contract)
+    for (k, a), (_, b) in zip(theirs.items(), back.items()):
+        assert torch.equal(a, b), k
     # Unet.py-equivalent (use_se=False) keeps the same contract minus the SE entries
-    assert list(ref.UNet(2, 2, False).state_dict().keys()) == list(iu.UNet(2, 2, False).state_dict().keys())
+    _assert_matches_contract(iu.UNet(2, 2, False).state_dict(), g10["unet_in2_nose"])

@@ -1817,7 +1817,7 @@ def test_train_loop_over_the_voc_reader(dev, tmp_path):
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
-def test_miou_within_0p3_pt_of_the_reference(dev, dtype):
+def test_miou_within_0p3_pt_of_the_reference(dev, dtype, tmp_path):
     """north_star: "mIoU within 0.3 pt of the reference on identical splits".
     tests/golden/g8c_miou_reference.json holds the held-out mIoU that the IMPORTED REFERENCE (its own UNet, train_model,
     validate_model and compute_metrics, Unet-ChannalAttention.py:100-163, 215-399; torch CPU fp32, build container,
@@ -1835,7 +1835,7 @@ def test_miou_within_0p3_pt_of_the_reference(dev, dtype):
     ref_by_seed = {r["seed"]: r["final"]["val_miou"] for r in ref["runs"]}
     seeds = sorted(ref_by_seed)[:5]
     assert len(seeds) >= 5 and ref["config"]["side"] == "reference"
-    out = os.path.join(root, "gpurun_out", f"g8c_miou_hip_{dtype}_test.json")
+    out = os.path.join(str(tmp_path), f"g8c_miou_hip_{dtype}_test.json")
     cfg = ref["config"]
     cmd = [sys.executable, os.path.join(root, "tests", "tools", "miou_experiment.py"), "--side", "hip", "--dtype", dtype,
            "--seeds", ",".join(str(s) for s in seeds), "--out", out]

@@ -8,5 +8,5 @@ for i in $(seq $N); do
   timeout -k 10 120 python3 $R/bench.py --allow-switches --steps 40 --warmup 10 --no-cpu-baseline --no-kernel-timing 2>/dev/null | python3 -c "$pick" base || exit 1
   INSAR_HIP_LIB=$EXP timeout -k 10 120 python3 $R/bench.py --allow-switches --steps 40 --warmup 10 --no-cpu-baseline --no-kernel-timing 2>/dev/null | python3 -c "$pick" exp || exit 1
 done
-timeout -k 10 200 python3 $R/bench.py --allow-switches --no-cpu-baseline 2>/dev/null | python3 -c "$pick" base || exit 1
-INSAR_HIP_LIB=$EXP timeout -k 10 200 python3 $R/bench.py --allow-switches --no-cpu-baseline 2>/dev/null | python3 -c "$pick" exp
+timeout -k 10 200 python3 $R/bench.py --full --allow-switches --no-cpu-baseline 2>/dev/null | python3 -c "$pick" base || exit 1
+INSAR_HIP_LIB=$EXP timeout -k 10 200 python3 $R/bench.py --full --allow-switches --no-cpu-baseline 2>/dev/null | python3 -c "$pick" exp

@@ -10,4 +10,4 @@ for i in 1 2 3; do
     timeout -k 10 150 python3 $R/bench.py --wgrad-fill $f --steps 40 --warmup 10 --no-cpu-baseline --no-kernel-timing --no-other-configs 2>/dev/null | python3 -c "$pick" "x=1 fill=$f" | tee -a $OUT/ab.txt
   done
 done
-timeout -k 10 300 python3 $R/bench.py --no-cpu-baseline --no-other-configs > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cut -c1-300 $OUT/bench.json
+timeout -k 10 300 python3 $R/bench.py --full --no-cpu-baseline --no-other-configs > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cut -c1-300 $OUT/bench.json

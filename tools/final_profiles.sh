@@ -13,11 +13,11 @@ echo "== pytest"; timeout -k 10 900 python3 -m pytest "$R/tests" -m gpu -q -p no
 echo "== race screens"
 RUNS=40 STEPS=24 timeout -k 10 200 python3 "$R/tools/debug_race_steps.py" 2>/dev/null | tee "$OUT/race_steps.log" || exit 1
 RUNS=600 timeout -k 10 300 python3 "$R/tools/debug_race.py" 2>/dev/null | tail -n 1 | tee "$OUT/race_step.log" || exit 1
-echo "== bench"; timeout -k 10 400 python3 "$R/bench.py" > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1
+echo "== bench"; timeout -k 10 400 python3 "$R/bench.py" --full > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1
 cut -c1-330 "$OUT/bench.json"
 echo "== phase times"; timeout -k 10 100 python3 "$R/tools/phase_times.py" 2>/dev/null | tee "$OUT/phase_times.log"
 echo "== rocprof stats (default command: timed region on two streams + the two event passes)"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/p1" -- python3 "$R/bench.py" --steps 10 --warmup 3 --settle 0 --no-cpu-baseline --no-other-configs > "$OUT/p1.log" 2>&1 || exit 1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/p1" -- python3 "$R/bench.py" --full --steps 10 --warmup 3 --settle 0 --no-cpu-baseline --no-other-configs > "$OUT/p1.log" 2>&1 || exit 1
 echo "== rocprof stats (timed region only, two streams)"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/p3" -- python3 "$R/bench.py" --steps 10 --warmup 3 --settle 0 --no-cpu-baseline --no-kernel-timing --no-other-configs > "$OUT/p3.log" 2>&1 || exit 1
 echo "== rocprof stats (single stream)"
@@ -62,7 +62,7 @@ timeout -k 10 300 python3 "$R/tools/gemm_bench.py" --what x3 --only down2.3,conv
 echo "== 2-rank rehearsal (gloo, both ranks on the one GPU: exercises the bucketed reducer inside backward)"
 timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 "$R/bench.py" --gpus 2 --steps 3 --warmup 1 --backend gloo --no-cpu-baseline --no-kernel-timing > "$OUT/bench_dp2_gloo.json" 2> "$OUT/bench_dp2_gloo.err"; cut -c1-160 "$OUT/bench_dp2_gloo.json"
 timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29534 "$R/bench.py" --gpus 2 --steps 3 --warmup 1 --backend gloo --shard-optimizer --no-cpu-baseline --no-kernel-timing > "$OUT/bench_dp2_gloo_sharded.json" 2> "$OUT/bench_dp2_gloo_sharded.err"; cut -c1-160 "$OUT/bench_dp2_gloo_sharded.json"
-echo "== config 4"; timeout -k 10 300 python3 "$R/bench.py" --dtype f32 --size 512 --batch 8 --loss ce --no-cpu-baseline > "$OUT/bench_cfg4.json" 2> "$OUT/bench_cfg4.err"; cut -c1-200 "$OUT/bench_cfg4.json"
-echo "== config 5"; timeout -k 10 300 python3 "$R/bench.py" --model deeplab --no-cpu-baseline > "$OUT/bench_cfg5.json" 2> "$OUT/bench_cfg5.err"; cut -c1-200 "$OUT/bench_cfg5.json"
+echo "== config 4"; timeout -k 10 300 python3 "$R/bench.py" --full --dtype f32 --size 512 --batch 8 --loss ce --no-cpu-baseline > "$OUT/bench_cfg4.json" 2> "$OUT/bench_cfg4.err"; cut -c1-200 "$OUT/bench_cfg4.json"
+echo "== config 5"; timeout -k 10 300 python3 "$R/bench.py" --full --model deeplab --no-cpu-baseline > "$OUT/bench_cfg5.json" 2> "$OUT/bench_cfg5.err"; cut -c1-200 "$OUT/bench_cfg5.json"
 echo done
 echo "== stand-alone pass timings"; timeout -k 10 300 python3 "$R/tools/pass_bench.py" 2>/dev/null | tee "$OUT/pass_bench.txt"
