@@ -452,6 +452,43 @@ int insar_cam_excite(const InsarCam* d, void* stream);
 int insar_cam_bwd_coef(const InsarCam* d, const float* red /*[B][rows][2][C]*/, int32_t rows, void* stream);
 int insar_cam_scatter_max(const InsarAct* dx, const float* dmax, const int32_t* arg, void* stream);
 
+/* ---- SpatialAttention (Unet-SpatialAttention.py:59-82, applied to each skip-concat at :131,137,143,149) ----------
+ * a = cat(mean_c x, max_c x); z = ReLU(BN2(conv(ReLU(BN1(conv(a, w1) + b1)), w2) + b2)); out = x * sigmoid(z).
+ * forward : insar_sa_compress -> insar_sa_conv(1) -> insar_bn_finalize(BN1, part = stat1, C = 1) -> insar_sa_conv(2)
+ *           -> insar_bn_finalize(BN2, part = stat2, C = 1) -> insar_sa_gate
+ *           (eval: the finalize calls read the running statistics; stat1 / stat2 are not written)
+ * backward: insar_sa_dscale -> insar_sa_bwd_coef(2) -> insar_sa_bwd_stencil(2) -> insar_sa_bwd_coef(1)
+ *           -> insar_sa_bwd_stencil(1) -> insar_sa_bwd_coef(0) -> insar_sa_dx
+ * The arg-max is the FIRST channel holding the maximum (torch.max(dim=1)); only that channel receives d max.
+ * C (= x.c_len) must be a multiple of 8. The fp32 maps are [B][H][W] unless noted; every reduction is a fixed
+ * partition of the image rows over `rows` work-groups, folded in a fixed order (bitwise reproducible). */
+typedef struct InsarSa {
+  InsarAct x;          /* the concat (un-gated) */
+  InsarAct y;          /* forward: gated output (same geometry and dtype); backward: d out, overwritten with d x */
+  float* comp;         /* [B][H+2][W+2][2] (mean, max), zero halo */
+  uint16_t* arg;       /* first arg-max channel */
+  float* z1; float* z2;  /* raw conv outputs (without bias) */
+  float* s;            /* sigmoid gate */
+  float* g2; float* g1;  /* backward: gradient wrt the BN2 / BN1 outputs (ReLU mask applied) */
+  float* dcomp;        /* backward: [B][H][W][2] (d mean, d max) */
+  float* stat1; float* stat2;  /* forward: [rows][2] BatchNorm partial sums (sum, sum of squares) */
+  float* part;         /* backward: [rows][20] partial sums */
+  int32_t rows;        /* work-groups of the row-partitioned passes, 1..4096 */
+  int32_t training;
+  const float* w1; const float* w2;  /* conv weights (1,2,3,3), (1,1,3,3) */
+  const float* bn;     /* [8] scale1, shift1, mean1, invstd1, scale2, shift2, mean2, invstd2 (insar_bn_finalize outputs) */
+  float* coef;         /* [4] backward: BN2 k1, k2; BN1 k1, k2 */
+  float* dw1; float* db1; float* dgamma1; float* dbeta1;   /* gradients (db1 / db2 nullable) */
+  float* dw2; float* db2; float* dgamma2; float* dbeta2;
+} InsarSa;
+int insar_sa_compress(const InsarSa* d, void* stream);
+int insar_sa_conv(const InsarSa* d, int32_t which /* 1 | 2 */, void* stream);
+int insar_sa_gate(const InsarSa* d, void* stream);
+int insar_sa_dscale(const InsarSa* d, void* stream);
+int insar_sa_bwd_coef(const InsarSa* d, int32_t stage /* 2, 1, 0 */, void* stream);
+int insar_sa_bwd_stencil(const InsarSa* d, int32_t which /* 2 | 1 */, void* stream);
+int insar_sa_dx(const InsarSa* d, void* stream);
+
 /* ---- MaxPool2d(2) (:106-109): y is the (H/2, W/2) grid rounded down (an odd last row / column belongs to no window) ---- */
 int insar_maxpool2_fwd(const InsarAct* x, const InsarAct* y, void* stream);
 /* dx (+)= route(dy) to the first maximum in scan order (torch semantics). */

@@ -78,6 +78,16 @@ class InsarCam(C.Structure):
                 ("dw1", C.c_void_p), ("dw2", C.c_void_p), ("accumulate", C.c_int32), ("_pad", C.c_int32)]
 
 
+class InsarSa(C.Structure):
+    _fields_ = [("x", InsarAct), ("y", InsarAct), ("comp", C.c_void_p), ("arg", C.c_void_p),
+                ("z1", C.c_void_p), ("z2", C.c_void_p), ("s", C.c_void_p), ("g2", C.c_void_p), ("g1", C.c_void_p),
+                ("dcomp", C.c_void_p), ("stat1", C.c_void_p), ("stat2", C.c_void_p), ("part", C.c_void_p),
+                ("rows", C.c_int32), ("training", C.c_int32), ("w1", C.c_void_p), ("w2", C.c_void_p),
+                ("bn", C.c_void_p), ("coef", C.c_void_p),
+                ("dw1", C.c_void_p), ("db1", C.c_void_p), ("dgamma1", C.c_void_p), ("dbeta1", C.c_void_p),
+                ("dw2", C.c_void_p), ("db2", C.c_void_p), ("dgamma2", C.c_void_p), ("dbeta2", C.c_void_p)]
+
+
 _P = C.c_void_p
 _I = C.c_int32
 _L = C.c_int64
@@ -157,6 +167,13 @@ _SIGNATURES = {
     "insar_cam_excite": [C.POINTER(InsarCam), _P],
     "insar_cam_bwd_coef": [C.POINTER(InsarCam), _P, _I, _P],
     "insar_cam_scatter_max": [_AP, _P, _P, _P],
+    "insar_sa_compress": [C.POINTER(InsarSa), _P],
+    "insar_sa_conv": [C.POINTER(InsarSa), _I, _P],
+    "insar_sa_gate": [C.POINTER(InsarSa), _P],
+    "insar_sa_dscale": [C.POINTER(InsarSa), _P],
+    "insar_sa_bwd_coef": [C.POINTER(InsarSa), _I, _P],
+    "insar_sa_bwd_stencil": [C.POINTER(InsarSa), _I, _P],
+    "insar_sa_dx": [C.POINTER(InsarSa), _P],
     "insar_resize_bilinear_fwd": [_AP, _AP, _P],
     "insar_resize_bilinear_bwd": [_AP, _AP, _P],
     "insar_maxpool2_fwd": [_AP, _AP, _P],

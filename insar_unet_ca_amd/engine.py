@@ -16,7 +16,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import _lib, tape
-from ._lib import InsarAct, InsarBnFinalize, InsarBnSeBwd, InsarIgemm, InsarSeFwd, InsarWgrad, call, ptr
+from ._lib import InsarAct, InsarBnFinalize, InsarBnSeBwd, InsarIgemm, InsarSa, InsarSeFwd, InsarWgrad, call, ptr
 from .tape import tape_py
 
 BN_ROW_PIX = 128        # igemm M-tile (rows of one stats slab row)
@@ -634,9 +634,12 @@ def grad_groups(net) -> List[List[torch.nn.Parameter]]:
     ups = [net.up1, net.up2, net.up3, net.up4]
     convs = [net.conv1, net.conv2, net.conv3, net.conv4]
     encs = [net.inc, net.down1[1], net.down2[1], net.down3[1], net.down4[1]]
-    groups = [[net.outc.weight, net.outc.bias] + double_conv_params(convs[3]) + [ups[3].weight, ups[3].bias]]
+    # the SA U-Net (spatial.UNet): sa{i+1} runs between conv{i+1} and up{i+1} in backward, so it joins decoder stage i
+    sas = [getattr(net, f"sa{i + 1}") for i in range(4)] if getattr(net, "spatial_attention", False) else None
+    sa = lambda i: double_conv_params(sas[i].compress_and_map) if sas else []
+    groups = [[net.outc.weight, net.outc.bias] + double_conv_params(convs[3]) + sa(3) + [ups[3].weight, ups[3].bias]]
     for i in (2, 1, 0):
-        groups.append(double_conv_params(convs[i]) + [ups[i].weight, ups[i].bias])
+        groups.append(double_conv_params(convs[i]) + sa(i) + [ups[i].weight, ups[i].bias])
     for l in (4, 3, 2, 1, 0):
         groups.append(double_conv_params(encs[l]))
     return groups
@@ -1149,6 +1152,101 @@ class DoubleConvPlan:
         self.u1.backward(self.dz1, sink, training, None, dx)
 
 
+SA_ROWS = 1024        # work-groups (= partial-sum rows) of the row-partitioned SpatialAttention passes
+
+
+class SAUnit:
+    """SpatialAttention (Unet-SpatialAttention.py:59-82) on a concat buffer `x`, gated output in `y` (csrc/spatial_attn.hip):
+    out = x * sigmoid(DoubleConv(2, 1)(cat(mean_c x, max_c x))). backward() overwrites the output gradient with the input
+    gradient in place."""
+
+    def __init__(self, ctx: Ctx, mod, x: Act, y: Act, name: str):
+        self.ctx, self.mod, self.x, self.y, self.name = ctx, mod, x, y, name
+        seq = mod.compress_and_map.double_conv
+        self.conv1, self.bn1, self.conv2, self.bn2 = seq[0], seq[1], seq[3], seq[4]
+        if tuple(self.conv1.weight.shape) != (1, 2, 3, 3) or tuple(self.conv2.weight.shape) != (1, 1, 3, 3):
+            raise _lib.InsarError(f"{name}: compress_and_map must be DoubleConv(2, 1)")
+        Cn = x.c_len
+        if Cn % 8 or Cn > 65535:
+            raise _lib.InsarError(f"{name}: SpatialAttention needs the channel count to be a multiple of 8 (<= 65535), got {Cn}")
+        B, H, W = x.B, x.H, x.W
+        self.M = M = B * H * W
+        dev = ctx.device
+        self.comp = torch.zeros((B, H + 2, W + 2, 2), dtype=torch.float32, device=dev)
+        self.arg = torch.zeros(M, dtype=torch.int16, device=dev)          # uint16 bits
+        self.maps = ctx.f32(5, M)                                         # z1, z2, s, g2, g1
+        self.dcomp = ctx.f32(M, 2)
+        self.rows = min(B * H, SA_ROWS)
+        self.stat1, self.stat2 = ctx.f32(self.rows, 2), ctx.f32(self.rows, 2)
+        self.part = ctx.f32(self.rows, 20)
+        self.bn = ctx.f32(8)
+        self.coef = ctx.f32(4)
+
+    def params(self) -> List[torch.nn.Parameter]:
+        return double_conv_params(self.mod.compress_and_map)
+
+    def _desc(self) -> InsarSa:
+        """Descriptor of this unit's buffers and parameters (built per call: see forward)."""
+        d = InsarSa()
+        d.x, d.y = self.x.desc, self.y.desc
+        d.comp, d.arg, d.dcomp = ptr(self.comp), ptr(self.arg), ptr(self.dcomp)
+        d.z1, d.z2, d.s, d.g2, d.g1 = (ptr(self.maps[k]) for k in range(5))
+        d.stat1, d.stat2, d.part, d.rows = ptr(self.stat1), ptr(self.stat2), ptr(self.part), self.rows
+        d.w1, d.w2 = ptr(self.conv1.weight), ptr(self.conv2.weight)
+        d.bn, d.coef = ptr(self.bn), ptr(self.coef)
+        return d
+
+    def _finalize(self, conv, bn, stat, k: int, training: bool, s) -> None:
+        d = InsarBnFinalize()
+        d.part, d.rows, d.count, d.C, d.training = ptr(stat), self.rows, self.M, 1, int(training)
+        d.conv_bias = ptr(conv.bias)
+        d.gamma, d.beta = ptr(bn.weight), ptr(bn.bias)
+        d.running_mean, d.running_var = ptr(bn.running_mean), ptr(bn.running_var)
+        d.num_batches_tracked = ptr(bn.num_batches_tracked)
+        d.momentum = bn.momentum if bn.momentum is not None else 0.1
+        d.eps = bn.eps
+        base = self.bn.data_ptr() + 16 * k
+        d.scale, d.shift, d.mean, d.invstd = base, base + 4, base + 8, base + 12
+        call("insar_bn_finalize", C.byref(d), s)
+
+    def forward(self, training: bool, sync=None) -> None:
+        if sync:
+            raise _lib.InsarError(f"{self.name}: synchronised BatchNorm (DataParallel(sync_bn=True)) is not supported for "
+                                  "SpatialAttention; use sync_bn=False")
+        if training and self.M <= 1:
+            raise ValueError("Expected more than 1 value per channel when training, got input size "
+                             f"torch.Size([{self.x.B}, 1, {self.x.H}, {self.x.W}])")
+        s = _lib.stream_ptr()
+        # a fresh descriptor per call, as for every other launch: a launch tape keeps the struct it recorded, and the
+        # parameter pointers are re-read on every ordinary call (tensors re-assigned with p.data = ... / assign=True)
+        d = self._desc()
+        d.training = int(training)
+        ref = C.byref(d)
+        call("insar_sa_compress", ref, s)
+        call("insar_sa_conv", ref, 1, s)
+        self._finalize(self.conv1, self.bn1, self.stat1, 0, training, s)
+        call("insar_sa_conv", ref, 2, s)
+        self._finalize(self.conv2, self.bn2, self.stat2, 1, training, s)
+        call("insar_sa_gate", ref, s)
+
+    def backward(self, dout: Act, sink: GradSink, training: bool) -> None:
+        """dout: gradient wrt the gated output, same geometry as x; overwritten with the gradient wrt x."""
+        s = _lib.stream_ptr()
+        d = self._desc()
+        d.y, d.training = dout.desc, int(training)
+        v = lambda p: ptr(sink.view(p))
+        d.dw1, d.db1, d.dgamma1, d.dbeta1 = v(self.conv1.weight), v(self.conv1.bias), v(self.bn1.weight), v(self.bn1.bias)
+        d.dw2, d.db2, d.dgamma2, d.dbeta2 = v(self.conv2.weight), v(self.conv2.bias), v(self.bn2.weight), v(self.bn2.bias)
+        ref = C.byref(d)
+        call("insar_sa_dscale", ref, s)
+        call("insar_sa_bwd_coef", ref, 2, s)
+        call("insar_sa_bwd_stencil", ref, 2, s)
+        call("insar_sa_bwd_coef", ref, 1, s)
+        call("insar_sa_bwd_stencil", ref, 1, s)
+        call("insar_sa_bwd_coef", ref, 0, s)
+        call("insar_sa_dx", ref, s)
+
+
 class UpPlan:
     """ConvTranspose2d(k=2, s=2) (:112,115,118,121) writing the upper half of a concat buffer."""
 
@@ -1368,6 +1466,10 @@ class UNetPlan(tape.PlanTape):
         self.dx5 = A(4, widths[4])
         self.dpooled = [A(l + 1, widths[l]) for l in range(4)]
         self.ddec = [A(l, widths[l]) for l in range(4)]
+        # the SA U-Net (spatial.UNet): each concat goes through SpatialAttention into a gated copy `gcat[l]` that the decoder
+        # block reads (the un-gated encoder half of `cat` is still needed by the max-pool backward)
+        sa_mods = [getattr(net, f"sa{i + 1}") for i in range(4)] if getattr(net, "spatial_attention", False) else None
+        self.gcat = [A(l, 2 * widths[l]) for l in range(4)] if sa_mods else None
 
         self.enc: List[DoubleConvPlan] = []
         enc_mods = [net.inc] + [d[1] for d in downs]
@@ -1389,7 +1491,9 @@ class UNetPlan(tape.PlanTape):
             l = 3 - i
             src = self.x5 if i == 0 else self.dec[l + 1]
             self.up.append(UpPlan(ctx, ups[i], src, self.cat[l].slice(widths[l], widths[l]), f"up{i + 1}"))
-            self.dconv.append(DoubleConvPlan(ctx, convs[i], self.cat[l], self.dec[l], f"conv{i + 1}"))
+            self.dconv.append(DoubleConvPlan(ctx, convs[i], self.gcat[l] if sa_mods else self.cat[l], self.dec[l], f"conv{i + 1}"))
+        self.sa: Optional[List[SAUnit]] = ([SAUnit(ctx, sa_mods[i], self.cat[3 - i], self.gcat[3 - i], f"sa{i + 1}") for i in range(4)]
+                                           if sa_mods else None)
         self.outc = OutConvPlan(ctx, net.outc, self.dec[0])
         # parameters in the order their gradients complete during backward, grouped by backward stage
         groups = grad_groups(net)
@@ -1406,6 +1510,8 @@ class UNetPlan(tape.PlanTape):
         gws += [u.w for u in self.up]
         self.weightset = WeightSet(ctx, gws)
         self.bn_modules = [u.bn for b in self.enc + self.dconv for u in (b.u1, b.u2)]
+        if self.sa:
+            self.bn_modules += [bn for u in self.sa for bn in (u.bn1, u.bn2)]
         self._tape_setup()
 
     def bucket_closes(self, min_elems: int):
@@ -1486,10 +1592,14 @@ class UNetPlan(tape.PlanTape):
             if gate:
                 gate(3 - i)
             self.up[i].forward()
+            if self.sa:
+                self.sa[i].forward(training, sync)
             self.dconv[i].forward(training, sync=sync)
         if gate:
             gate(0)
         self.up[3].forward()
+        if self.sa:
+            self.sa[3].forward(training, sync)
         if self.outc.virtual_grad_ok():      # last block: BN/ReLU/gate + outc in one pass, no 64-channel output tensor
             return self.dconv[3].forward(training, self.outc, sync=sync)
         self.dconv[3].forward(training, sync=sync)
@@ -1525,6 +1635,8 @@ class UNetPlan(tape.PlanTape):
             self.dconv[i].backward(None if og else self.ddec[l], sink, training, self.dcat[l], og)
             if og and wg:
                 self.outc.fold_fused(sink)
+            if self.sa:
+                self.sa[i].backward(self.dcat[l], sink, training)
             dsrc = self.dx5 if i == 0 else self.ddec[l + 1]
             self.up[i].backward(self.dcat[l].slice(w[l], w[l]), sink, dsrc, self.enc[4] if i == 0 else self.dconv[i - 1])
             if on_bucket is not None:

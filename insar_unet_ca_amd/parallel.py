@@ -28,7 +28,7 @@ from typing import Callable, List, Optional, Tuple
 import torch
 import torch.distributed as dist
 
-from . import engine
+from . import _lib, engine
 
 
 class BucketReducer:
@@ -141,6 +141,10 @@ class DataParallel(torch.nn.Module):
         super().__init__()
         if not dist.is_initialized():
             raise RuntimeError("torch.distributed must be initialised before wrapping a model in DataParallel")
+        if sync_bn and getattr(module, "spatial_attention", False):
+            # the 1-channel BatchNorms of the SA U-Net's SpatialAttention units have no synchronised path
+            raise _lib.InsarError("DataParallel(sync_bn=True) is not supported for the SA U-Net (spatial.UNet): its "
+                                  "SpatialAttention BatchNorms would keep per-replica statistics; use sync_bn=False")
         self.module = module
         self.pg = process_group
         self.reducer = BucketReducer(process_group)
