@@ -557,6 +557,10 @@ int insar_maxpool3s2_bwd(const InsarAct* dy, const uint8_t* arg, const InsarAct*
 int insar_bn_add_relu(const InsarAct* y, const float* scale, const float* shift, const InsarAct* res, const InsarAct* dst,
                       int32_t relu, void* stream);
 int insar_relu_gate_bwd(const InsarAct* dout, const InsarAct* out, const InsarAct* g, void* stream);
+/* SE-gated Bottleneck tail (FCN-ResNet50 with BottleneckWithSE): dst = relu(gate[n][c] * (y*scale + shift) + res), gate
+ * fp32 [B][C] from insar_se_excite. C's 16-byte chunks (8 bf16 / 4 fp32 channels) must divide or be a multiple of 256. */
+int insar_se_res_apply(const InsarAct* y, const float* scale, const float* shift, const float* gate, const InsarAct* res,
+                       const InsarAct* dst, void* stream);
 /* ASPP pooling branch: out (B,1,1,C) = factor * sum_hw x;  dst (B,H,W,C) (+)= factor * src (B,1,1,C). */
 int insar_sum_hw(const InsarAct* x, const InsarAct* out, float factor, void* stream);
 int insar_broadcast_hw(const InsarAct* src, const InsarAct* dst, float factor, int32_t accumulate, void* stream);

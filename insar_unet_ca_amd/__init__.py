@@ -5,6 +5,7 @@ from .data import DevicePrefetcher, ShardedSampler, SyntheticTiles, VOCSegDatase
 from .loss import CrossEntropyLoss, DiceCELoss, DiceLoss  # noqa: F401
 from .modules import ChannelAttentionModule, DoubleConv, MaxPool2d, SELayer, UNet  # noqa: F401
 from .deeplab import DeepLabV3_SingleChannel_Attn  # noqa: F401
+from .fcn import FCN_SingleChannel, FCN_SingleChannel_SE  # noqa: F401
 from .spatial import SpatialAttention, UNet as UNetSpatialAttention  # noqa: F401
 from .optim import Adam  # noqa: F401
 from .graph import GraphedTrainStep  # noqa: F401
@@ -13,4 +14,4 @@ from .train import compute_metrics, save_history, train_model, validate_model  #
 __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "ChannelAttentionModule", "MaxPool2d", "CrossEntropyLoss", "DiceLoss", "DiceCELoss", "Adam", "GraphedTrainStep",
            "compute_metrics", "train_model", "validate_model", "save_history", "VOCSegDataset", "SyntheticTiles",
            "ShardedSampler", "DevicePrefetcher", "make_loader", "reference_transforms", "InsarError", "LIB_PATH",
-           "SpatialAttention", "UNetSpatialAttention"]
+           "SpatialAttention", "UNetSpatialAttention", "FCN_SingleChannel", "FCN_SingleChannel_SE"]

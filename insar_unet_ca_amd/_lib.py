@@ -199,6 +199,7 @@ _SIGNATURES = {
     "insar_maxpool3s2_bwd": [_AP, _P, _AP, _P],
     "insar_bn_add_relu": [_AP, _P, _P, _AP, _AP, _I, _P],
     "insar_relu_gate_bwd": [_AP, _AP, _AP, _P],
+    "insar_se_res_apply": [_AP, _P, _P, _P, _AP, _AP, _P],
     "insar_sum_hw": [_AP, _AP, _F, _P],
     "insar_broadcast_hw": [_AP, _AP, _F, _I, _P],
     "insar_broadcast_hw_gate": [_AP, _AP, _AP, _F, _I, _P],

@@ -762,8 +762,155 @@ static int check_out(const InsarAct* x, int K, const char* who) {
   return INSAR_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Wide inputs (64 < C / chunk <= 128: the FCN head's 512 channels in fp32): one wave per pixel, lane l owns the chunks
+// l and l + 64, the channel sum is a fixed wave_sum tree. The paths above keep every narrower input, bit for bit.
+// ---------------------------------------------------------------------------------------------
+#define DR_WIDE_CPL 2
+
+template <typename T>
+__device__ __forceinline__ void wide_load(const ActView& x, int n, int h, int w, int lane, int cpp, float (&f)[DR_WIDE_CPL][Chunk<T>::N]) {
+  constexpr int CH = Chunk<T>::N;
+#pragma unroll
+  for (int u = 0; u < DR_WIDE_CPL; ++u) {
+    const int cc = lane + 64 * u;
+    if (cc < cpp) Chunk<T>::unpack(*(const uint4*)(x.base + (x.elem_offset(n, h, w) + (int64_t)cc * CH) * (int64_t)sizeof(T)), f[u]);
+    else {
+#pragma unroll
+      for (int j = 0; j < CH; ++j) f[u][j] = 0.f;
+    }
+  }
+}
+
+template <typename T>
+__global__ void conv1x1_out_fwd_wide_kernel(ActView x, const float* __restrict__ wt, const float* __restrict__ bias,
+                                            float* __restrict__ logits, int K) {
+  constexpr int CH = Chunk<T>::N;
+  const int C = x.c_len, cpp = C / CH;
+  const int lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+  const int64_t HW = (int64_t)x.H * x.W, P = (int64_t)x.B * HW;
+  for (int64_t p = (int64_t)blockIdx.x * nw + (threadIdx.x >> 6); p < P; p += (int64_t)gridDim.x * nw) {
+    const int n = (int)(p / HW);
+    const int64_t q = p - (int64_t)n * HW;
+    const int h = (int)(q / x.W), w = (int)(q - (int64_t)h * x.W);
+    float f[DR_WIDE_CPL][CH];
+    wide_load<T>(x, n, h, w, lane, cpp, f);
+    for (int k = 0; k < K; ++k) {
+      float a = 0.f;
+#pragma unroll
+      for (int u = 0; u < DR_WIDE_CPL; ++u) {
+        const int cc = lane + 64 * u;
+        if (cc < cpp) {
+#pragma unroll
+          for (int j = 0; j < CH; ++j) a = fmaf(f[u][j], wt[(int64_t)k * C + cc * CH + j], a);
+        }
+      }
+      a = wave_sum(a);
+      if (lane == 0) logits[((int64_t)n * K + k) * HW + q] = a + (bias ? bias[k] : 0.f);
+    }
+  }
+}
+
+// dx (nullable) = sum_k dl W[k];  part[block][K*C + K] = this block's sums of dl * x and of dl, its waves folded in order
+template <typename T>
+__global__ void conv1x1_out_bwd_wide_kernel(ActView x, const float* __restrict__ wt, const float* __restrict__ dl, int K,
+                                            ActView dx, float* __restrict__ part) {
+  constexpr int CH = Chunk<T>::N;
+  extern __shared__ float sp[];                      // [K*C + K]
+  const int C = x.c_len, cpp = C / CH;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int64_t HW = (int64_t)x.H * x.W, P = (int64_t)x.B * HW;
+  float aw[DR_MAXK][DR_WIDE_CPL][CH], ab[DR_MAXK];
+#pragma unroll
+  for (int k = 0; k < DR_MAXK; ++k) {
+    ab[k] = 0.f;
+#pragma unroll
+    for (int u = 0; u < DR_WIDE_CPL; ++u)
+#pragma unroll
+      for (int j = 0; j < CH; ++j) aw[k][u][j] = 0.f;
+  }
+  for (int64_t p = (int64_t)blockIdx.x * nw + wave; p < P; p += (int64_t)gridDim.x * nw) {
+    const int n = (int)(p / HW);
+    const int64_t q = p - (int64_t)n * HW;
+    const int h = (int)(q / x.W), w = (int)(q - (int64_t)h * x.W);
+    float f[DR_WIDE_CPL][CH], o[DR_WIDE_CPL][CH];
+    wide_load<T>(x, n, h, w, lane, cpp, f);
+#pragma unroll
+    for (int u = 0; u < DR_WIDE_CPL; ++u)
+#pragma unroll
+      for (int j = 0; j < CH; ++j) o[u][j] = 0.f;
+#pragma unroll
+    for (int k = 0; k < DR_MAXK; ++k) {
+      if (k < K) {
+        const float g = dl[((int64_t)n * K + k) * HW + q];
+#pragma unroll
+        for (int u = 0; u < DR_WIDE_CPL; ++u) {
+          const int cc = lane + 64 * u;
+          if (cc < cpp) {
+#pragma unroll
+            for (int j = 0; j < CH; ++j) {
+              o[u][j] = fmaf(g, wt[(int64_t)k * C + cc * CH + j], o[u][j]);
+              aw[k][u][j] = fmaf(g, f[u][j], aw[k][u][j]);
+            }
+          }
+        }
+        ab[k] += g;
+      }
+    }
+    if (dx.base) {
+#pragma unroll
+      for (int u = 0; u < DR_WIDE_CPL; ++u) {
+        const int cc = lane + 64 * u;
+        if (cc < cpp) *(uint4*)(dx.base + (dx.elem_offset(n, h, w) + (int64_t)cc * CH) * (int64_t)sizeof(T)) = Chunk<T>::pack(o[u]);
+      }
+    }
+  }
+  // fold the waves in wave order through one LDS row
+  const int pw = K * C + K;
+  for (int wv = 0; wv < nw; ++wv) {
+    if (wave == wv) {
+#pragma unroll
+      for (int k = 0; k < DR_MAXK; ++k) {
+        if (k < K) {
+#pragma unroll
+          for (int u = 0; u < DR_WIDE_CPL; ++u) {
+            const int cc = lane + 64 * u;
+            if (cc < cpp) {
+#pragma unroll
+              for (int j = 0; j < CH; ++j) {
+                float* d = sp + k * C + cc * CH + j;
+                *d = wv == 0 ? aw[k][u][j] : *d + aw[k][u][j];
+              }
+            }
+          }
+          if (lane == 0) sp[K * C + k] = wv == 0 ? ab[k] : sp[K * C + k] + ab[k];
+        }
+      }
+    }
+    __syncthreads();
+  }
+  for (int o = threadIdx.x; o < pw; o += blockDim.x) part[(int64_t)blockIdx.x * pw + o] = sp[o];
+}
+
+static int wide_out(const InsarAct* x) {
+  const int ch = x->dtype == INSAR_BF16 ? 8 : 4;
+  const int cpp = x->c_len / ch;
+  return x->c_len % ch == 0 && cpp > 64 && cpp <= 64 * DR_WIDE_CPL;
+}
+
 extern "C" int insar_conv1x1_out_fwd(const InsarAct* x, const float* w, const float* bias, float* logits, int32_t K, void* stream) {
   int rc;
+  if (x && wide_out(x)) {
+    if ((rc = insar_check_act(x, "insar_conv1x1_out_fwd", "x"))) return rc;
+    if (K < 1 || K > DR_MAXK) INSAR_FAIL(INSAR_E_SHAPE, "insar_conv1x1_out_fwd: num_classes=%d must be 1..%d", K, DR_MAXK);
+    if (!w || !logits) INSAR_FAIL(INSAR_E_ARG, "insar_conv1x1_out_fwd: null pointer");
+    const int grid = insar_grid_cap(((int64_t)x->B * x->H * x->W + 3) / 4);
+    hipStream_t s = (hipStream_t)stream;
+    if (x->dtype == INSAR_BF16) hipLaunchKernelGGL(conv1x1_out_fwd_wide_kernel<bf16_t>, dim3(grid), dim3(DR_THREADS), 0, s, make_view(*x), w, bias, logits, K);
+    else hipLaunchKernelGGL(conv1x1_out_fwd_wide_kernel<float>, dim3(grid), dim3(DR_THREADS), 0, s, make_view(*x), w, bias, logits, K);
+    INSAR_CHECK_LAUNCH("insar_conv1x1_out_fwd");
+    return INSAR_OK;
+  }
   if ((rc = check_out(x, K, "insar_conv1x1_out_fwd"))) return rc;
   if (!w || !logits) INSAR_FAIL(INSAR_E_ARG, "insar_conv1x1_out_fwd: null pointer");
   size_t lds = (size_t)K * x->c_len * sizeof(float);
@@ -894,6 +1041,21 @@ extern "C" int insar_conv1x1_out_bwd_blocks(int32_t B, int32_t H) {
 extern "C" int insar_conv1x1_out_bwd(const InsarAct* x, const float* w, const float* dlogits, int32_t K,
                                      const InsarAct* dx, float* part, void* stream) {
   int rc;
+  if (x && wide_out(x)) {
+    if ((rc = insar_check_act(x, "insar_conv1x1_out_bwd", "x"))) return rc;
+    if ((rc = insar_check_act(dx, "insar_conv1x1_out_bwd", "dx"))) return rc;
+    if (K < 1 || K > DR_MAXK) INSAR_FAIL(INSAR_E_SHAPE, "insar_conv1x1_out_bwd: num_classes=%d must be 1..%d", K, DR_MAXK);
+    if (!w || !dlogits || !part) INSAR_FAIL(INSAR_E_ARG, "insar_conv1x1_out_bwd: null pointer");
+    if (x->B != dx->B || x->H != dx->H || x->W != dx->W || x->c_len != dx->c_len || x->dtype != dx->dtype)
+      INSAR_FAIL(INSAR_E_SHAPE, "insar_conv1x1_out_bwd: x/dx mismatch");
+    const size_t lds = (size_t)(K * x->c_len + K) * sizeof(float);
+    const int grid = insar_conv1x1_out_bwd_blocks(x->B, x->H);
+    hipStream_t s = (hipStream_t)stream;
+    if (x->dtype == INSAR_BF16) hipLaunchKernelGGL(conv1x1_out_bwd_wide_kernel<bf16_t>, dim3(grid), dim3(DR_THREADS), lds, s, make_view(*x), w, dlogits, K, make_view(*dx), part);
+    else hipLaunchKernelGGL(conv1x1_out_bwd_wide_kernel<float>, dim3(grid), dim3(DR_THREADS), lds, s, make_view(*x), w, dlogits, K, make_view(*dx), part);
+    INSAR_CHECK_LAUNCH("insar_conv1x1_out_bwd");
+    return INSAR_OK;
+  }
   if ((rc = check_out(x, K, "insar_conv1x1_out_bwd"))) return rc;
   if ((rc = insar_check_act(dx, "insar_conv1x1_out_bwd", "dx"))) return rc;
   if (!w || !dlogits || !part) INSAR_FAIL(INSAR_E_ARG, "insar_conv1x1_out_bwd: null pointer");

@@ -292,7 +292,9 @@ class ConvUnit:
         return 8 | (16 if narrow else 0) | ((self.d << 8) if self.d > 1 else 0)
 
     # ---- forward ------------------------------------------------------------------------------------------
-    def forward(self, training: bool) -> None:
+    def forward(self, training: bool, apply: bool = True) -> None:
+        """apply=False: the convolution and the BatchNorm statistics only (scale / shift ready, `out` not written: the
+        SE-gated residual tail of fcn.SEBottleneckPlan applies them itself)."""
         s = _lib.stream_ptr()
         if training and self.M <= 1:
             raise ValueError("Expected more than 1 value per channel when training, got input size "
@@ -315,6 +317,8 @@ class ConvUnit:
         d.eps = bn.eps
         d.scale, d.shift, d.mean, d.invstd = ptr(self.scale), ptr(self.shift), ptr(self.mean), ptr(self.invstd)
         call("insar_bn_finalize", C.byref(d), s)
+        if not apply:
+            return
         if self.res is not None:
             call("insar_bn_add_relu", self.y.ref, ptr(self.scale), ptr(self.shift), self.res.ref, self.out.ref, int(self.relu), s)
         else:
@@ -450,6 +454,10 @@ class ConvUnit:
 
 
 class BottleneckPlan:
+    # the consumer's gating dgrad GEMM may also take this block's conv3 BatchNorm-backward sums (over the whole batch) in its
+    # epilogue (`plain_for`); fcn.SEBottleneckPlan needs them per image and turns this off
+    plain_sums = True
+
     def __init__(self, ctx: Ctx, mod: Bottleneck, x: Act, name: str):
         self.ctx, self.mod, self.x, self.name = ctx, mod, x, name
         self.u1 = ConvUnit(ctx, mod.conv1, mod.bn1, x, None, True, name + ".conv1")
@@ -501,16 +509,21 @@ class BottleneckPlan:
         self.dout_gated = False
         last = self.u1 if self.ud is None else self.ud
         gate = self.x if (GATE_FUSE and producer is not None and producer.out is self.x and last.can_gate()) else None
-        self.u3.backward(g, sink, training, self.dz2, relu=False, bstat_for=self.u2)
+        plain_for = producer.u3 if gate is not None and producer.plain_sums else None
+        self._tail_backward(g, sink, training)
         self.u2.backward(self.dz2, sink, training, self.dz1, bstat_for=self.u1)
         if self.ud is None:
             self.u1.backward(self.dz1, sink, training, dx, add=g, gate=gate,            # identity branch: dx = dgrad + g
-                             plain_for=producer.u3 if gate is not None else None)
+                             plain_for=plain_for)
         else:
             self.u1.backward(self.dz1, sink, training, dx)
-            self.ud.backward(g, sink, training, dx, relu=False, add=dx, gate=gate, plain_for=producer.u3 if gate is not None else None)
+            self.ud.backward(g, sink, training, dx, relu=False, add=dx, gate=gate, plain_for=plain_for)
         if gate is not None:
             producer.dout_gated = True
+
+    def _tail_backward(self, g: Act, sink: GradSink, training: bool) -> None:
+        """bn3 / conv3 backward from the gated incoming gradient g (into dz2)."""
+        self.u3.backward(g, sink, training, self.dz2, relu=False, bstat_for=self.u2)
 
 
 class DeepLabPlan(tape.PlanTape):

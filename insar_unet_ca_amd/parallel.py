@@ -145,6 +145,9 @@ class DataParallel(torch.nn.Module):
             # the 1-channel BatchNorms of the SA U-Net's SpatialAttention units have no synchronised path
             raise _lib.InsarError("DataParallel(sync_bn=True) is not supported for the SA U-Net (spatial.UNet): its "
                                   "SpatialAttention BatchNorms would keep per-replica statistics; use sync_bn=False")
+        if sync_bn and getattr(module, "sync_bn_unsupported", None):
+            raise _lib.InsarError(f"DataParallel(sync_bn=True) is not supported for {type(module).__name__}: "
+                                  f"{module.sync_bn_unsupported}; use sync_bn=False")
         self.module = module
         self.pg = process_group
         self.reducer = BucketReducer(process_group)
@@ -192,7 +195,8 @@ class DataParallel(torch.nn.Module):
     def _flatten_parameters(self) -> None:
         """Move every parameter into ONE flat fp32 buffer with the gradient buffer's layout (engine.flat_layout over
         engine.grad_groups); the nn.Parameters become views of it. Cached plans hold raw pointers: dropped."""
-        groups = engine.grad_groups(self.module)
+        own = getattr(self.module, "grad_groups", None)       # nets whose plan lays out its own stages (fcn.py)
+        groups = own() if callable(own) else engine.grad_groups(self.module)
         params = [p for g in groups for p in g]
         if len({id(p) for p in params}) != len(list(self.module.parameters())):
             raise RuntimeError("shard_optimizer: the flat layout does not cover every parameter of the module")
