@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define INSAR_ABI_VERSION 6
+#define INSAR_ABI_VERSION 7
 
 enum { INSAR_F32 = 0, INSAR_BF16 = 1 };
 
@@ -529,6 +529,33 @@ int insar_dice_ce(const float* logits, const int64_t* target, int32_t B, int32_t
 /* ---- metrics (compute_metrics, :215-269): argmax (ties -> lower class) + TP/FP/FN counts -------- */
 int insar_confusion(const float* logits, const int64_t* target, int32_t B, int32_t K, int64_t HW,
                     int64_t ignore_index, int64_t* counts /*[3][K], zeroed by the call*/, void* stream);
+
+/* ---- whole-scene inference (build-side addition; the reference stops at fixed-size tiles): csrc/scene.hip -----------
+ * A scene [H][W] (row-major, one channel) is cut into T x T tiles whose origins (y0, x0) the caller lists in a device
+ * table int32 [n][2]; every tile lies inside the scene (infer.plan_tiles; there is no padding path). T is a multiple of
+ * 16, 0 <= overlap <= T / 2, 2 <= K <= 8 classes (INSAR_E_SHAPE otherwise). All three validate before they launch. */
+enum { INSAR_SCENE_U8 = 0, INSAR_SCENE_F32 = 1 };
+/* out [n][1][T][T] fp32 (16-byte aligned) <- the n tiles. A uint8 scene gets the reference's ToTensor + Normalize(0.5, 0.5)
+ * in its order, x = v / 255.0f; out = (x - 0.5f) / 0.5f (Unet-ChannalAttention.py:428-432); a float32 scene is copied. A table
+ * entry that is not inside the scene gives a tile of zeros. */
+int insar_scene_gather(const void* scene, int32_t dtype /*INSAR_SCENE_**/, int32_t H, int32_t W, const int32_t* origins,
+                       int32_t n, int32_t T, float* out /*[n][1][T][T]*/, void* stream);
+/* acc [K][H][W] += w * softmax_k(logits), wsum [H][W] += w for every pixel under the n tiles of `logits` [n][K][T][T]
+ * (fp32 NCHW, what every net returns). Softmax over the class axis, max-subtracted, fp32. w(y, x) = r(y - y0) * r(x - x0),
+ * r(i) = min(i + 1, T - i, overlap + 1) / (overlap + 1): strictly positive, 1 for overlap = 0, and two tiles at the regular
+ * stride T - overlap sum to 1 across their overlap. Gather form, no atomics: the thread that owns a pixel adds the covering
+ * tiles of this call in ascending table index (acc = fma(w, p, acc)), so feeding the tiles of a scene in index order in
+ * batches of ANY size on one stream gives bitwise the same acc / wsum. [y_lo, y_hi) x [x_lo, x_hi) is a box of scene pixels
+ * that contains every tile of the call (the caller knows the origins; the library reads nothing back): pixels outside it
+ * are not visited. A table entry that is not inside the scene is ignored. The caller zeroes acc / wsum before the first
+ * batch of a scene. */
+int insar_scene_blend(const float* logits, const int32_t* origins, int32_t n, int32_t K, int32_t T, int32_t overlap,
+                      float* acc, float* wsum, int32_t H, int32_t W, int32_t y_lo, int32_t y_hi, int32_t x_lo, int32_t x_hi,
+                      void* stream);
+/* prob [K][H][W] = acc / wsum (nullable: skipped), mask [H][W] uint8 = argmax over classes (ties -> lower class, the rule of
+ * insar_confusion), conf [H][W] = the winning probability. A pixel with wsum == 0 (no tile) gets prob = 0, mask = 0, conf = 0. */
+int insar_scene_finalize(const float* acc, const float* wsum, int32_t K, int32_t H, int32_t W, float* prob /*nullable*/,
+                         uint8_t* mask, float* conf, void* stream);
 
 /* ---- optimizer: optim.Adam(lr=1e-4) (:466,346), multi-tensor ------------------------------------
  * table: int64[ntensors][5] = {param*, grad*, exp_avg*, exp_avg_sq*, numel}; chunks: int32[nchunks][2]

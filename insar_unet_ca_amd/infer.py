@@ -1,0 +1,237 @@
+"""Whole-scene inference: cut a scene into overlapping tiles, run the eval-mode forward of any net of this package on
+them, and stitch the class probabilities back together on the device (csrc/scene.hip: insar_scene_gather / _blend /
+_finalize). The reference stops at fixed-size tiles; this is what its nets are trained for.
+
+Tiling rule (`plan_tiles`): along each axis origins 0, s, 2s, ... with s = tile - overlap while origin + tile <= size, then
+one more tile flush with the edge if the last one is not. Every tile lies inside the scene: there is no padding path, and a
+scene smaller than a tile is refused. Window (`window_1d`): the separable trapezoid r(i) = min(i + 1, tile - i, o + 1) / (o + 1).
+
+The stitch is bitwise reproducible and independent of the batch size: a pixel's contributions are added in ascending tile
+index (row-major over the tile grid) by the thread that owns the pixel; no atomics. The nets' own forward is NOT promised
+bitwise equal across batch sizes (kernel selection depends on the GEMM's M), so `predict` as a whole is reproducible for a
+fixed `batch`, and `stitch_logits` for any `chunk`.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import InsarError, call, ptr
+
+MAX_CLASSES = 8          # SC_MAX_K of csrc/scene.hip: the per-thread accumulators stay in registers up to here
+
+
+def _check_geometry(H: int, W: int, tile: int, overlap: int) -> None:
+    for name, v in (("H", H), ("W", W), ("tile", tile), ("overlap", overlap)):
+        if int(v) != v:
+            raise InsarError(f"plan_tiles: {name}={v!r} is not an integer")
+    if tile < 16 or tile % 16:
+        raise InsarError(f"tile={tile}: must be a positive multiple of 16 (the U-Net's four 2x2 poolings)")
+    if not 0 <= overlap <= tile // 2:
+        raise InsarError(f"overlap={overlap}: must lie in 0..tile // 2 = {tile // 2}")
+    if H < tile or W < tile:
+        raise InsarError(f"scene {H} x {W} is smaller than the tile {tile}: there is no padding path")
+
+
+def _axis_origins(size: int, tile: int, stride: int) -> list:
+    out = list(range(0, size - tile + 1, stride))
+    if out[-1] != size - tile:
+        out.append(size - tile)          # flush with the edge; overlaps its neighbours by more than `overlap`
+    return out
+
+
+def plan_tiles(H: int, W: int, tile: int, overlap: int) -> np.ndarray:
+    """int32 [N, 2] tile origins (y0, x0), row-major over the tile grid. Host arithmetic only."""
+    _check_geometry(H, W, tile, overlap)
+    H, W, tile, overlap = int(H), int(W), int(tile), int(overlap)
+    ys = _axis_origins(H, tile, tile - overlap)
+    xs = _axis_origins(W, tile, tile - overlap)
+    return np.array([(y, x) for y in ys for x in xs], dtype=np.int32).reshape(-1, 2)
+
+
+def window_1d(tile: int, overlap: int) -> np.ndarray:
+    """float32 [tile]: r(i) = min(i + 1, tile - i, overlap + 1) / (overlap + 1), the quotient the blend kernel forms."""
+    if tile < 1 or not 0 <= overlap <= tile // 2:
+        raise InsarError(f"window_1d: tile={tile}, overlap={overlap}: need 0 <= overlap <= tile // 2")
+    i = np.arange(tile)
+    m = np.minimum(np.minimum(i + 1, tile - i), overlap + 1)
+    return m.astype(np.float32) / np.float32(overlap + 1)
+
+
+def _check_origins(origins, H: int, W: int, tile: int) -> np.ndarray:
+    o = origins.detach().cpu().numpy() if isinstance(origins, torch.Tensor) else np.asarray(origins)
+    if o.ndim != 2 or o.shape[1] != 2 or o.shape[0] < 1 or not np.issubdtype(o.dtype, np.integer):
+        raise InsarError(f"origins: expected an integer [N, 2] table, got {o.dtype} {o.shape}")
+    if (o < 0).any() or (o[:, 0] + tile > H).any() or (o[:, 1] + tile > W).any():
+        raise InsarError(f"origins: a {tile} x {tile} tile leaves the {H} x {W} scene")
+    return np.ascontiguousarray(o, dtype=np.int32)
+
+
+def _check_classes(K: int) -> None:
+    if not 2 <= K <= MAX_CLASSES:
+        raise InsarError(f"num_classes={K}: the scene kernels cover 2..{MAX_CLASSES} classes")
+
+
+def _as_scene(scene, device: torch.device) -> torch.Tensor:
+    """2-D uint8 / float32 numpy array or tensor -> contiguous device tensor (a host scene is copied once)."""
+    if isinstance(scene, np.ndarray):
+        if scene.dtype not in (np.uint8, np.float32):
+            raise InsarError(f"scene dtype {scene.dtype}: uint8 or float32")
+        if scene.ndim != 2:
+            raise InsarError(f"scene must be 2-D [H, W], got {scene.ndim}-D")
+        scene = torch.from_numpy(np.ascontiguousarray(scene))
+    elif not isinstance(scene, torch.Tensor):
+        raise InsarError(f"scene: numpy array or torch tensor, got {type(scene).__name__}")
+    if scene.dtype not in (torch.uint8, torch.float32):
+        raise InsarError(f"scene dtype {scene.dtype}: uint8 or float32")
+    if scene.dim() != 2:
+        raise InsarError(f"scene must be 2-D [H, W], got {scene.dim()}-D")
+    if device.type != "cuda":
+        raise InsarError("scene inference runs on a ROCm device (no CPU fallback)")
+    return scene.detach().to(device).contiguous()
+
+
+def gather_tiles(scene: torch.Tensor, origins_dev: torch.Tensor, tile: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float32 [n, 1, tile, tile] <- the tiles of a device scene [H, W] at the int32 device table `origins_dev` [n, 2]
+    (every tile inside the scene). uint8 scenes are normalised like `data.reference_transforms`, float32 ones copied."""
+    if not scene.is_cuda or not origins_dev.is_cuda:
+        raise InsarError("gather_tiles: scene and origins must be ROCm tensors (no CPU fallback)")
+    if scene.dim() != 2 or scene.dtype not in (torch.uint8, torch.float32) or not scene.is_contiguous():
+        raise InsarError("gather_tiles: scene must be a contiguous 2-D uint8 or float32 tensor")
+    if origins_dev.dtype != torch.int32 or origins_dev.dim() != 2 or origins_dev.shape[1] != 2 or not origins_dev.is_contiguous():
+        raise InsarError("gather_tiles: origins must be a contiguous int32 [n, 2] tensor")
+    n = origins_dev.shape[0]
+    if out is None:
+        out = torch.empty(n, 1, tile, tile, dtype=torch.float32, device=scene.device)
+    code = _lib.SCENE_U8 if scene.dtype == torch.uint8 else _lib.SCENE_F32
+    call("insar_scene_gather", ptr(scene), code, scene.shape[0], scene.shape[1], ptr(origins_dev), n, tile, ptr(out),
+         _lib.stream_ptr())
+    return out
+
+
+def _blend(logits: torch.Tensor, origins: np.ndarray, origins_dev: torch.Tensor, first: int, K: int, tile: int, overlap: int,
+           acc: torch.Tensor, wsum: torch.Tensor) -> None:
+    """Add tiles first .. first + n - 1 of the table (n = logits.shape[0]) into acc / wsum."""
+    n = logits.shape[0]
+    if tuple(logits.shape) != (n, K, tile, tile):
+        raise InsarError(f"logits {tuple(logits.shape)}: expected ({n}, {K}, {tile}, {tile})")
+    lg = logits.detach()
+    if lg.dtype != torch.float32 or not lg.is_contiguous():
+        lg = lg.float().contiguous()
+    o = origins[first:first + n]
+    H, W = wsum.shape
+    call("insar_scene_blend", ptr(lg), ptr(origins_dev) + 8 * first, n, K, tile, overlap, ptr(acc), ptr(wsum), H, W,
+         int(o[:, 0].min()), int(o[:, 0].max()) + tile, int(o[:, 1].min()), int(o[:, 1].max()) + tile, _lib.stream_ptr())
+
+
+def _finalize(acc: torch.Tensor, wsum: torch.Tensor, return_prob: bool) -> Dict[str, torch.Tensor]:
+    K, H, W = acc.shape
+    dev = acc.device
+    out = {"mask": torch.empty(H, W, dtype=torch.uint8, device=dev), "conf": torch.empty(H, W, dtype=torch.float32, device=dev)}
+    if return_prob:
+        out["prob"] = torch.empty(K, H, W, dtype=torch.float32, device=dev)
+    call("insar_scene_finalize", ptr(acc), ptr(wsum), K, H, W, ptr(out.get("prob")), ptr(out["mask"]), ptr(out["conf"]),
+         _lib.stream_ptr())
+    return out
+
+
+def _accumulators(K: int, H: int, W: int, device: torch.device):
+    buf = torch.empty(K + 1, H, W, dtype=torch.float32, device=device)      # one allocation, one clear per scene
+    return buf, buf[:K], buf[K]
+
+
+def stitch_logits(logits: torch.Tensor, origins, H: int, W: int, tile: int, overlap: int, chunk: Optional[int] = None,
+                  return_prob: bool = True) -> Dict[str, torch.Tensor]:
+    """The blend + finalize stage alone: logits [N, K, tile, tile] of the tiles at `origins` [N, 2] (index order = blend
+    order) -> {"mask", "conf"[, "prob"]}, fed to the blend kernel `chunk` tiles at a time (None: all at once). The result
+    does not depend on `chunk`, bit for bit."""
+    _check_geometry(H, W, tile, overlap)
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda:
+        raise InsarError("stitch_logits: logits must be a ROCm tensor (no CPU fallback)")
+    if logits.dim() != 4:
+        raise InsarError(f"stitch_logits: logits must be [N, K, tile, tile], got {tuple(logits.shape)}")
+    N, K = logits.shape[0], logits.shape[1]
+    _check_classes(K)
+    o = _check_origins(origins, H, W, tile)
+    if o.shape[0] != N:
+        raise InsarError(f"stitch_logits: {N} tiles of logits, {o.shape[0]} origins")
+    chunk = N if chunk is None else int(chunk)
+    if chunk < 1:
+        raise InsarError(f"stitch_logits: chunk={chunk}")
+    with torch.no_grad():
+        o_dev = torch.from_numpy(o).to(logits.device)
+        buf, acc, wsum = _accumulators(K, H, W, logits.device)
+        buf.zero_()
+        for i in range(0, N, chunk):
+            _blend(logits[i:i + chunk], o, o_dev, i, K, tile, overlap, acc, wsum)
+        return _finalize(acc, wsum, return_prob)
+
+
+class ScenePredictor:
+    """Tiled prediction of a whole scene with any net of this package (1-channel input, logits [n, K, tile, tile]).
+
+        pred = ScenePredictor(net, tile=256, overlap=32, batch=16, num_classes=2)
+        out = pred.predict(scene)                 # scene: 2-D uint8 / float32, numpy or torch, host or device
+        out["mask"]  uint8 [H, W]   class map        out["conf"]  float32 [H, W]  its probability
+        out["prob"]  float32 [K, H, W]               (return_prob=True)
+
+    uint8 scenes are normalised as the reference's data_transforms do (v / 255, then (x - 0.5) / 0.5); float32 scenes are
+    taken as already normalised. Works on the current stream; the tile batch, the origin table and the accumulators are
+    kept between calls with the same scene size (the outputs are fresh tensors every call)."""
+
+    def __init__(self, model: torch.nn.Module, tile: int = 256, overlap: int = 32, batch: int = 16, num_classes: int = 2):
+        _check_geometry(tile, tile, tile, overlap)
+        _check_classes(num_classes)
+        if int(batch) != batch or batch < 1:
+            raise InsarError(f"batch={batch!r}: a positive integer")
+        self.model, self.tile, self.overlap, self.batch, self.num_classes = model, int(tile), int(overlap), int(batch), int(num_classes)
+        self._geom: dict = {}            # (H, W, device) -> (origins, origins_dev, buf, acc, wsum)
+        self._tiles: dict = {}           # device -> float32 [batch, 1, tile, tile]
+
+    def _buffers(self, H: int, W: int, device: torch.device):
+        key = (H, W, device)
+        if key not in self._geom:
+            origins = plan_tiles(H, W, self.tile, self.overlap)
+            self._geom[key] = (origins, torch.from_numpy(origins).to(device)) + _accumulators(self.num_classes, H, W, device)
+        if device not in self._tiles:
+            self._tiles[device] = torch.empty(self.batch, 1, self.tile, self.tile, dtype=torch.float32, device=device)
+        return self._geom[key] + (self._tiles[device],)
+
+    def release(self) -> None:
+        """Drop the cached buffers (they are scene-sized)."""
+        self._geom.clear()
+        self._tiles.clear()
+
+    @torch.no_grad()
+    def predict(self, scene, return_prob: bool = False) -> Dict[str, torch.Tensor]:
+        shape = tuple(getattr(scene, "shape", ()))
+        if len(shape) == 2:
+            _check_geometry(shape[0], shape[1], self.tile, self.overlap)       # refuse before anything is copied
+        try:
+            device = next(self.model.parameters()).device
+        except StopIteration:
+            raise InsarError("ScenePredictor: the model has no parameters") from None
+        sc = _as_scene(scene, device)
+        H, W = sc.shape
+        K, T = self.num_classes, self.tile
+        origins, o_dev, buf, acc, wsum, tiles = self._buffers(H, W, device)
+        N = origins.shape[0]
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            buf.zero_()
+            for i in range(0, N, self.batch):
+                n = min(self.batch, N - i)
+                x = gather_tiles(sc, o_dev[i:i + n], T, out=tiles[:n])
+                _blend(self.model(x), origins, o_dev, i, K, T, self.overlap, acc, wsum)
+        finally:
+            self.model.train(was_training)
+        return _finalize(acc, wsum, return_prob)
+
+
+def predict_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw) -> Dict[str, torch.Tensor]:
+    """One-shot ScenePredictor(model, **kw).predict(scene, return_prob)."""
+    return ScenePredictor(model, **kw).predict(scene, return_prob=return_prob)
