@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define INSAR_ABI_VERSION 7
+#define INSAR_ABI_VERSION 8
 
 enum { INSAR_F32 = 0, INSAR_BF16 = 1 };
 
@@ -525,6 +525,33 @@ int insar_dice(const float* logits, const int64_t* target, int32_t B, int32_t K,
 int insar_dice_ce(const float* logits, const int64_t* target, int32_t B, int32_t K, int64_t HW,
                   int64_t ignore_index, float smooth, float ce_weight, float dice_weight, float* dlogits,
                   float* loss_out, float* ws, void* stream);
+
+/* ---- imbalance-aware losses (build-side addition): csrc/loss_weighted.hip -------------------------------------------
+ * Same conventions as the three entry points above. A pixel is valid when its target is not ignore_index and lies in
+ * [0, K); K <= 16. weight / alpha: device float[K], read by the kernels (never by the host), so the launch arguments do
+ * not change from step to step. Results are bitwise reproducible (block partials folded in fixed order).
+ *
+ * Class-weighted, label-smoothed CE with torch's mean reduction (divide by W = sum of w[target] over valid pixels).
+ * ws: float[2 + 2*blocks]; dlogits = [(1-e) w[y] (p - onehot) + (e/K) (S p - w)] / W, S = sum of the weights. */
+int insar_cross_entropy_w(const float* logits, const int64_t* target, int32_t B, int32_t K, int64_t HW,
+                          int64_t ignore_index, const float* weight, float label_smoothing, float* dlogits,
+                          float* loss_out, float* ws, void* stream);
+/* Focal loss: mean over valid pixels of alpha[y] (1 - p_t)^gamma (-log p_t); alpha nullable (ones); 0 <= gamma <= 64.
+ * ws: float[2 + 2*blocks]. */
+int insar_focal(const float* logits, const int64_t* target, int32_t B, int32_t K, int64_t HW, int64_t ignore_index,
+                float gamma, const float* alpha, float* dlogits, float* loss_out, float* ws, void* stream);
+/* ce_weight * (weighted / smoothed CE; or focal with alpha = weight when focal_gamma >= 0) + dice_weight * Dice (unweighted),
+ * one statistics pass + one gradient pass like insar_dice_ce. weight nullable (ones); focal_gamma < 0 = no focal term;
+ * label smoothing and focal do not combine. ws: float[4 + 3K + blocks*(3 + 3K)]; loss_out[0..2] = combined, CE term, Dice. */
+int insar_dice_ce_w(const float* logits, const int64_t* target, int32_t B, int32_t K, int64_t HW,
+                    int64_t ignore_index, float smooth, float ce_weight, float dice_weight, const float* weight,
+                    float label_smoothing, float focal_gamma, float* dlogits, float* loss_out, float* ws,
+                    void* stream);
+/* Per-class pixel counts: counts[c] += pixels with target c (c < K), counts[K] += pixels equal to ignore_index. The call
+ * ADDS to counts (the caller clears it once and accumulates batches); other labels are counted nowhere.
+ * ws: int64[(K + 1) * blocks], blocks = insar_ce_blocks(npix). */
+int insar_label_hist(const int64_t* target, int64_t npix, int32_t K, int64_t ignore_index, int64_t* counts,
+                     int64_t* ws, void* stream);
 
 /* ---- metrics (compute_metrics, :215-269): argmax (ties -> lower class) + TP/FP/FN counts -------- */
 int insar_confusion(const float* logits, const int64_t* target, int32_t B, int32_t K, int64_t HW,

@@ -2,7 +2,7 @@
 Createroner/InSAR-Unet-CA's Unet-ChannalAttention.py model/loss/optimizer entry points)."""
 from ._lib import InsarError, LIB_PATH  # noqa: F401
 from .data import DevicePrefetcher, ShardedSampler, SyntheticTiles, VOCSegDataset, make_loader, reference_transforms  # noqa: F401
-from .loss import CrossEntropyLoss, DiceCELoss, DiceLoss  # noqa: F401
+from .loss import CrossEntropyLoss, DiceCELoss, DiceLoss, FocalLoss, class_weights, label_histogram  # noqa: F401
 from .modules import ChannelAttentionModule, DoubleConv, MaxPool2d, SELayer, UNet  # noqa: F401
 from .deeplab import DeepLabV3_SingleChannel_Attn  # noqa: F401
 from .fcn import FCN_SingleChannel, FCN_SingleChannel_SE  # noqa: F401
@@ -16,4 +16,5 @@ __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "Cha
            "compute_metrics", "train_model", "validate_model", "save_history", "VOCSegDataset", "SyntheticTiles",
            "ShardedSampler", "DevicePrefetcher", "make_loader", "reference_transforms", "InsarError", "LIB_PATH",
            "SpatialAttention", "UNetSpatialAttention", "FCN_SingleChannel", "FCN_SingleChannel_SE",
-           "ScenePredictor", "predict_scene", "stitch_logits", "plan_tiles", "window_1d", "gather_tiles"]
+           "ScenePredictor", "predict_scene", "stitch_logits", "plan_tiles", "window_1d", "gather_tiles",
+           "FocalLoss", "class_weights", "label_histogram"]

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("INSAR_HIP_LIB") or os.path.join(_HERE, "libinsar_hip.so")
 
 F32, BF16 = 0, 1
-ABI_VERSION = 7
+ABI_VERSION = 8
 SCENE_U8, SCENE_F32 = 0, 1
 IGEMM_OOB_ZERO = 1
 IGEMM_PINGPONG = 2
@@ -187,6 +187,10 @@ _SIGNATURES = {
     "insar_dice": [_P, _P, _I, _I, _L, _L, _F, _P, _P, _P, _P],
     "insar_dice_ce": [_P, _P, _I, _I, _L, _L, _F, _F, _F, _P, _P, _P, _P],
     "insar_confusion": [_P, _P, _I, _I, _L, _L, _P, _P],
+    "insar_cross_entropy_w": [_P, _P, _I, _I, _L, _L, _P, _F, _P, _P, _P, _P],
+    "insar_focal": [_P, _P, _I, _I, _L, _L, _F, _P, _P, _P, _P, _P],
+    "insar_dice_ce_w": [_P, _P, _I, _I, _L, _L, _F, _F, _F, _P, _F, _F, _P, _P, _P, _P],
+    "insar_label_hist": [_P, _L, _I, _L, _P, _P, _P],
     "insar_scene_gather": [_P, _I, _I, _I, _P, _I, _I, _P, _P],
     "insar_scene_blend": [_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "insar_scene_finalize": [_P, _P, _I, _I, _I, _P, _P, _P, _P],
