@@ -6,6 +6,7 @@ Kernel level: the same stored gradient and the same y go through both; the folde
 Network level: every parameter gradient of a training step with the fusion on against the fusion off (no decision is
 involved in backward — the ReLU masks come from y — so fp32 agrees to summation order and bf16 to a few roundings of dy)."""
 import ctypes as C
+import math
 
 import numpy as np
 import pytest
@@ -43,6 +44,26 @@ def _reference_sums(dout, y, scale, shift, dev):
     return part.double().sum(0), part.double().view(dout.B, rows, 2, dout.c_len).sum(1)
 
 
+def _assert_float64_sums(slab, dout, y, scale, shift, per_image=False):
+    """The folded slab against the float64 reference of the same sums (tests/bn_chain_ref.reduce on the stored dout and y;
+    mask = y*scale + shift > 0 in float64, which is the decision the kernel's single fused multiply-add takes): the anchor
+    that does not go through a sibling kernel. Tolerance: the rule and the K of tests/test_bn_backward_chain_gpu.py,
+    |got - ref| <= K * 2^-24 * sqrt(n) * sum|terms| with n the pixels behind one sum."""
+    from tests import bn_chain_ref as R
+    from tests.test_bn_backward_chain_gpu import K
+    inner = lambda a: a.buf[:, 1:-1, 1:-1, a.c_off:a.c_off + a.c_len].cpu()
+    ref, unit = R.reduce(inner(dout), inner(y), scale.cpu(), shift.cpu(), 1, dout.H)       # [B][1][2][C], one part per image
+    ref, unit = ref[:, 0], unit[:, 0]
+    got = slab.double().cpu()
+    r = R.ratio(got.sum(0), ref.sum(0), math.sqrt(dout.B) * unit.sum(0))
+    print(f"ratio epilogue sums: {r:.3f}")
+    assert r <= K, r
+    if per_image:
+        r = R.ratio(got.view(dout.B, -1, 2, dout.c_len).sum(1), ref, unit)
+        print(f"ratio epilogue sums per image: {r:.3f}")
+        assert r <= K, r
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("cin,cout,B,hw", [(256, 256, 2, 32), (512, 256, 4, 16), (128, 64, 2, 64), (1024, 512, 16, 16)])
 def test_igemm_epilogue_sums_against_the_reduce_pass(dev, dtype, cin, cout, B, hw):
@@ -72,6 +93,7 @@ def test_igemm_epilogue_sums_against_the_reduce_pass(dev, dtype, cin, cout, B, h
     if (hw * hw) % bm == 0:
         per_img = slab.double().view(B, rows // B, 2, cin).sum(1)
         assert (per_img - ref_img).abs().max().item() <= 2e-5 * ref_img.abs().max().item()
+    _assert_float64_sums(slab, dx, y, scale, shift, per_image=(hw * hw) % bm == 0)
     # the GEMM output itself is what the plain launch writes, bit for bit
     dx2 = engine.Act.alloc(B, hw, hw, cin, dtype, dev)
     engine._igemm(dy, dx2, wd, cin, hw, hw, 1, engine._TAPS3_DGRAD, 0)
@@ -99,6 +121,7 @@ def test_conv_transpose_input_gradient_sums(dev, dtype):
     torch.cuda.synchronize()
     ref_tot, _ = _reference_sums(dx, y, scale, shift, dev)
     assert (slab.double().sum(0) - ref_tot).abs().max().item() <= 2e-5 * ref_tot.abs().max().item()
+    _assert_float64_sums(slab, dx, y, scale, shift)
 
 
 @pytest.mark.parametrize("two", [0, 1, 2])
@@ -126,6 +149,7 @@ def test_flat_kernel_epilogue_sums_against_the_reduce_pass(dev, dtype, cin, cout
     torch.cuda.synchronize()
     ref_tot, _ = _reference_sums(dx, y, scale, shift, dev)
     assert (slab.double().sum(0) - ref_tot).abs().max().item() <= 2e-5 * ref_tot.abs().max().item()
+    _assert_float64_sums(slab, dx, y, scale, shift)
     dx2 = engine.Act.alloc(B, hw, hw, cin, dtype, dev)
     engine._conv3x3_flat(dy, dx2, wd, 1, None)
     torch.cuda.synchronize()
@@ -152,6 +176,7 @@ def test_c64_kernel_epilogue_sums_against_the_reduce_pass(dev):
     torch.cuda.synchronize()
     ref_tot, _ = _reference_sums(dx, y, scale, shift, dev)
     assert (slab.double().sum(0) - ref_tot).abs().max().item() <= 2e-5 * ref_tot.abs().max().item()
+    _assert_float64_sums(slab, dx, y, scale, shift)
     dx2 = engine.Act.alloc(B, hw, hw, 64, dtype, dev)
     engine._conv3x3_c64(dy, dx2, wd, 1, None)
     torch.cuda.synchronize()
