@@ -24,8 +24,9 @@ import torch.nn as nn
 
 from . import _lib, engine, tape
 from .tape import tape_py
-from ._lib import InsarBnFinalize, InsarBnSeBwd, InsarCam, InsarWgrad, call, ptr
-from .engine import Act, Ctx, GemmWeight, GradSink, OutConvPlan, WeightSet, _igemm, _round_up, _rows_per_part, _wgrad_nsplit
+from ._lib import InsarCam, InsarWgrad, call, ptr
+from .engine import (Act, Ctx, GemmWeight, GradSink, OutConvPlan, WeightSet, _igemm, _rows_per_part, _wgrad_nsplit, bn_bwd_desc,
+                     bn_finalize_desc)
 from .modules import ChannelAttentionModule, _PlanCache, _UNetFn, _require_device, _resolve_dtype
 
 ASPP_RATES = (12, 24, 36)
@@ -115,7 +116,67 @@ class _DeepLabV3(nn.Module):
                                         nn.ReLU(), nn.Conv2d(256, 21, 1))
 
 
-class DeepLabV3_SingleChannel_Attn(nn.Module):
+class _ResNetSegBase(nn.Module):
+    """What the wrappers of the segmentation networks on the ResNet-50 trunk share (DeepLabV3_SingleChannel_Attn here,
+    fcn.FCN_SingleChannel / fcn.FCN_SingleChannel_SE): refused options, checkpoint loading, forward on the HIP plan.
+    A subclass builds `self.model` (backbone + classifier) and provides `_check_input` and `_new_plan`."""
+
+    def _setup(self, backbone: str, pretrained: bool, compute_dtype: Optional[torch.dtype]) -> None:
+        if backbone != "resnet50":
+            raise ValueError(f"Unsupported backbone: {backbone}" if backbone != "resnet101" else
+                             "resnet101 is not part of BASELINE.json's configurations")
+        if pretrained:
+            raise _lib.InsarError("pretrained=True needs torchvision's downloaded weights; load a state_dict instead")
+        self.compute_dtype = compute_dtype
+        self._plans = _PlanCache()
+        self._hooks: dict = {}
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        """As nn.Module.load_state_dict, except that `model.aux_classifier.*` keys (present in checkpoints of a reference model
+        built with pretrained=True: torchvision then adds an FCNHead that `forward` never calls) are ignored."""
+        if any(k.startswith("model.aux_classifier.") for k in state_dict):
+            state_dict = OrderedDict((k, v) for k, v in state_dict.items() if not k.startswith("model.aux_classifier."))
+        return super().load_state_dict(state_dict, strict=strict, **kw)
+
+    @torch.no_grad()
+    def load_backbone_state_dict(self, resnet_state_dict, strict: bool = True):
+        """Load a torchvision ResNet-50 state_dict (e.g. IMAGENET1K weights from a local file) into the backbone, as the
+        reference's constructors effectively do (`weights_backbone`): `fc.*` is dropped, and the 3-channel `conv1.weight`
+        (64, 3, 7, 7) becomes the 1-channel stem by averaging over the input channels — the reference's own rule for
+        pretrained stems. A backbone with SE blocks keeps its own `se_block` weights, which a ResNet-50 does not have."""
+        sd = OrderedDict((k, v) for k, v in resnet_state_dict.items() if not k.startswith("fc."))
+        w = sd.get("conv1.weight")
+        if w is not None and w.shape[1] == 3:
+            sd["conv1.weight"] = w.mean(dim=1, keepdim=True)
+        bb = self.model.backbone
+        own_se = [k for k in bb.state_dict() if ".se_block." in k]
+        if not own_se:
+            return bb.load_state_dict(sd, strict=strict)
+        res = bb.load_state_dict(sd, strict=False)
+        bad = [k for k in res.missing_keys if k not in own_se] + list(res.unexpected_keys)
+        if strict and bad:
+            raise RuntimeError(f"load_backbone_state_dict: mismatched keys {bad[:8]}")
+        return res
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        self._check_input(x)
+        b, _c, h, w = x.shape
+        dt = _resolve_dtype(self)
+        plan = self._plans.get((b, h, w, dt, x.device), lambda: self._new_plan(b, h, w, dt, x.device))
+        for bn in plan.bn_modules:
+            if bn.training != self.training:
+                raise _lib.InsarError(f"{type(self).__name__}: mixed BatchNorm modes are not supported by the HIP path")
+        return _UNetFn.apply(plan, self.training, torch.is_grad_enabled(), self._hooks, x, *plan.grad_params)
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        for m in self.modules():
+            if hasattr(m, "_plans") and isinstance(m._plans, _PlanCache):
+                m._plans.clear()
+        return out
+
+
+class DeepLabV3_SingleChannel_Attn(_ResNetSegBase):
     """Same constructor, attribute names and state_dict as the reference's wrapper (:83-137); forward (:140-162) on HIP.
 
     Initialisation differs from the reference's call site in ONE respect, and it matters for anyone comparing training
@@ -130,11 +191,7 @@ class DeepLabV3_SingleChannel_Attn(nn.Module):
     def __init__(self, num_classes: int = 2, backbone: str = "resnet50", pretrained: bool = False,
                  compute_dtype: Optional[torch.dtype] = None):
         super().__init__()
-        if backbone != "resnet50":
-            raise ValueError(f"Unsupported backbone: {backbone}" if backbone != "resnet101" else
-                             "resnet101 is not part of BASELINE.json's configurations")
-        if pretrained:
-            raise _lib.InsarError("pretrained=True needs torchvision's downloaded weights; load a state_dict instead")
+        self._setup(backbone, pretrained, compute_dtype)
         self.model = _DeepLabV3()
         self.model.classifier[4] = nn.Conv2d(256, num_classes, kernel_size=(1, 1), stride=(1, 1))          # :102
         self.model.backbone["conv1"] = nn.Conv2d(1, 64, kernel_size=7, stride=2, padding=3, bias=False)    # :105-118
@@ -143,48 +200,15 @@ class DeepLabV3_SingleChannel_Attn(nn.Module):
         self.aspp = self.model.classifier[0]                                                                # :126
         self.post_aspp_conv = nn.Sequential(self.model.classifier[1], self.model.classifier[2], self.model.classifier[3])
         self.upsample_conv = self.model.classifier[4]                                                       # :137
-        self.compute_dtype = compute_dtype
-        self._plans = _PlanCache()
-        self._hooks: dict = {}
 
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        """As nn.Module.load_state_dict, except that `model.aux_classifier.*` keys (present in checkpoints of a reference model
-        built with pretrained=True: torchvision then adds an FCNHead that `forward` never calls, :140-162) are ignored."""
-        aux = [k for k in state_dict if k.startswith("model.aux_classifier.")]
-        if aux:
-            state_dict = OrderedDict((k, v) for k, v in state_dict.items() if not k.startswith("model.aux_classifier."))
-        return super().load_state_dict(state_dict, strict=strict, **kw)
-
-    @torch.no_grad()
-    def load_backbone_state_dict(self, resnet_state_dict, strict: bool = True):
-        """Load a torchvision ResNet-50 state_dict (e.g. IMAGENET1K weights from a local file) into the backbone, as the
-        reference's constructor effectively does (:92, `weights_backbone`): `fc.*` is dropped, and the 3-channel `conv1.weight`
-        (64, 3, 7, 7) becomes the 1-channel stem by averaging over the input channels — the reference's own rule for
-        pretrained stems (:105-118)."""
-        sd = OrderedDict((k, v) for k, v in resnet_state_dict.items() if not k.startswith("fc."))
-        w = sd.get("conv1.weight")
-        if w is not None and w.shape[1] == 3:
-            sd["conv1.weight"] = w.mean(dim=1, keepdim=True)
-        return self.backbone.load_state_dict(sd, strict=strict)
-
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def _check_input(self, x: torch.Tensor) -> None:
         _require_device(x, "DeepLabV3_SingleChannel_Attn")
-        b, c, h, w = x.shape
+        _b, c, _h, _w = x.shape
         if c != 1:
             raise _lib.InsarError(f"DeepLabV3_SingleChannel_Attn: expected 1 input channel, got {c}")
-        dt = _resolve_dtype(self)
-        plan = self._plans.get((b, h, w, dt, x.device), lambda: DeepLabPlan(self, b, h, w, dt, x.device))
-        for bn in plan.bn_modules:
-            if bn.training != self.training:
-                raise _lib.InsarError("DeepLabV3_SingleChannel_Attn: mixed BatchNorm modes are not supported by the HIP path")
-        return _UNetFn.apply(plan, self.training, torch.is_grad_enabled(), self._hooks, x, *plan.grad_params)
 
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        for m in self.modules():
-            if hasattr(m, "_plans") and isinstance(m._plans, _PlanCache):
-                m._plans.clear()
-        return out
+    def _new_plan(self, B: int, H: int, W: int, dtype: torch.dtype, device: torch.device) -> "DeepLabPlan":
+        return DeepLabPlan(self, B, H, W, dtype, device)
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -306,16 +330,8 @@ class ConvUnit:
                    stats=self.stats if training else None, oob=self.oob)
         if training and self.stat_rps:
             call("insar_colsum_partial", ptr(self.stats), ptr(self.sums), self.stat_rows, 2 * self.cout, self.stat_rps, s)
-        bn = self.bn
-        d = InsarBnFinalize()
-        d.part, d.rows, d.count, d.C, d.training = ptr(self.sums), self.fold_rows, self.M, self.cout, int(training)
-        d.conv_bias = 0
-        d.gamma, d.beta = ptr(bn.weight), ptr(bn.bias)
-        d.running_mean, d.running_var = ptr(bn.running_mean), ptr(bn.running_var)
-        d.num_batches_tracked = ptr(bn.num_batches_tracked)
-        d.momentum = bn.momentum if bn.momentum is not None else 0.1
-        d.eps = bn.eps
-        d.scale, d.shift, d.mean, d.invstd = ptr(self.scale), ptr(self.shift), ptr(self.mean), ptr(self.invstd)
+        d = bn_finalize_desc(self.bn, ptr(self.sums), self.fold_rows, self.M, self.cout, training, 0,
+                             ptr(self.scale), ptr(self.shift), ptr(self.mean), ptr(self.invstd))
         call("insar_bn_finalize", C.byref(d), s)
         if not apply:
             return
@@ -346,12 +362,7 @@ class ConvUnit:
             call("insar_bnrelu_bwd_reduce", dout.ref, self.y.ref, ptr(self.scale), ptr(self.shift), ptr(self.red_part), int(relu),
                  self.red_rpp, s)
         red, red_rows = (self.bred, self.bred_rows) if fused else (self.red_part, self.red_rows)
-        d = InsarBnSeBwd()
-        d.B, d.H, d.W, d.C, d.Cr, d.use_se = B, self.Ho, self.Wo, self.cout, 1, 0
-        d.mean, d.invstd = ptr(self.mean), ptr(self.invstd)
-        d.dgamma, d.dbeta = ptr(sink.view(self.bn.weight)), ptr(sink.view(self.bn.bias))
-        d.k1, d.k2 = ptr(self.k1), ptr(self.k2)
-        d.accumulate = 0
+        d = bn_bwd_desc(B, self.Ho, self.Wo, self.cout, self.bn, sink, self.mean, self.invstd, self.k1, self.k2)
         if engine.COEF_SIMPLE:      # no SE gate: one channel-parallel launch over all slab rows
             call("insar_bn_bwd_coef", C.byref(d), ptr(red), red_rows * B, ptr(self.scale), 0, int(training), s)
         elif engine.COEF_FUSE:      # both coefficient stages in one launch (stage 2 by the last-arriving work-group)
@@ -526,142 +537,157 @@ class BottleneckPlan:
         self.u3.backward(g, sink, training, self.dz2, relu=False, bstat_for=self.u2)
 
 
-class DeepLabPlan(tape.PlanTape):
-    """Buffers + launch sequence of DeepLabV3_SingleChannel_Attn.forward / backward for one input geometry."""
+class StemPlan:
+    """The one-channel ResNet stem: conv7x7 s2 (1 -> 64) -> BatchNorm -> ReLU -> MaxPool(3, 2, 1). Raw conv output `y0`,
+    activation `z0`, pooled output `p0` (the first residual block's input)."""
 
-    def __init__(self, net: DeepLabV3_SingleChannel_Attn, B: int, H: int, W: int, dtype: torch.dtype, device: torch.device):
+    def __init__(self, ctx: Ctx, conv: nn.Conv2d, bn: nn.BatchNorm2d, B: int, H: int, W: int):
+        self.ctx, self.conv, self.bn, self.B, self.H, self.W = ctx, conv, bn, B, H, W
+        h2, w2 = H // 2, W // 2
+        A = lambda h, w: Act.alloc(B, h, w, 64, ctx.dtype, ctx.device)
+        self.y0, self.z0, self.p0 = A(h2, w2), A(h2, w2), A(H // 4, W // 4)
+        self.pool_arg = torch.zeros((B, H // 4, W // 4, 64), dtype=torch.uint8, device=ctx.device)
+        self.M = B * h2 * w2
+        self.rows = call("insar_conv7x7s2_fwd_rows", B, H)
+        self.stats = ctx.f32(self.rows, 2, 64)
+        self.rps = 0 if self.rows <= 256 else max(64, -(-self.rows // 64))
+        self.fold = self.rows if not self.rps else -(-self.rows // self.rps)
+        self.sums = ctx.f32(self.fold, 2, 64) if self.rps else self.stats
+        self.scale, self.shift, self.mean, self.invstd, self.k1, self.k2 = (ctx.f32(64) for _ in range(6))
+        self.rpp = _rows_per_part(B, h2)
+        self.red_rows = -(-h2 // self.rpp)
+        self.red = ctx.f32(B * self.red_rows, 2, 64)
+        self.ws = ctx.f32(B * (3 * 64 + 1))
+        self.nb = call("insar_conv7x7s2_wgrad_blocks", B, h2)
+        self.part = ctx.f32(self.nb, 64 * 49)
+        self.dz0 = self.dy0 = self.dp0 = None
+
+    def params(self):
+        return [self.conv.weight, self.bn.weight, self.bn.bias]
+
+    def forward(self, x_in: torch.Tensor, training: bool) -> None:
+        s = _lib.stream_ptr()
+        if training and self.M <= 1:
+            raise ValueError("Expected more than 1 value per channel when training")
+        call("insar_conv7x7s2_fwd", ptr(x_in), self.H, self.W, ptr(self.conv.weight), self.y0.ref,
+             ptr(self.stats) if training else 0, s)
+        if training and self.rps:
+            call("insar_colsum_partial", ptr(self.stats), ptr(self.sums), self.rows, 128, self.rps, s)
+        d = bn_finalize_desc(self.bn, ptr(self.sums), self.fold, self.M, 64, training, 0,
+                             ptr(self.scale), ptr(self.shift), ptr(self.mean), ptr(self.invstd))
+        call("insar_bn_finalize", C.byref(d), s)
+        call("insar_bn_relu_apply", self.y0.ref, ptr(self.scale), ptr(self.shift), 0, self.z0.ref, 1, s)
+        call("insar_maxpool3s2_fwd", self.z0.ref, self.p0.ref, ptr(self.pool_arg), s)
+
+    def grad_out(self) -> Act:
+        """Gradient wrt p0 (written by the first residual block); the stem's gradient buffers are allocated on first use."""
+        if self.dp0 is None:
+            like = lambda a: Act.alloc(a.B, a.H, a.W, 64, self.ctx.dtype, self.ctx.device)
+            self.dp0, self.dz0, self.dy0 = like(self.p0), like(self.z0), like(self.z0)
+        return self.dp0
+
+    def backward(self, dp0: Act, x_in: torch.Tensor, sink: GradSink, training: bool) -> None:
+        """MaxPool gradient, BN + ReLU backward, weight gradient of the 7x7 conv (on the side stream; the caller joins)."""
+        ctx, s = self.ctx, _lib.stream_ptr()
+        call("insar_maxpool3s2_bwd", dp0.ref, ptr(self.pool_arg), self.dz0.ref, s)
+        call("insar_bnrelu_bwd_reduce", self.dz0.ref, self.y0.ref, ptr(self.scale), ptr(self.shift), ptr(self.red), 1, self.rpp, s)
+        d = bn_bwd_desc(self.B, self.z0.H, self.z0.W, 64, self.bn, sink, self.mean, self.invstd, self.k1, self.k2)
+        call("insar_bnse_bwd_coef", C.byref(d), ptr(self.red), self.red_rows, ptr(self.scale), ptr(self.shift),
+             ptr(self.ws), 0, int(training), s)
+        call("insar_bnrelu_bwd_apply", self.dz0.ref, self.y0.ref, ptr(self.scale), ptr(self.shift), ptr(self.mean),
+             ptr(self.invstd), 0, 0, ptr(self.k1), ptr(self.k2), self.dy0.ref, 1, s)
+        with ctx.side_stream():
+            call("insar_conv7x7s2_wgrad", ptr(x_in), self.H, self.W, self.dy0.ref, ptr(self.part), _lib.stream_ptr())
+            ctx.colsum(self.part, sink.view(self.conv.weight).view(-1), 1, self.nb, 64 * 49)
+
+
+class ResNetTrunkPlan(tape.PlanTape):
+    """Buffers + launch sequence, for one input geometry, of what the segmentation networks on the ResNet-50 trunk share:
+    stem, the 16 residual blocks at output stride 8, and — around the head a subclass puts between them — dropout on the
+    device-counter mask, the 1x1 output conv at low resolution and the bilinear resize to the input size.
+
+    A subclass builds its head in __init__ between `super().__init__` and `_finish`, with `_dropout_setup` and `self.outc`
+    (an OutConvPlan) among it, and implements
+      _head_forward(training):                 from `self.x5` (the last block's output) to `self.outc.x`;
+      _head_backward(dz, sink, training, on_bucket): from dz, the gradient wrt `self.outc.x`, to the last block's
+                                               `grad_out()` — the head writes that buffer (and may gate it for the block:
+                                               BottleneckPlan.dout_gated) and reports its own stages to on_bucket."""
+
+    def __init__(self, net, B: int, H: int, W: int, dtype: torch.dtype, device: torch.device, name: str):
         if H % 8 or W % 8:
-            raise _lib.InsarError(f"H={H}, W={W}: the HIP path of DeepLabV3-CA covers inputs that are multiples of 8 (output stride 8)")
+            raise _lib.InsarError(f"H={H}, W={W}: the HIP path of {name} covers inputs that are multiples of 8 (output stride 8)")
         self.net, self.B, self.H, self.W = net, B, H, W
         ctx = self.ctx = Ctx(device, dtype)
-        A = lambda h, w, c: Act.alloc(B, h, w, c, dtype, device)
-        bb, head = net.model.backbone, net.model.classifier
-        # stem
-        self.stem_conv, self.stem_bn = bb["conv1"], bb["bn1"]
-        h2, w2, h4, w4 = H // 2, W // 2, H // 4, W // 4
-        self.y0, self.z0, self.p0 = A(h2, w2, 64), A(h2, w2, 64), A(h4, w4, 64)
-        self.pool_arg = torch.zeros((B, h4, w4, 64), dtype=torch.uint8, device=device)
-        self.st_rows = call("insar_conv7x7s2_fwd_rows", B, H)
-        self.st_stats = ctx.f32(self.st_rows, 2, 64)
-        self.st_rps = 0 if self.st_rows <= 256 else max(64, -(-self.st_rows // 64))
-        self.st_fold = self.st_rows if not self.st_rps else -(-self.st_rows // self.st_rps)
-        self.st_sums = ctx.f32(self.st_fold, 2, 64) if self.st_rps else self.st_stats
-        self.st_scale, self.st_shift, self.st_mean, self.st_invstd, self.st_k1, self.st_k2 = (ctx.f32(64) for _ in range(6))
-        self.st_rpp = _rows_per_part(B, h2)
-        self.st_red_rows = -(-h2 // self.st_rpp)
-        self.st_red = ctx.f32(B * self.st_red_rows, 2, 64)
-        self.st_ws = ctx.f32(B * (3 * 64 + 1))
-        self.st_nb = call("insar_conv7x7s2_wgrad_blocks", B, h2)
-        self.st_part = ctx.f32(self.st_nb, 64 * 49)
-        self.dz0 = self.dy0 = self.dp0 = None
-        # residual layers
+        bb = net.model.backbone
+        self.stem = StemPlan(ctx, bb["conv1"], bb["bn1"], B, H, W)
         self.blocks: List[BottleneckPlan] = []
         self.layer_blocks: List[List[BottleneckPlan]] = []
-        x = self.p0
+        x = self.stem.p0
         for li in range(1, 5):
             grp = []
             for bi, mod in enumerate(bb[f"layer{li}"]):
-                blk = BottleneckPlan(ctx, mod, x, f"layer{li}.{bi}")
+                blk = self._block_plan(mod)(ctx, mod, x, f"layer{li}.{bi}")
                 grp.append(blk)
                 self.blocks.append(blk)
                 x = blk.out
             self.layer_blocks.append(grp)
         self.x5 = x
-        h8, w8 = x.H, x.W
-        # ASPP
-        aspp = head[0]
-        self.cat = A(h8, w8, 1280)
-        self.branches = [ConvUnit(ctx, aspp.convs[i][0], aspp.convs[i][1], self.x5, self.cat.slice(256 * i, 256), True, f"aspp.convs.{i}")
-                         for i in range(4)]
-        # The pooling branch runs in fp32 whatever the compute type (B x 2048 values): the pooled vectors of similar tiles
-        # differ by far less than bf16 resolves, and the BatchNorm behind the 1x1 conv divides by that spread.
-        self.ctx32 = ctx
-        if dtype != torch.float32:
-            self.ctx32 = Ctx(device, torch.float32)
-            self.ctx32.side = None               # its (tiny) weight gradient stays on the main stream
-        self.gp = Act.alloc(B, 1, 1, 2048, torch.float32, device)
-        self.pool_unit = ConvUnit(self.ctx32, aspp.convs[4][1], aspp.convs[4][2], self.gp, None, True, "aspp.convs.4")
-        self.project = ConvUnit(ctx, aspp.project[0], aspp.project[1], self.cat, None, True, "aspp.project")
-        self.drop_p = float(aspp.project[3].p)
-        self.zdrop = A(h8, w8, 256)
-        self.drop_mask = torch.zeros((B, h8, w8, 256), dtype=torch.uint8, device=device)
+
+    def _block_plan(self, mod: nn.Module) -> type:
+        """The plan class of one residual block's module."""
+        return BottleneckPlan
+
+    def _dropout_setup(self, p: float, C: int) -> None:
+        """nn.Dropout(p) on a C-channel activation at the trunk's output resolution."""
+        x5, dev = self.x5, self.ctx.device
+        self.drop_p = float(p)
+        self.zdrop = Act.alloc(self.B, x5.H, x5.W, C, self.ctx.dtype, dev)
+        self.drop_mask = torch.zeros((self.B, x5.H, x5.W, C), dtype=torch.uint8, device=dev)
         self.drop_active = False
         self.drop_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        self.drop_counter = torch.zeros(1, dtype=torch.int64, device=device)
+        self.drop_counter = torch.zeros(1, dtype=torch.int64, device=dev)
         self.external_mask = False        # tests: apply a caller-supplied mask instead of drawing one
-        # head: 3x3 conv + BN + ReLU (post_aspp_conv), ChannelAttentionModule, 1x1 classifier, bilinear resize
-        self.head = ConvUnit(ctx, head[1], head[2], self.zdrop, None, True, "classifier.1")
-        cam = net.attention_module
-        self.cam_mod, self.cam_cr = cam, cam.mlp[0].out_channels
-        self.zc = A(h8, w8, 256)
-        self.cam_rpp = _rows_per_part(B, h8)
-        self.cam_rows = -(-h8 // self.cam_rpp)
-        f = ctx.f32
-        self.cam_psum, self.cam_pmax = f(B * self.cam_rows, 256), f(B * self.cam_rows, 256)
-        self.cam_parg = torch.zeros(B * self.cam_rows, 256, dtype=torch.int32, device=device)
-        self.cam_avg, self.cam_mx, self.cam_gate = f(B, 256), f(B, 256), f(B, 256)
-        self.cam_arg = torch.zeros(B, 256, dtype=torch.int32, device=device)
-        self.cam_ha, self.cam_hm = f(B, self.cam_cr), f(B, self.cam_cr)
-        self.cam_coefB, self.cam_dmax = f(B, 256), f(B, 256)
-        self.cam_red = f(B * self.cam_rows, 2, 256)
-        self.cam_ws = f(B * (256 + 2 * self.cam_cr))
-        self.ones, self.zeros = ctx.const(1.0, 256), ctx.const(0.0, 256)
-        self.outc = OutConvPlan(ctx, head[4], self.zc)
-        self.K = head[4].out_channels
-        self.logits_lo = None
-        # gradient buffers of the head side (allocated on first backward)
-        self._g = {}
-        # parameters grouped by backward stage (completion order), for the flat gradient buffer / DP buckets
-        cam_params = [cam.mlp[0].weight, cam.mlp[2].weight]
-        groups = [[head[4].weight, head[4].bias] + cam_params + self.head.params(),
-                  self.project.params() + self.pool_unit.params() + [p for u in self.branches for p in u.params()]]
-        for grp in reversed(self.layer_blocks):
-            groups.append([p for blk in reversed(grp) for p in blk.params()])
-        groups[-1] = groups[-1] + [self.stem_conv.weight, self.stem_bn.weight, self.stem_bn.bias]
+
+    def _trunk_groups(self) -> List[List[nn.Parameter]]:
+        """The trunk's parameters by backward stage, in completion order: layer4 ... layer1 (blocks last to first), the stem
+        with layer1."""
+        groups = [[p for blk in reversed(grp) for p in blk.params()] for grp in reversed(self.layer_blocks)]
+        groups[-1] = groups[-1] + self.stem.params()
+        return groups
+
+    def _finish(self, groups: List[List[nn.Parameter]], units: List[ConvUnit]) -> None:
+        """groups: every parameter by backward stage (completion order), the layout of the flat gradient buffer and the DP
+        buckets. units: the head's ConvUnits, in the order their GEMM-layout weights are refreshed after the blocks'."""
         self.grad_params = [p for g in groups for p in g]
-        if len({id(p) for p in self.grad_params}) != len(list(net.parameters())):
-            raise _lib.InsarError("DeepLabPlan: the gradient layout does not cover every parameter")
-        self.sink = GradSink(ctx, None, groups)
+        n = len(list(self.net.parameters()))
+        if len({id(p) for p in self.grad_params}) != n or len(self.grad_params) != n:
+            raise _lib.InsarError(f"{type(self).__name__}: the gradient layout does not cover every parameter exactly once")
+        self.sink = GradSink(self.ctx, None, groups)
         self.stage_sizes = self.sink.group_sizes
         self.stage_ends = [sum(self.stage_sizes[:i + 1]) for i in range(len(self.stage_sizes))]
-        self._closes = {}
-        units = [u for blk in self.blocks for u in blk.units()] + self.branches + [self.pool_unit, self.project, self.head]
-        self.units = units
-        self.weightset = WeightSet(ctx, [u.w for u in units])
-        self.bn_modules = [self.stem_bn] + [u.bn for u in units]
-        self._logits_lo = self._dlo = None
+        self.units = [u for blk in self.blocks for u in blk.units()] + units
+        self.weightset = WeightSet(self.ctx, [u.w for u in self.units])
+        self.bn_modules = [self.stem.bn] + [u.bn for u in self.units]
+        self.K = self.outc.K
+        self.logits_lo = self._logits_lo = self._dlo = None
+        self._g = {}                       # gradient buffers of the head side (allocated on first backward)
         self._tape_setup()
         self.busy = False
         self.training = True
         self.x_in: Optional[torch.Tensor] = None
-
-    def bucket_closes(self, min_elems: int):
-        if min_elems not in self._closes:
-            from .parallel import plan_buckets
-            self._closes[min_elems] = set(plan_buckets(self.stage_sizes, min_elems))
-        return self._closes[min_elems]
 
     def _grad(self, key: str, like: Act) -> Act:
         if key not in self._g:
             self._g[key] = Act.alloc(like.B, like.H, like.W, like.c_len, like.buf.dtype, self.ctx.device)
         return self._g[key]
 
-    def _cam_desc(self) -> InsarCam:
-        d = InsarCam()
-        z = self.head.out
-        d.B, d.H, d.W, d.C, d.Cr, d.rows = z.B, z.H, z.W, 256, self.cam_cr, self.cam_rows
-        d.psum, d.pmax, d.parg = ptr(self.cam_psum), ptr(self.cam_pmax), ptr(self.cam_parg)
-        d.w1, d.w2 = ptr(self.cam_mod.mlp[0].weight), ptr(self.cam_mod.mlp[2].weight)
-        d.avg, d.mx, d.arg = ptr(self.cam_avg), ptr(self.cam_mx), ptr(self.cam_arg)
-        d.ha, d.hm, d.gate = ptr(self.cam_ha), ptr(self.cam_hm), ptr(self.cam_gate)
-        d.coefB, d.dmax, d.ws = ptr(self.cam_coefB), ptr(self.cam_dmax), ptr(self.cam_ws)
-        d.accumulate = 0
-        return d
-
-    # ---- forward (DeepLabV3-ChannelAttention.py:140-162) -------------------------------------------------------
     def _tape_key(self, which: str) -> tuple:
         return super()._tape_key(which) + (self.drop_p,)
 
+    def _after_replay(self) -> None:
+        """What a replayed forward leaves to restore on the plan beyond `training`, `x_in` and `drop_active`."""
+
+    # ---- forward -------------------------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor, training: bool) -> torch.Tensor:
         """The ordinary launch sequence (_forward_eager) or, in the steady state of a training loop, its launch tape (tape.py)."""
         if x.dtype != torch.float32 or not x.is_contiguous():
@@ -676,6 +702,7 @@ class DeepLabPlan(tape.PlanTape):
             self.training = training
             self.x_in = x.detach()                 # the stem's weight gradient reads it in backward
             self.drop_active = training and self.drop_p > 0.0
+            self._after_replay()
             return logits
         return out
 
@@ -686,59 +713,32 @@ class DeepLabPlan(tape.PlanTape):
         self.x_in = x.detach()
         with ctx.side_stream():
             self.weightset.refresh()
-        # stem (:144 backbone): conv7x7 s2 -> BN -> ReLU -> MaxPool(3, 2, 1)
-        if training and self.B * (self.H // 2) * (self.W // 2) <= 1:
-            raise ValueError("Expected more than 1 value per channel when training")
-        call("insar_conv7x7s2_fwd", ptr(self.x_in), self.H, self.W, ptr(self.stem_conv.weight), self.y0.ref,
-             ptr(self.st_stats) if training else 0, s)
-        if training and self.st_rps:
-            call("insar_colsum_partial", ptr(self.st_stats), ptr(self.st_sums), self.st_rows, 128, self.st_rps, s)
-        bn = self.stem_bn
-        d = InsarBnFinalize()
-        d.part, d.rows, d.count, d.C, d.training = ptr(self.st_sums), self.st_fold, self.B * (self.H // 2) * (self.W // 2), 64, int(training)
-        d.conv_bias = 0
-        d.gamma, d.beta = ptr(bn.weight), ptr(bn.bias)
-        d.running_mean, d.running_var, d.num_batches_tracked = ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked)
-        d.momentum, d.eps = (bn.momentum if bn.momentum is not None else 0.1), bn.eps
-        d.scale, d.shift, d.mean, d.invstd = ptr(self.st_scale), ptr(self.st_shift), ptr(self.st_mean), ptr(self.st_invstd)
-        call("insar_bn_finalize", C.byref(d), s)
-        call("insar_bn_relu_apply", self.y0.ref, ptr(self.st_scale), ptr(self.st_shift), 0, self.z0.ref, 1, s)
-        call("insar_maxpool3s2_fwd", self.z0.ref, self.p0.ref, ptr(self.pool_arg), s)
+        self.stem.forward(self.x_in, training)
         ctx.join_side()                       # GEMM-layout weights are ready
         for blk in self.blocks:
             blk.forward(training)
-        # ASPP (:148)
-        for u in self.branches:
-            u.forward(training)
-        hw = self.x5.H * self.x5.W
-        call("insar_sum_hw", self.x5.ref, self.gp.ref, 1.0 / hw, s)
-        self.pool_unit.forward(training)
-        call("insar_broadcast_hw", self.pool_unit.out.ref, self.cat.slice(1024, 256).ref, 1.0, 0, s)
-        self.project.forward(training)
-        self.drop_active = training and self.drop_p > 0.0
-        if self.drop_active:
-            # mask = hash(seed drawn once from torch's RNG, device-side forward counter, element index): a new mask every
-            # training forward, also when the step is replayed from a captured hipGraph
-            ctr = self.drop_counter
-            tape_py(lambda: ctr.add_(1))
-            call("insar_dropout", self.project.out.ref, self.zdrop.ref, ptr(self.drop_mask), self.drop_seed, ptr(self.drop_counter),
-                 self.drop_p, 0 if self.external_mask else 1, s)
-            self.head.x = self.zdrop
-        else:
-            self.head.x = self.project.out
-        # head (:151 post_aspp_conv, :154 attention, :157 upsample_conv, :160 resize)
-        self.head.forward(training)
-        z = self.head.out
-        call("insar_cam_pool", z.ref, ptr(self.cam_psum), ptr(self.cam_pmax), ptr(self.cam_parg), self.cam_rpp, s)
-        dcam = self._cam_desc()
-        call("insar_cam_excite", C.byref(dcam), s)
-        call("insar_bn_relu_apply", z.ref, ptr(self.ones), ptr(self.zeros), ptr(self.cam_gate), self.zc.ref, 0, s)
+        self._head_forward(training)
+        # output conv at the trunk's resolution, bilinear resize to the input size
+        lo = self.outc.x
         if self._logits_lo is None:
-            self._logits_lo = torch.empty((self.B, self.K, z.H, z.W), dtype=torch.float32, device=ctx.device)
+            self._logits_lo = torch.empty((self.B, self.K, lo.H, lo.W), dtype=torch.float32, device=ctx.device)
         self.logits_lo = self.outc.forward(out=self._logits_lo)       # plan-owned (a launch tape holds its address)
         logits = torch.empty((self.B, self.K, self.H, self.W), dtype=torch.float32, device=ctx.device)
-        call("insar_bilinear_fwd", ptr(self.logits_lo), ptr(logits), self.B * self.K, z.H, z.W, self.H, self.W, s)
+        call("insar_bilinear_fwd", ptr(self.logits_lo), ptr(logits), self.B * self.K, lo.H, lo.W, self.H, self.W, s)
         return logits
+
+    def _dropout_forward(self, src: Act, training: bool) -> Act:
+        """Dropout of src in training mode (into zdrop); returns the activation the next layer reads."""
+        self.drop_active = training and self.drop_p > 0.0
+        if not self.drop_active:
+            return src
+        # mask = hash(seed drawn once from torch's RNG, device-side forward counter, element index): a new mask every
+        # training forward, also when the step is replayed from a captured hipGraph
+        ctr = self.drop_counter
+        tape_py(lambda: ctr.add_(1))
+        call("insar_dropout", src.ref, self.zdrop.ref, ptr(self.drop_mask), self.drop_seed, ptr(self.drop_counter),
+             self.drop_p, 0 if self.external_mask else 1, _lib.stream_ptr())
+        return self.zdrop
 
     # ---- backward ------------------------------------------------------------------------------------------------
     def backward(self, dlogits: torch.Tensor, on_bucket=None) -> List[torch.Tensor]:
@@ -758,15 +758,119 @@ class DeepLabPlan(tape.PlanTape):
     def _backward_eager(self, dlogits: torch.Tensor, on_bucket=None) -> List[torch.Tensor]:
         s = _lib.stream_ptr()
         ctx, sink, training = self.ctx, self.sink, self.training
-        z = self.head.out
+        lo = self.outc.x
         if self._dlo is None:
             self._dlo = torch.empty_like(self.logits_lo)
-        dlo = self._dlo
-        call("insar_bilinear_bwd", ptr(dlogits), ptr(dlo), self.B * self.K, z.H, z.W, self.H, self.W, s)
-        dzc = self._grad("dzc", self.zc)
-        self.outc.backward(dlo, sink, dzc)
+        call("insar_bilinear_bwd", ptr(dlogits), ptr(self._dlo), self.B * self.K, lo.H, lo.W, self.H, self.W, s)
+        dz = self._grad("dz", lo)                        # gradient wrt the output conv's input
+        self.outc.backward(self._dlo, sink, dz)
+        self._head_backward(dz, sink, training, on_bucket)
+        # residual layers, last to first
+        for li in (3, 2, 1, 0):
+            grp = self.layer_blocks[li]
+            for bi in range(len(grp) - 1, -1, -1):
+                prev = grp[bi - 1] if bi > 0 else (self.layer_blocks[li - 1][-1] if li > 0 else None)
+                grp[bi].backward(sink, training, (prev or self.stem).grad_out(), prev)
+            if li > 0 and on_bucket is not None:
+                on_bucket(self, ("layer", li + 1))
+        self.stem.backward(self.stem.grad_out(), self.x_in, sink, training)
+        if on_bucket is not None:
+            on_bucket(self, ("layer", 1))
+        ctx.join_side()
+        return [sink.view(p) for p in self.grad_params]
+
+    def _dropout_backward(self, dout: Act) -> Act:
+        """Gradient wrt the dropout's input from dout, the gradient wrt its output (dout itself where no mask was applied)."""
+        if not self.drop_active:
+            return dout
+        din = self._grad("ddrop", dout)
+        call("insar_dropout", dout.ref, din.ref, ptr(self.drop_mask), 0, 0, self.drop_p, 0, _lib.stream_ptr())
+        return din
+
+
+class DeepLabPlan(ResNetTrunkPlan):
+    """The head of DeepLabV3_SingleChannel_Attn on the trunk: ASPP, dropout, post_aspp_conv, ChannelAttentionModule
+    (DeepLabV3-ChannelAttention.py:140-162)."""
+
+    def __init__(self, net: DeepLabV3_SingleChannel_Attn, B: int, H: int, W: int, dtype: torch.dtype, device: torch.device):
+        super().__init__(net, B, H, W, dtype, device, "DeepLabV3-CA")
+        ctx, head = self.ctx, net.model.classifier
+        h8, w8 = self.x5.H, self.x5.W
+        A = lambda c: Act.alloc(B, h8, w8, c, dtype, device)
+        # ASPP
+        aspp = head[0]
+        self.cat = A(1280)
+        self.branches = [ConvUnit(ctx, aspp.convs[i][0], aspp.convs[i][1], self.x5, self.cat.slice(256 * i, 256), True, f"aspp.convs.{i}")
+                         for i in range(4)]
+        # The pooling branch runs in fp32 whatever the compute type (B x 2048 values): the pooled vectors of similar tiles
+        # differ by far less than bf16 resolves, and the BatchNorm behind the 1x1 conv divides by that spread.
+        self.ctx32 = ctx
+        if dtype != torch.float32:
+            self.ctx32 = Ctx(device, torch.float32)
+            self.ctx32.side = None               # its (tiny) weight gradient stays on the main stream
+        self.gp = Act.alloc(B, 1, 1, 2048, torch.float32, device)
+        self.pool_unit = ConvUnit(self.ctx32, aspp.convs[4][1], aspp.convs[4][2], self.gp, None, True, "aspp.convs.4")
+        self.project = ConvUnit(ctx, aspp.project[0], aspp.project[1], self.cat, None, True, "aspp.project")
+        self._dropout_setup(aspp.project[3].p, 256)
+        # head: 3x3 conv + BN + ReLU (post_aspp_conv), ChannelAttentionModule, 1x1 classifier
+        self.head = ConvUnit(ctx, head[1], head[2], self.zdrop, None, True, "classifier.1")
+        cam = net.attention_module
+        self.cam_mod, self.cam_cr = cam, cam.mlp[0].out_channels
+        self.zc = A(256)
+        self.cam_rpp = _rows_per_part(B, h8)
+        self.cam_rows = -(-h8 // self.cam_rpp)
+        f = ctx.f32
+        self.cam_psum, self.cam_pmax = f(B * self.cam_rows, 256), f(B * self.cam_rows, 256)
+        self.cam_parg = torch.zeros(B * self.cam_rows, 256, dtype=torch.int32, device=device)
+        self.cam_avg, self.cam_mx, self.cam_gate = f(B, 256), f(B, 256), f(B, 256)
+        self.cam_arg = torch.zeros(B, 256, dtype=torch.int32, device=device)
+        self.cam_ha, self.cam_hm = f(B, self.cam_cr), f(B, self.cam_cr)
+        self.cam_coefB, self.cam_dmax = f(B, 256), f(B, 256)
+        self.cam_red = f(B * self.cam_rows, 2, 256)
+        self.cam_ws = f(B * (256 + 2 * self.cam_cr))
+        self.ones, self.zeros = ctx.const(1.0, 256), ctx.const(0.0, 256)
+        self.outc = OutConvPlan(ctx, head[4], self.zc)
+        # the head's two backward stages, then the trunk's
+        groups = [[head[4].weight, head[4].bias, cam.mlp[0].weight, cam.mlp[2].weight] + self.head.params(),
+                  self.project.params() + self.pool_unit.params() + [p for u in self.branches for p in u.params()]]
+        self._finish(groups + self._trunk_groups(), self.branches + [self.pool_unit, self.project, self.head])
+
+    def _cam_desc(self) -> InsarCam:
+        d = InsarCam()
+        z = self.head.out
+        d.B, d.H, d.W, d.C, d.Cr, d.rows = z.B, z.H, z.W, 256, self.cam_cr, self.cam_rows
+        d.psum, d.pmax, d.parg = ptr(self.cam_psum), ptr(self.cam_pmax), ptr(self.cam_parg)
+        d.w1, d.w2 = ptr(self.cam_mod.mlp[0].weight), ptr(self.cam_mod.mlp[2].weight)
+        d.avg, d.mx, d.arg = ptr(self.cam_avg), ptr(self.cam_mx), ptr(self.cam_arg)
+        d.ha, d.hm, d.gate = ptr(self.cam_ha), ptr(self.cam_hm), ptr(self.cam_gate)
+        d.coefB, d.dmax, d.ws = ptr(self.cam_coefB), ptr(self.cam_dmax), ptr(self.cam_ws)
+        d.accumulate = 0
+        return d
+
+    def _head_forward(self, training: bool) -> None:
+        s = _lib.stream_ptr()
+        # ASPP (:148)
+        for u in self.branches:
+            u.forward(training)
+        hw = self.x5.H * self.x5.W
+        call("insar_sum_hw", self.x5.ref, self.gp.ref, 1.0 / hw, s)
+        self.pool_unit.forward(training)
+        call("insar_broadcast_hw", self.pool_unit.out.ref, self.cat.slice(1024, 256).ref, 1.0, 0, s)
+        self.project.forward(training)
+        self.head.x = self._dropout_forward(self.project.out, training)
+        # head (:151 post_aspp_conv, :154 attention; :157 upsample_conv and :160 resize follow in the trunk)
+        self.head.forward(training)
+        z = self.head.out
+        call("insar_cam_pool", z.ref, ptr(self.cam_psum), ptr(self.cam_pmax), ptr(self.cam_parg), self.cam_rpp, s)
+        dcam = self._cam_desc()
+        call("insar_cam_excite", C.byref(dcam), s)
+        call("insar_bn_relu_apply", z.ref, ptr(self.ones), ptr(self.zeros), ptr(self.cam_gate), self.zc.ref, 0, s)
+
+    def _head_backward(self, dzc: Act, sink: GradSink, training: bool, on_bucket) -> None:
+        s = _lib.stream_ptr()
+        z = self.head.out
         # ChannelAttentionModule backward (csrc/cam.hip)
-        dz = self._grad("dz", z)
+        dz = self._grad("dhead", z)
         call("insar_bnrelu_bwd_reduce", dzc.ref, z.ref, ptr(self.ones), ptr(self.zeros), ptr(self.cam_red), 0, self.cam_rpp, s)
         dcam = self._cam_desc()
         w1, w2 = self.cam_mod.mlp[0].weight, self.cam_mod.mlp[2].weight
@@ -779,13 +883,8 @@ class DeepLabPlan(tape.PlanTape):
         self.head.backward(dz, sink, training, dzdrop)
         if on_bucket is not None:
             on_bucket(self, ("head", 0))
-        if self.drop_active:
-            dproj = self._grad("dproj", self.project.out)
-            call("insar_dropout", dzdrop.ref, dproj.ref, ptr(self.drop_mask), 0, 0, self.drop_p, 0, s)
-        else:
-            dproj = dzdrop
         dcat = self._grad("dcat", self.cat)
-        self.project.backward(dproj, sink, training, dcat)
+        self.project.backward(self._dropout_backward(dzdrop), sink, training, dcat)
         dx5 = self.blocks[-1].grad_out()
         dzp = self._grad("dzp", self.pool_unit.out)
         call("insar_sum_hw", dcat.slice(1024, 256).ref, dzp.ref, 1.0, s)
@@ -801,38 +900,3 @@ class DeepLabPlan(tape.PlanTape):
             call("insar_broadcast_hw", dgp.ref, dx5.ref, 1.0 / (self.x5.H * self.x5.W), 1, s)
         if on_bucket is not None:
             on_bucket(self, ("aspp", 0))
-        # residual layers, last to first
-        if self.dp0 is None:
-            self.dp0 = Act.alloc(self.p0.B, self.p0.H, self.p0.W, 64, ctx.dtype, ctx.device)
-            self.dz0 = Act.alloc(self.z0.B, self.z0.H, self.z0.W, 64, ctx.dtype, ctx.device)
-            self.dy0 = Act.alloc(self.z0.B, self.z0.H, self.z0.W, 64, ctx.dtype, ctx.device)
-        for li in (3, 2, 1, 0):
-            grp = self.layer_blocks[li]
-            for bi in range(len(grp) - 1, -1, -1):
-                blk = grp[bi]
-                prev = grp[bi - 1] if bi > 0 else (self.layer_blocks[li - 1][-1] if li > 0 else None)
-                dx = prev.grad_out() if prev is not None else self.dp0
-                blk.backward(sink, training, dx, prev)
-            if li > 0 and on_bucket is not None:
-                on_bucket(self, ("layer", li + 1))
-        # stem backward: MaxPool gradient, BN + ReLU backward, weight gradient of the 7x7 conv
-        call("insar_maxpool3s2_bwd", self.dp0.ref, ptr(self.pool_arg), self.dz0.ref, s)
-        call("insar_bnrelu_bwd_reduce", self.dz0.ref, self.y0.ref, ptr(self.st_scale), ptr(self.st_shift), ptr(self.st_red), 1,
-             self.st_rpp, s)
-        d = InsarBnSeBwd()
-        d.B, d.H, d.W, d.C, d.Cr, d.use_se = self.B, self.z0.H, self.z0.W, 64, 1, 0
-        d.mean, d.invstd = ptr(self.st_mean), ptr(self.st_invstd)
-        d.dgamma, d.dbeta = ptr(sink.view(self.stem_bn.weight)), ptr(sink.view(self.stem_bn.bias))
-        d.k1, d.k2 = ptr(self.st_k1), ptr(self.st_k2)
-        d.accumulate = 0
-        call("insar_bnse_bwd_coef", C.byref(d), ptr(self.st_red), self.st_red_rows, ptr(self.st_scale), ptr(self.st_shift),
-             ptr(self.st_ws), 0, int(training), s)
-        call("insar_bnrelu_bwd_apply", self.dz0.ref, self.y0.ref, ptr(self.st_scale), ptr(self.st_shift), ptr(self.st_mean),
-             ptr(self.st_invstd), 0, 0, ptr(self.st_k1), ptr(self.st_k2), self.dy0.ref, 1, s)
-        with ctx.side_stream():
-            call("insar_conv7x7s2_wgrad", ptr(self.x_in), self.H, self.W, self.dy0.ref, ptr(self.st_part), _lib.stream_ptr())
-            ctx.colsum(self.st_part, sink.view(self.stem_conv.weight).view(-1), 1, self.st_nb, 64 * 49)
-        if on_bucket is not None:
-            on_bucket(self, ("layer", 1))
-        ctx.join_side()
-        return [sink.view(p) for p in self.grad_params]

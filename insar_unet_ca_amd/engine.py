@@ -645,6 +645,35 @@ def grad_groups(net) -> List[List[torch.nn.Parameter]]:
     return groups
 
 
+def bn_finalize_desc(bn, part: int, rows: int, count: int, C: int, training: bool, conv_bias: int,
+                     scale: int, shift: int, mean: int, invstd: int) -> InsarBnFinalize:
+    """Descriptor of insar_bn_finalize for BatchNorm module `bn`: `rows` rows of per-channel (sum, sum of squares) at `part`
+    over `count` values per channel (the conv's bias, if it has one, is added to the mean), coefficients out to the four
+    pointers. Built per call: the parameter and buffer pointers are re-read every time."""
+    d = InsarBnFinalize()
+    d.part, d.rows, d.count, d.C, d.training = part, rows, count, C, int(training)
+    d.conv_bias = conv_bias
+    d.gamma, d.beta = ptr(bn.weight), ptr(bn.bias)
+    d.running_mean, d.running_var = ptr(bn.running_mean), ptr(bn.running_var)
+    d.num_batches_tracked = ptr(bn.num_batches_tracked)
+    d.momentum = bn.momentum if bn.momentum is not None else 0.1
+    d.eps = bn.eps
+    d.scale, d.shift, d.mean, d.invstd = scale, shift, mean, invstd
+    return d
+
+
+def bn_bwd_desc(B: int, H: int, W: int, C: int, bn, sink: "GradSink", mean, invstd, k1, k2) -> InsarBnSeBwd:
+    """Descriptor of the BatchNorm-backward coefficient launches for a unit without an SE gate (a unit with one adds its
+    fields): dgamma / dbeta into the sink's views of `bn`'s parameters, k1 / k2 for the apply pass."""
+    d = InsarBnSeBwd()
+    d.B, d.H, d.W, d.C, d.Cr, d.use_se = B, H, W, C, 1, 0
+    d.mean, d.invstd = ptr(mean), ptr(invstd)
+    d.dgamma, d.dbeta = ptr(sink.view(bn.weight)), ptr(sink.view(bn.bias))
+    d.k1, d.k2 = ptr(k1), ptr(k2)
+    d.accumulate = 0
+    return d
+
+
 class ConvBN:
     """conv3x3 (bias) -> BatchNorm2d -> ReLU, the unit DoubleConv is made of (:81-86)."""
 
@@ -753,9 +782,7 @@ class ConvBN:
                    stats=self.stats if training else None)
         if training and self.stat_rps:
             call("insar_colsum_partial", ptr(self.stats), ptr(self.sums), self.stat_rows, 2 * self.cout, self.stat_rps, s)
-        bn = self.bn
-        d = InsarBnFinalize()
-        d.part, d.rows, d.count, d.C, d.training = ptr(self.sums), self.fold_rows, self.M, self.cout, int(training)
+        part, rows, count = ptr(self.sums), self.fold_rows, self.M
         if self.sync:
             import torch.distributed as dist
             pg, world = self.sync
@@ -763,14 +790,9 @@ class ConvBN:
                 self.sync_sums = self.ctx.f32(2 * self.cout)
             self.ctx.colsum(self.sums, self.sync_sums, 1, self.fold_rows, 2 * self.cout)
             dist.all_reduce(self.sync_sums, op=dist.ReduceOp.SUM, group=pg)
-            d.part, d.rows, d.count = ptr(self.sync_sums), 1, self.M * world
-        d.conv_bias = ptr(self.conv.bias) if self.conv.bias is not None else 0
-        d.gamma, d.beta = ptr(bn.weight), ptr(bn.bias)
-        d.running_mean, d.running_var = ptr(bn.running_mean), ptr(bn.running_var)
-        d.num_batches_tracked = ptr(bn.num_batches_tracked)
-        d.momentum = bn.momentum if bn.momentum is not None else 0.1
-        d.eps = bn.eps
-        d.scale, d.shift, d.mean, d.invstd = ptr(self.scale), ptr(self.shift), ptr(self.mean), ptr(self.invstd)
+            part, rows, count = ptr(self.sync_sums), 1, self.M * world
+        d = bn_finalize_desc(self.bn, part, rows, count, self.cout, training, ptr(self.conv.bias) if self.conv.bias is not None else 0,
+                             ptr(self.scale), ptr(self.shift), ptr(self.mean), ptr(self.invstd))
         call("insar_bn_finalize", C.byref(d), s)
 
     def apply(self, dst: Act, gate: Optional[torch.Tensor], pooled: Optional[Act] = None,
@@ -850,19 +872,13 @@ class ConvBN:
             call("insar_bnrelu_bwd_reduce", dout.ref, self.y.ref, ptr(self.scale), ptr(self.shift), ptr(self.red_part), 1, self.red_rpp, s)
         red, red_rows = (self.bred, self.bred_rows) if (self.bred_ready and outc_grad is None and pool_grad is None) else (self.red_part, self.red_rows)
         self.bred_ready = False
-        d = InsarBnSeBwd()
-        d.B, d.H, d.W, d.C = B, H, W, self.cout
-        d.Cr = se.cr if se else 1
-        d.use_se = 1 if se else 0
-        d.mean, d.invstd = ptr(self.mean), ptr(self.invstd)
+        d = bn_bwd_desc(B, H, W, self.cout, self.bn, sink, self.mean, self.invstd, self.k1, self.k2)
         if se:
+            d.Cr, d.use_se = se.cr, 1
             d.pooled, d.sq, d.hid, d.gate = ptr(se.pooled), ptr(se.sq), ptr(se.hid), ptr(se.gate)
             d.w1, d.w2 = ptr(se.fc1.weight), ptr(se.fc2.weight)
             d.dw1, d.dw2 = ptr(sink.view(se.fc1.weight)), ptr(sink.view(se.fc2.weight))
             d.coefB = ptr(se.coefB)
-        d.dgamma, d.dbeta = ptr(sink.view(self.bn.weight)), ptr(sink.view(self.bn.bias))
-        d.k1, d.k2 = ptr(self.k1), ptr(self.k2)
-        d.accumulate = 0
         dbias = ptr(sink.view(self.conv.bias)) if self.conv.bias is not None else 0
         coef_args = (C.byref(d), ptr(red), red_rows, ptr(self.scale), ptr(self.shift), ptr(self.bwd_ws),
                      dbias, int(training))
@@ -1197,16 +1213,8 @@ class SAUnit:
         return d
 
     def _finalize(self, conv, bn, stat, k: int, training: bool, s) -> None:
-        d = InsarBnFinalize()
-        d.part, d.rows, d.count, d.C, d.training = ptr(stat), self.rows, self.M, 1, int(training)
-        d.conv_bias = ptr(conv.bias)
-        d.gamma, d.beta = ptr(bn.weight), ptr(bn.bias)
-        d.running_mean, d.running_var = ptr(bn.running_mean), ptr(bn.running_var)
-        d.num_batches_tracked = ptr(bn.num_batches_tracked)
-        d.momentum = bn.momentum if bn.momentum is not None else 0.1
-        d.eps = bn.eps
         base = self.bn.data_ptr() + 16 * k
-        d.scale, d.shift, d.mean, d.invstd = base, base + 4, base + 8, base + 12
+        d = bn_finalize_desc(bn, ptr(stat), self.rows, self.M, 1, training, ptr(conv.bias), base, base + 4, base + 8, base + 12)
         call("insar_bn_finalize", C.byref(d), s)
 
     def forward(self, training: bool, sync=None) -> None:
@@ -1502,7 +1510,6 @@ class UNetPlan(tape.PlanTape):
         # flat-buffer offsets at which each backward stage's gradients are complete (for DP buckets)
         self.stage_sizes = self.sink.group_sizes
         self.stage_ends = [sum(self.stage_sizes[:i + 1]) for i in range(len(self.stage_sizes))]
-        self._closes = {}
         self._gate_events = None
         self.busy = False
         self.training = True
@@ -1513,12 +1520,6 @@ class UNetPlan(tape.PlanTape):
         if self.sa:
             self.bn_modules += [bn for u in self.sa for bn in (u.bn1, u.bn2)]
         self._tape_setup()
-
-    def bucket_closes(self, min_elems: int):
-        if min_elems not in self._closes:
-            from .parallel import plan_buckets
-            self._closes[min_elems] = set(plan_buckets(self.stage_sizes, min_elems))
-        return self._closes[min_elems]
 
     # ---- forward ----------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor, training: bool) -> torch.Tensor:

@@ -138,12 +138,21 @@ def tape_live(fn: Callable[[], None]) -> None:
 
 
 class PlanTape:
-    """Mixin of engine.UNetPlan / deeplab.DeepLabPlan: `forward` / `backward` dispatch between the ordinary code
-    (`_forward_eager`, `_backward_eager`) and the tape of that code."""
+    """Base of the plans (engine.UNetPlan, deeplab.ResNetTrunkPlan and through it DeepLabPlan and fcn.FCNPlan): `forward` /
+    `backward` dispatch between the ordinary code (`_forward_eager`, `_backward_eager`) and the tape of that code."""
 
     def _tape_setup(self) -> None:
         self._tapes: Dict[tuple, dict] = {}
         self._tape_params = list(self.net.parameters())
+        self._closes: Dict[int, set] = {}
+
+    def bucket_closes(self, min_elems: int) -> set:
+        """The backward stages (indices into stage_sizes) after which a data-parallel bucket of at least min_elems gradient
+        elements is complete (parallel.plan_buckets)."""
+        if min_elems not in self._closes:
+            from .parallel import plan_buckets
+            self._closes[min_elems] = set(plan_buckets(self.stage_sizes, min_elems))
+        return self._closes[min_elems]
 
     # what must not change under a tape (cheap to evaluate per call)
     def _tape_key(self, which: str) -> tuple:

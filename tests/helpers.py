@@ -7,6 +7,46 @@ import torch
 from oracle import closed_form as cf
 
 
+def fake_abi_result(name: str, a: tuple) -> int:
+    """What the mocked C ABI (mock_abi) answers: plausible geometry for the host-side queries, 0 (success) for launches."""
+    if name == "insar_igemm_num_mtiles":
+        return (a[0] + 127) // 128
+    if name == "insar_igemm_tile_rows":
+        return 128
+    if name == "insar_wgrad_tile":
+        return 64
+    if name == "insar_wgrad_tile_pair":
+        return (64 << 16) | 64
+    if name == "insar_conv3x3_small_fwd_rows":
+        return 64
+    if name == "insar_conv3x3_small_wgrad_blocks":
+        return min(a[0] * a[1], 512)
+    if name == "insar_conv1x1_out_bwd_blocks":
+        return min(a[0] * a[1], 1024)
+    if name == "insar_ce_blocks":
+        return min((a[0] + 255) // 256, 1024)
+    return 0
+
+
+def mock_abi(monkeypatch, answers=None) -> list:
+    """Replace the C ABI under the package's host code, so that plans build and run on CPU tensors without a kernel: `call`
+    in every module that launches, the stream pointer, the device check. Returns the list that collects the entry-point
+    names in call order. answers: name -> f(*args) for queries that fake_abi_result leaves at 0."""
+    from insar_unet_ca_amd import _lib, deeplab, engine, fcn, modules
+    calls, answers = [], answers or {}
+
+    def fake_call(name, *a):
+        calls.append(name)
+        return answers[name](*a) if name in answers else fake_abi_result(name, a)
+
+    for m in (_lib, engine, modules, deeplab, fcn):
+        monkeypatch.setattr(m, "call", fake_call, raising=False)
+    monkeypatch.setattr(_lib, "stream_ptr", lambda: 0)
+    for m in (modules, deeplab, fcn):
+        monkeypatch.setattr(m, "_require_device", lambda x, who: None, raising=False)
+    return calls
+
+
 def to_np(t):
     if isinstance(t, torch.Tensor):
         return t.detach().double().cpu().numpy()

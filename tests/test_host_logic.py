@@ -11,6 +11,7 @@ from insar_unet_ca_amd import _lib, engine, modules
 from insar_unet_ca_amd.data import SyntheticTiles, make_batch, make_tile
 from insar_unet_ca_amd.parallel import plan_buckets
 from oracle import unet_ca_oracle as orc
+from tests.helpers import mock_abi
 
 
 def test_state_dict_contract_matches_reference(golden):
@@ -68,37 +69,7 @@ def test_unsupported_configurations_fail_loudly():
 
 @pytest.fixture
 def mocked_abi(monkeypatch):
-    calls = []
-
-    def fake_call(name, *a):
-        calls.append(name)
-        if name == "insar_igemm_num_mtiles":
-            return (a[0] + 127) // 128
-        if name == "insar_igemm_tile_rows":
-            return 128
-        if name == "insar_wgrad_tile":
-            return 64
-        if name == "insar_wgrad_tile_pair":
-            return (64 << 16) | 64
-        if name == "insar_wgrad_conv3_tile":
-            return 0
-        if name in ("insar_conv3x3_flat_ok", "insar_conv3x3_flat_num_mtiles"):
-            return 0
-        if name == "insar_conv3x3_small_fwd_rows":
-            return 64
-        if name == "insar_conv3x3_small_wgrad_blocks":
-            return min(a[0] * a[1], 512)
-        if name == "insar_conv1x1_out_bwd_blocks":
-            return min(a[0] * a[1], 1024)
-        if name == "insar_ce_blocks":
-            return min((a[0] + 255) // 256, 1024)
-        return 0
-
-    for m in (_lib, engine, modules):
-        monkeypatch.setattr(m, "call", fake_call, raising=False)
-    monkeypatch.setattr(_lib, "stream_ptr", lambda: 0)
-    monkeypatch.setattr(modules, "_require_device", lambda x, who: None)
-    return calls
+    return mock_abi(monkeypatch)
 
 
 def test_plan_launch_sequence(mocked_abi):

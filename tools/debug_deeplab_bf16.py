@@ -18,7 +18,7 @@ for dt in (torch.float32, torch.bfloat16):
     net = net.to(dev).train()
     logits = net(x)
     plan = next(iter(net._plans.plans.values()))[0]
-    rec = {"y0": plan.y0.nchw(), "z0": plan.z0.nchw(), "p0": plan.p0.nchw()}
+    rec = {"y0": plan.stem.y0.nchw(), "z0": plan.stem.z0.nchw(), "p0": plan.stem.p0.nchw()}
     for blk in plan.blocks:
         rec[blk.name + ".u1.y"] = blk.u1.y.nchw()
         rec[blk.name + ".u2.y"] = blk.u2.y.nchw()
