@@ -584,6 +584,47 @@ int insar_scene_blend(const float* logits, const int32_t* origins, int32_t n, in
 int insar_scene_finalize(const float* acc, const float* wsum, int32_t K, int32_t H, int32_t W, float* prob /*nullable*/,
                          uint8_t* mask, float* conf, void* stream);
 
+/* ---- regions of a class map (build-side addition; the reference has no post-processing): csrc/regions.hip --------------
+ * Connected regions of a class map `mask` uint8 [H][W] (row-major, H * W < 2^31, no tile-multiple requirement). A pixel is
+ * foreground if mask != 0 and, when `conf` fp32 [H][W] is given, conf >= min_conf; two foreground pixels are connected if
+ * they are 4- / 8-neighbours (connectivity 4 | 8) AND carry the same class. A region's root is its smallest row-major pixel
+ * index; regions of area >= min_area are kept and numbered 1..N in ascending root order (scipy.ndimage.label's numbering).
+ * One call per phase, in this order on one stream; seven launches in all, whatever the mask holds; no work-group waits on
+ * another. Every argument is checked before the device is touched (null pointers, H * W, connectivity, max_regions,
+ * alignment).
+ *   scratch: insar_regions_scratch_bytes(...) bytes, 16-byte aligned: int32 parent [H*W], int32 area / id [H*W], block counts.
+ *            Nothing in it has to survive between calls or be cleared by the caller.
+ *   table:   InsarRegion [1 + max_regions], 16-byte aligned. Record 0 is the header: its `area` is N, the TRUE number of kept
+ *            regions, which may exceed max_regions; records 1..min(N, max_regions) are the regions. The kernels never write
+ *            past record max_regions. All statistics are integers (no float atomics): bitwise reproducible. */
+typedef struct InsarRegion {
+  int64_t area;            /* pixels (header record: N) */
+  int64_t sum_y, sum_x;    /* centroid = sum / area */
+  int64_t sum_conf;        /* sum of llrint(clamp(conf, 0, 1) * 2^30); 0 without conf */
+  int32_t y0, x0, y1, x1;  /* half-open bounding box */
+  int32_t root;            /* smallest row-major pixel index */
+  int32_t cls;             /* class value */
+  int32_t _pad[2];
+} InsarRegion;
+/* host only: bytes of scratch for an H x W scene and of a table of max_regions regions */
+int insar_regions_scratch_bytes(int32_t H, int32_t W, int32_t max_regions, int64_t* scratch_bytes, int64_t* table_bytes);
+/* 1 launch: every 32 x 64 tile labelled in LDS; parent[i] = global index of the smallest pixel of i's component WITHIN its
+ * tile, -1 for background; area cleared. conf nullable (then min_conf is ignored). */
+int insar_regions_tiles(const uint8_t* mask, const float* conf /*nullable*/, float min_conf, int32_t H, int32_t W,
+                        int32_t connectivity, void* scratch, void* stream);
+/* 1 launch: unions across tile borders only; every access to parent is an agent-scope atomic. */
+int insar_regions_merge(const uint8_t* mask, int32_t H, int32_t W, int32_t connectivity, void* scratch, void* stream);
+/* 1 launch: parent[i] = root of i; area[root] = pixels of the region. */
+int insar_regions_flatten(int32_t H, int32_t W, void* scratch, void* stream);
+/* 3 launches (per-block counts of kept roots + table cleared; one-work-group scan, N to the header; per-block offsets):
+ * area[root] becomes the region's id (0: dropped); records 1..min(N, max_regions) get root and cls. min_area >= 1. */
+int insar_regions_number(const uint8_t* mask, int32_t H, int32_t W, int64_t min_area, int32_t max_regions, void* scratch,
+                         void* table, void* stream);
+/* 1 launch: labels int32 [H][W] (0: background or dropped), mask_out = mask where labels != 0 else 0, statistics added
+ * into the table. conf nullable (sum_conf stays 0). */
+int insar_regions_relabel(const uint8_t* mask, const float* conf /*nullable*/, int32_t H, int32_t W, int32_t max_regions,
+                          void* scratch, void* table, int32_t* labels, uint8_t* mask_out, void* stream);
+
 /* ---- optimizer: optim.Adam(lr=1e-4) (:466,346), multi-tensor ------------------------------------
  * table: int64[ntensors][5] = {param*, grad*, exp_avg*, exp_avg_sq*, numel}; chunks: int32[nchunks][2]
  * = {tensor index, chunk index}; each chunk covers `chunk_elems` elements. */

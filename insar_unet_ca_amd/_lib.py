@@ -194,6 +194,12 @@ _SIGNATURES = {
     "insar_scene_gather": [_P, _I, _I, _I, _P, _I, _I, _P, _P],
     "insar_scene_blend": [_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "insar_scene_finalize": [_P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "insar_regions_scratch_bytes": [_I, _I, _I, _P, _P],
+    "insar_regions_tiles": [_P, _P, _F, _I, _I, _I, _P, _P],
+    "insar_regions_merge": [_P, _I, _I, _I, _P, _P],
+    "insar_regions_flatten": [_I, _I, _P, _P],
+    "insar_regions_number": [_P, _I, _I, _L, _I, _P, _P, _P],
+    "insar_regions_relabel": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     "insar_adam_step": [_P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P],
     "insar_scale_f32": [_P, _L, _F, _P],
     "insar_mul_dev_f32": [_P, _P, _L, _P, _P],

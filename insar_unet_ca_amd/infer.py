@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from ._lib import InsarError, call, ptr
+from .regions import DEFAULT_MAX_REGIONS, RegionScratch, label_regions
 
 MAX_CLASSES = 8          # SC_MAX_K of csrc/scene.hip: the per-thread accumulators stay in registers up to here
 
@@ -180,7 +181,10 @@ class ScenePredictor:
 
     uint8 scenes are normalised as the reference's data_transforms do (v / 255, then (x - 0.5) / 0.5); float32 scenes are
     taken as already normalised. Works on the current stream; the tile batch, the origin table and the accumulators are
-    kept between calls with the same scene size (the outputs are fresh tensors every call)."""
+    kept between calls with the same scene size (the outputs are fresh tensors every call).
+
+        det = pred.detect(scene, min_area=20, min_conf=0.6)      # predict + regions.label_regions on its mask / conf
+        det["labels"] int32 [H, W]   det["regions"] host table   det["count"] N   det["mask_clean"] uint8 [H, W]"""
 
     def __init__(self, model: torch.nn.Module, tile: int = 256, overlap: int = 32, batch: int = 16, num_classes: int = 2):
         _check_geometry(tile, tile, tile, overlap)
@@ -190,6 +194,7 @@ class ScenePredictor:
         self.model, self.tile, self.overlap, self.batch, self.num_classes = model, int(tile), int(overlap), int(batch), int(num_classes)
         self._geom: dict = {}            # (H, W, device) -> (origins, origins_dev, buf, acc, wsum)
         self._tiles: dict = {}           # device -> float32 [batch, 1, tile, tile]
+        self._regions: dict = {}         # (H, W, device, max_regions) -> RegionScratch
 
     def _buffers(self, H: int, W: int, device: torch.device):
         key = (H, W, device)
@@ -204,6 +209,7 @@ class ScenePredictor:
         """Drop the cached buffers (they are scene-sized)."""
         self._geom.clear()
         self._tiles.clear()
+        self._regions.clear()
 
     @torch.no_grad()
     def predict(self, scene, return_prob: bool = False) -> Dict[str, torch.Tensor]:
@@ -231,7 +237,27 @@ class ScenePredictor:
             self.model.train(was_training)
         return _finalize(acc, wsum, return_prob)
 
+    def detect(self, scene, return_prob: bool = False, **region_kwargs) -> dict:
+        """`predict(scene)` followed by `label_regions(out["mask"], out["conf"], **region_kwargs)`: the predict outputs
+        unchanged, plus "labels", "regions", "count" and the cleaned class map under "mask_clean"."""
+        out = dict(self.predict(scene, return_prob=return_prob))
+        H, W = out["mask"].shape
+        max_regions = region_kwargs.get("max_regions", DEFAULT_MAX_REGIONS)
+        key = (H, W, out["mask"].device, max_regions)
+        if key not in self._regions and isinstance(max_regions, int) and max_regions >= 1:
+            self._regions[key] = RegionScratch(H, W, out["mask"].device, max_regions)
+        reg = label_regions(out["mask"], out["conf"], scratch=self._regions.get(key), **region_kwargs)
+        out.update(labels=reg["labels"], regions=reg["regions"], count=reg["count"], mask_clean=reg["mask"])
+        return out
+
 
 def predict_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw) -> Dict[str, torch.Tensor]:
     """One-shot ScenePredictor(model, **kw).predict(scene, return_prob)."""
     return ScenePredictor(model, **kw).predict(scene, return_prob=return_prob)
+
+
+def detect_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw) -> dict:
+    """One-shot ScenePredictor(model, ...).detect(scene, return_prob, ...): tile / overlap / batch / num_classes go to the
+    predictor, every other keyword to `label_regions`."""
+    pred_kw = {k: kw.pop(k) for k in ("tile", "overlap", "batch", "num_classes") if k in kw}
+    return ScenePredictor(model, **pred_kw).detect(scene, return_prob=return_prob, **kw)
