@@ -625,6 +625,33 @@ int insar_regions_number(const uint8_t* mask, int32_t H, int32_t W, int64_t min_
 int insar_regions_relabel(const uint8_t* mask, const float* conf /*nullable*/, int32_t H, int32_t W, int32_t max_regions,
                           void* scratch, void* table, int32_t* labels, uint8_t* mask_out, void* stream);
 
+/* ---- augmentation and test-time augmentation (build-side addition; the reference resizes and normalises, nothing else):
+ * csrc/augment.hip ------------------------------------------------------------------------------------------------------
+ * A parameter table is a device array int32 [n][4], 16-byte aligned; row s = {int32 op, float gain, float bias, float sigma}
+ * of sample s. D4 op codes 0..7 on an [H][W] plane a, in numpy terms: b = a.T if op & 4 else a; if op & 2: b = b[::-1, :];
+ * if op & 1: b = b[:, ::-1] (rot90(a, 1) is op 6, rot90(a, 3) is op 5; every op is its own inverse except 5 <-> 6). The
+ * kernels use op & 7 and, where H != W, clear bit 2: no content of a table makes them leave the planes.
+ *   aug_hash64(key, i): z = key + 0x9E3779B97F4A7C15 * (i + 1); z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *                       z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31)           (uint64, wrap-around)
+ * Both validate every argument before they touch the device. */
+enum { INSAR_AUG_MASK_NONE = 0, INSAR_AUG_MASK_U8 = 1, INSAR_AUG_MASK_I64 = 2 };
+/* Fill the table for n samples. key = seed ^ (step * 0xD1B54A32D192ED03); h_j = aug_hash64(key, 4 s + j) >> 32, j = 0..3;
+ * op = the (h_0 % popcount(ops_mask))-th set bit of ops_mask (1..255) counting from bit 0; u(h) = (float)(h >> 8) * 2^-24;
+ * gain = gain_lo + (gain_hi - gain_lo) * u(h_1) in fp32, product and sum rounded separately; bias, sigma likewise from
+ * h_2, h_3. lo <= hi, all bounds finite, sigma_lo >= 0. */
+int insar_aug_draw(uint64_t seed, uint64_t step, int32_t n, int32_t ops_mask, float gain_lo, float gain_hi, float bias_lo,
+                   float bias_hi, float sigma_lo, float sigma_hi, int32_t* table, void* stream);
+/* x, xo fp32 [n][C][H][W]; m [n][H][W] uint8 or int64 (m_dtype), mo int64 [n][H][W]; either pair may be null, not both;
+ * never in place; H, W <= 32768. With (i', j') the source index the op of sample s assigns to output (i, j):
+ *   t = gain_s * x[s][c][i'][j']; t = t + bias_s; if sigma_s != 0: t = t + sigma_s * z; xo[s][c][i][j] = t
+ *   mo[s][i][j] = (int64) m[s][i'][j']
+ * z = (float)(S - 131070) * 0x1.bb67aep-16f, S = the sum of the four 16-bit fields of aug_hash64(noise_seed, lin),
+ * lin = ((s * C + c) * H + i) * W + j the OUTPUT index: approximately unit normal, |z| < 3.47. Every product and sum above is
+ * rounded on its own (no fused multiply-add). 16-byte accesses where W % 4 == 0 and the pointers are 16-byte aligned
+ * (uint8 masks: 4-byte), element-wise ones otherwise: misalignment is not an error. */
+int insar_aug_apply(const float* x, float* xo, int32_t C, const void* m, int32_t m_dtype /*INSAR_AUG_MASK_**/, int64_t* mo,
+                    int32_t n, int32_t H, int32_t W, const int32_t* table, uint64_t noise_seed, void* stream);
+
 /* ---- optimizer: optim.Adam(lr=1e-4) (:466,346), multi-tensor ------------------------------------
  * table: int64[ntensors][5] = {param*, grad*, exp_avg*, exp_avg_sq*, numel}; chunks: int32[nchunks][2]
  * = {tensor index, chunk index}; each chunk covers `chunk_elems` elements. */

@@ -12,10 +12,11 @@ from .graph import GraphedTrainStep  # noqa: F401
 from .train import compute_metrics, save_history, train_model, validate_model  # noqa: F401
 from .infer import ScenePredictor, detect_scene, gather_tiles, plan_tiles, predict_scene, stitch_logits, window_1d  # noqa: F401
 from .regions import label_regions  # noqa: F401
+from .augment import Augment  # noqa: F401
 
 __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "ChannelAttentionModule", "MaxPool2d", "CrossEntropyLoss", "DiceLoss", "DiceCELoss", "Adam", "GraphedTrainStep",
            "compute_metrics", "train_model", "validate_model", "save_history", "VOCSegDataset", "SyntheticTiles",
            "ShardedSampler", "DevicePrefetcher", "make_loader", "reference_transforms", "InsarError", "LIB_PATH",
            "SpatialAttention", "UNetSpatialAttention", "FCN_SingleChannel", "FCN_SingleChannel_SE",
            "ScenePredictor", "predict_scene", "stitch_logits", "plan_tiles", "window_1d", "gather_tiles",
-           "FocalLoss", "class_weights", "label_histogram", "label_regions", "detect_scene"]
+           "FocalLoss", "class_weights", "label_histogram", "label_regions", "detect_scene", "Augment"]

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("INSAR_HIP_LIB") or os.path.join(_HERE, "libinsar_hip.
 F32, BF16 = 0, 1
 ABI_VERSION = 8
 SCENE_U8, SCENE_F32 = 0, 1
+AUG_MASK_NONE, AUG_MASK_U8, AUG_MASK_I64 = 0, 1, 2
 IGEMM_OOB_ZERO = 1
 IGEMM_PINGPONG = 2
 
@@ -200,6 +201,8 @@ _SIGNATURES = {
     "insar_regions_flatten": [_I, _I, _P, _P],
     "insar_regions_number": [_P, _I, _I, _L, _I, _P, _P, _P],
     "insar_regions_relabel": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "insar_aug_draw": [C.c_uint64, C.c_uint64, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P],
+    "insar_aug_apply": [_P, _P, _I, _P, _I, _P, _I, _I, _I, _P, C.c_uint64, _P],
     "insar_adam_step": [_P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P],
     "insar_scale_f32": [_P, _L, _F, _P],
     "insar_mul_dev_f32": [_P, _P, _L, _P, _P],

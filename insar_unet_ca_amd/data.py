@@ -228,11 +228,18 @@ class DevicePrefetcher:
     `compact_masks`: int64 masks whose values all lie in 0..255 (class indices and the ignore value 255 of the reference's
     VOC layout) cross the host link as uint8 — an eighth of their bytes, 9.4 instead of 16.8 MB per batch of config 2 —
     and are widened to int64 into the device slot on the copy stream; the yielded tensors are the same int64 masks bit for
-    bit. A batch with any other value takes the plain path."""
+    bit. A batch with any other value takes the plain path.
+    `augment`: an `augment.Augment`. Its transform then runs on the copy stream right after the batch's copy, into a second
+    pair of tensors per slot (guarded by the slot's same two events), and that pair is what is yielded: float32 images and
+    int64 masks, batch k transformed with the object's step k. On the `compact_masks` path the kernel reads the uint8
+    device buffer and writes the int64 masks itself; the widening copy is skipped. Augmentation is for the TRAINING
+    loader: the validation loader gets no `augment`. With augment=None nothing of this exists."""
 
-    def __init__(self, loader, device, slots: int = 2, compact_masks: bool = True):
+    def __init__(self, loader, device, slots: int = 2, compact_masks: bool = True, augment=None):
         self.loader, self.device = loader, torch.device(device)
         self.compact_masks = compact_masks
+        self.augment = augment
+        self._aug = [None] * max(2, slots)          # per slot: the augmented (images, masks) pair that is yielded
         self._pin_u8 = [None] * max(2, slots)
         self._dev_u8 = [None] * max(2, slots)
         if self.device.type != "cuda":
@@ -254,6 +261,9 @@ class DevicePrefetcher:
             self._dev[slot] = (torch.empty(x.shape, dtype=x.dtype, device=self.device),
                                torch.empty(y.shape, dtype=y.dtype, device=self.device))
             self._pin[slot] = None
+            if self.augment is not None:
+                self._aug[slot] = (torch.empty(x.shape, dtype=torch.float32, device=self.device),
+                                   torch.empty(y.shape, dtype=torch.int64, device=self.device))
             # the caching allocator may hand back a block whose last use on the compute stream is still queued (first use
             # of a slot, or a re-allocation for the last, smaller batch): the first copy into it waits for that stream
             self.copy_stream.wait_stream(torch.cuda.current_stream(self.device))
@@ -290,9 +300,12 @@ class DevicePrefetcher:
             self._dev[slot][0].copy_(src[0], non_blocking=True)
             if compact:
                 self._dev_u8[slot].copy_(self._pin_u8[slot], non_blocking=True)
-                self._dev[slot][1].copy_(self._dev_u8[slot])          # widened on the device, on the copy stream
+                if self.augment is None:
+                    self._dev[slot][1].copy_(self._dev_u8[slot])          # widened on the device, on the copy stream
             else:
                 self._dev[slot][1].copy_(src[1], non_blocking=True)
+            if self.augment is not None:
+                self.augment(self._dev[slot][0], self._dev_u8[slot] if compact else self._dev[slot][1], out=self._aug[slot])
             ready = torch.cuda.Event()
             ready.record(self.copy_stream)
         self._ready[slot] = ready
@@ -316,7 +329,7 @@ class DevicePrefetcher:
             if batch is not None:
                 pending.append((nxt, self._stage(nxt, batch)))
             torch.cuda.current_stream(self.device).wait_event(ready)
-            yield self._dev[cur]
+            yield self._dev[cur] if self.augment is None else self._aug[cur]
             done = torch.cuda.Event()
             done.record(torch.cuda.current_stream(self.device))       # the consumer's launches are enqueued up to here
             self._free[cur] = done

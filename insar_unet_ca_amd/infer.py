@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from ._lib import InsarError, call, ptr
+from .augment import D4_INVERSE, apply_table, check_tta, constant_table
 from .regions import DEFAULT_MAX_REGIONS, RegionScratch, label_regions
 
 MAX_CLASSES = 8          # SC_MAX_K of csrc/scene.hip: the per-thread accumulators stay in registers up to here
@@ -183,11 +184,19 @@ class ScenePredictor:
     taken as already normalised. Works on the current stream; the tile batch, the origin table and the accumulators are
     kept between calls with the same scene size (the outputs are fresh tensors every call).
 
+    `tta` = 2, 4 or 8 averages the class probabilities over the D4 ops 0 .. tta - 1 (augment.py: 2 adds the horizontal flip, 4
+    the flips, 8 all flips and rotations): per batch and op, in ascending op order, the tiles are transformed
+    (insar_aug_apply), the net runs, its float32 logits are transformed back with the inverse op and blended at the same
+    origins; the blend adds into acc / wsum, so finalize returns the mean over ops. tta = 1 launches none of this. For a
+    fixed `batch` and `tta` the output is bitwise reproducible.
+
         det = pred.detect(scene, min_area=20, min_conf=0.6)      # predict + regions.label_regions on its mask / conf
         det["labels"] int32 [H, W]   det["regions"] host table   det["count"] N   det["mask_clean"] uint8 [H, W]"""
 
-    def __init__(self, model: torch.nn.Module, tile: int = 256, overlap: int = 32, batch: int = 16, num_classes: int = 2):
+    def __init__(self, model: torch.nn.Module, tile: int = 256, overlap: int = 32, batch: int = 16, num_classes: int = 2,
+                 tta: int = 1):
         _check_geometry(tile, tile, tile, overlap)
+        self.tta = check_tta(tta)
         _check_classes(num_classes)
         if int(batch) != batch or batch < 1:
             raise InsarError(f"batch={batch!r}: a positive integer")
@@ -195,6 +204,7 @@ class ScenePredictor:
         self._geom: dict = {}            # (H, W, device) -> (origins, origins_dev, buf, acc, wsum)
         self._tiles: dict = {}           # device -> float32 [batch, 1, tile, tile]
         self._regions: dict = {}         # (H, W, device, max_regions) -> RegionScratch
+        self._tta: dict = {}             # device -> (tables int32 [8, batch, 4], tiles' and logits' transformed copies)
 
     def _buffers(self, H: int, W: int, device: torch.device):
         key = (H, W, device)
@@ -210,6 +220,26 @@ class ScenePredictor:
         self._geom.clear()
         self._tiles.clear()
         self._regions.clear()
+        self._tta.clear()
+
+    def _tta_buffers(self, device: torch.device):
+        if device not in self._tta:
+            tables = constant_table([op for op in range(8) for _ in range(self.batch)], device).view(8, self.batch, 4)
+            self._tta[device] = (tables, torch.empty(self.batch, 1, self.tile, self.tile, dtype=torch.float32, device=device),
+                                 torch.empty(self.batch, self.num_classes, self.tile, self.tile, dtype=torch.float32, device=device))
+        return self._tta[device]
+
+    def _forward_tta(self, x: torch.Tensor, op: int, n: int, bufs) -> torch.Tensor:
+        """Logits of the n tiles `x` seen through D4 op `op`, brought back to the tiles' own orientation."""
+        tables, xt, lt = bufs
+        apply_table(x, None, tables[op, :n], out=(xt[:n], None))
+        lg = self.model(xt[:n]).detach()
+        if tuple(lg.shape) != (n, self.num_classes, self.tile, self.tile):
+            raise InsarError(f"logits {tuple(lg.shape)}: expected ({n}, {self.num_classes}, {self.tile}, {self.tile})")
+        if lg.dtype != torch.float32 or not lg.is_contiguous():
+            lg = lg.float().contiguous()
+        apply_table(lg, None, tables[D4_INVERSE[op], :n], out=(lt[:n], None))
+        return lt[:n]
 
     @torch.no_grad()
     def predict(self, scene, return_prob: bool = False) -> Dict[str, torch.Tensor]:
@@ -225,6 +255,7 @@ class ScenePredictor:
         K, T = self.num_classes, self.tile
         origins, o_dev, buf, acc, wsum, tiles = self._buffers(H, W, device)
         N = origins.shape[0]
+        tta_bufs = self._tta_buffers(device) if self.tta > 1 else None
         was_training = self.model.training
         self.model.eval()
         try:
@@ -232,7 +263,11 @@ class ScenePredictor:
             for i in range(0, N, self.batch):
                 n = min(self.batch, N - i)
                 x = gather_tiles(sc, o_dev[i:i + n], T, out=tiles[:n])
-                _blend(self.model(x), origins, o_dev, i, K, T, self.overlap, acc, wsum)
+                if self.tta == 1:
+                    _blend(self.model(x), origins, o_dev, i, K, T, self.overlap, acc, wsum)
+                    continue
+                for op in range(self.tta):
+                    _blend(self._forward_tta(x, op, n, tta_bufs), origins, o_dev, i, K, T, self.overlap, acc, wsum)
         finally:
             self.model.train(was_training)
         return _finalize(acc, wsum, return_prob)
@@ -257,7 +292,7 @@ def predict_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw
 
 
 def detect_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw) -> dict:
-    """One-shot ScenePredictor(model, ...).detect(scene, return_prob, ...): tile / overlap / batch / num_classes go to the
-    predictor, every other keyword to `label_regions`."""
-    pred_kw = {k: kw.pop(k) for k in ("tile", "overlap", "batch", "num_classes") if k in kw}
+    """One-shot ScenePredictor(model, ...).detect(scene, return_prob, ...): tile / overlap / batch / num_classes / tta go to
+    the predictor, every other keyword to `label_regions`."""
+    pred_kw = {k: kw.pop(k) for k in ("tile", "overlap", "batch", "num_classes", "tta") if k in kw}
     return ScenePredictor(model, **pred_kw).detect(scene, return_prob=return_prob, **kw)
