@@ -702,6 +702,63 @@ int insar_bilinear_bwd(const float* dout, float* din, int32_t planes, int32_t Hi
 int insar_adam_step_dev(const int64_t* table, const int32_t* chunks, int32_t nchunks, int32_t chunk_elems,
                         float lr, double beta1, double beta2, float eps, float* state, float grad_scale, void* stream);
 
+/* ---- optimizer: AdamW with a global-norm clip, a learning-rate schedule and EMA weights (csrc/optim_w.hip; not in the
+ * reference) --------------------------------------------------------------------------------------------------------
+ * One step is insar_gradnorm_partials (only with clipping or the non-finite check) -> insar_optw_advance ->
+ * insar_adamw_step on one stream. Every per-step scalar lives in an InsarOptwState in DEVICE memory, written by
+ * insar_optw_advance and read by insar_adamw_step, so no launch argument changes from step to step.
+ * table: int64[ntensors][8] = {param*, grad*, exp_avg*, exp_avg_sq*, ema* or 0, numel, bits of float weight_decay (low 32),
+ * bits of float lr_mult (low 32)}; chunks / chunk_elems as for insar_adam_step.
+ *
+ * InsarOptwState (48 bytes, 8-byte aligned; zero-initialised = no step taken, with coef set to 1 by the first advance): */
+typedef struct InsarOptwState {
+  int64_t t;        /*  0: steps taken (skipped steps do not count) */
+  int64_t skipped;  /*  8: steps skipped because the gradient norm was inf or NaN */
+  float bc1;        /* 16: 1 - beta1^t */
+  float bc2_sqrt;   /* 20: sqrt(1 - beta2^t) */
+  float lr;         /* 24: base learning rate of step t (the schedule's value; a tensor uses lr * lr_mult) */
+  float coef;       /* 28: clip coefficient of this step, min(1, max_norm / (norm + 1e-6)); exactly 1 when nothing is clipped */
+  float grad_norm;  /* 32: global L2 norm of grad * grad_scale of this step (written only when the norm pass ran) */
+  float ema_alpha;  /* 36: 1 - decay_t of this step */
+  int32_t skip;     /* 40: 1: insar_adamw_step of this step returns without touching anything */
+  int32_t _pad;     /* 44 */
+} InsarOptwState;
+
+enum { INSAR_SCHED_NONE = 0, INSAR_SCHED_CONSTANT = 1, INSAR_SCHED_COSINE = 2, INSAR_SCHED_POLY = 3 };
+
+/* What is fixed per optimizer (host memory; copied into the launch). With s = t - 1 steps finished before step t:
+ *   s <  warmup_steps: lr_t = lr * (warmup_start + (1 - warmup_start) * s / warmup_steps)
+ *   CONSTANT: lr;  s >= total_steps: min_lr;  q = (s - warmup_steps) / (total_steps - warmup_steps)
+ *   COSINE:   min_lr + (lr - min_lr) * (1 + cos(pi q)) / 2;   POLY: min_lr + (lr - min_lr) * (1 - q)^power
+ * (NONE: lr_t = lr), evaluated in double and rounded to float once. */
+typedef struct InsarOptwConfig {
+  double lr;            /* base learning rate (the first parameter group's) */
+  double beta1, beta2;
+  double max_norm;      /* clip bound on the global gradient norm; < 0: no clipping */
+  double warmup_start;  /* lr factor at s = 0 */
+  double min_lr;
+  double power;
+  double ema_decay;     /* < 0: no EMA; decay_t = min(ema_decay, (1 + t) / (10 + t)) with ema_warmup, else ema_decay */
+  int64_t warmup_steps;
+  int64_t total_steps;
+  int32_t schedule;     /* INSAR_SCHED_* */
+  int32_t skip_nonfinite; /* 1: a step whose gradient norm is inf / NaN is skipped and counted */
+  int32_t ema_warmup;
+  int32_t _pad;
+} InsarOptwConfig;
+
+/* partials[c] = sum over chunk c of (grad * grad_scale)^2: fp32 per thread, wave shuffle, four waves through LDS; no atomics. */
+int insar_gradnorm_partials(const int64_t* table, const int32_t* chunks, int32_t nchunks, int32_t chunk_elems,
+                            float grad_scale, float* partials, void* stream);
+/* One work-group: norm = sqrt(sum of the partials, fixed order, double); coef; then either marks the step skipped or advances
+ * t, the bias corrections (double, as insar_adam_step_dev), lr and the EMA factor. nparts = 0: no norm pass, coef = 1. */
+int insar_optw_advance(const InsarOptwConfig* cfg, const float* partials, int32_t nparts, InsarOptwState* state, void* stream);
+/* g' = grad * (grad_scale * coef); decoupled: p -= (lr * lr_mult * wd) * p, else g' += wd * p; Adam's update of
+ * insar_adam_step with g'; ema += (p_new - ema) * ema_alpha where the row has an EMA pointer. 16-byte accesses where
+ * every pointer of the row is 16-byte aligned, element-wise otherwise. Nothing is written when state->skip is set. */
+int insar_adamw_step(const int64_t* table, const int32_t* chunks, int32_t nchunks, int32_t chunk_elems, float beta1,
+                     float beta2, float eps, float grad_scale, int32_t decoupled, const InsarOptwState* state, void* stream);
+
 /* ---- small helpers ---------------------------------------------------------------------------- */
 int insar_scale_f32(float* p, int64_t n, float s, void* stream);
 /* out[i] = x[i] * *scale, the factor in DEVICE memory: backward of the loss entry points (criterion(...).backward() at :345

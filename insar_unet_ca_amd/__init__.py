@@ -7,7 +7,7 @@ from .modules import ChannelAttentionModule, DoubleConv, MaxPool2d, SELayer, UNe
 from .deeplab import DeepLabV3_SingleChannel_Attn  # noqa: F401
 from .fcn import FCN_SingleChannel, FCN_SingleChannel_SE  # noqa: F401
 from .spatial import SpatialAttention, UNet as UNetSpatialAttention  # noqa: F401
-from .optim import Adam  # noqa: F401
+from .optim import Adam, AdamW, LRSchedule, split_decay_groups  # noqa: F401
 from .graph import GraphedTrainStep  # noqa: F401
 from .train import compute_metrics, save_history, train_model, validate_model  # noqa: F401
 from .infer import ScenePredictor, detect_scene, gather_tiles, plan_tiles, predict_scene, stitch_logits, window_1d  # noqa: F401
@@ -19,4 +19,5 @@ __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "Cha
            "ShardedSampler", "DevicePrefetcher", "make_loader", "reference_transforms", "InsarError", "LIB_PATH",
            "SpatialAttention", "UNetSpatialAttention", "FCN_SingleChannel", "FCN_SingleChannel_SE",
            "ScenePredictor", "predict_scene", "stitch_logits", "plan_tiles", "window_1d", "gather_tiles",
-           "FocalLoss", "class_weights", "label_histogram", "label_regions", "detect_scene", "Augment"]
+           "FocalLoss", "class_weights", "label_histogram", "label_regions", "detect_scene", "Augment",
+           "AdamW", "LRSchedule", "split_decay_groups"]

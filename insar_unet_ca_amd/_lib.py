@@ -90,6 +90,20 @@ class InsarSa(C.Structure):
                 ("dw2", C.c_void_p), ("db2", C.c_void_p), ("dgamma2", C.c_void_p), ("dbeta2", C.c_void_p)]
 
 
+class InsarOptwState(C.Structure):
+    _fields_ = [("t", C.c_int64), ("skipped", C.c_int64), ("bc1", C.c_float), ("bc2_sqrt", C.c_float), ("lr", C.c_float),
+                ("coef", C.c_float), ("grad_norm", C.c_float), ("ema_alpha", C.c_float), ("skip", C.c_int32), ("_pad", C.c_int32)]
+
+
+class InsarOptwConfig(C.Structure):
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("max_norm", C.c_double),
+                ("warmup_start", C.c_double), ("min_lr", C.c_double), ("power", C.c_double), ("ema_decay", C.c_double),
+                ("warmup_steps", C.c_int64), ("total_steps", C.c_int64), ("schedule", C.c_int32),
+                ("skip_nonfinite", C.c_int32), ("ema_warmup", C.c_int32), ("_pad", C.c_int32)]
+
+
+SCHED_NONE, SCHED_CONSTANT, SCHED_COSINE, SCHED_POLY = 0, 1, 2, 3
+
 _P = C.c_void_p
 _I = C.c_int32
 _L = C.c_int64
@@ -207,6 +221,9 @@ _SIGNATURES = {
     "insar_scale_f32": [_P, _L, _F, _P],
     "insar_mul_dev_f32": [_P, _P, _L, _P, _P],
     "insar_adam_step_dev": [_P, _P, _I, _I, _F, C.c_double, C.c_double, _F, _P, _F, _P],
+    "insar_gradnorm_partials": [_P, _P, _I, _I, _F, _P, _P],
+    "insar_optw_advance": [_P, _P, _I, _P, _P],
+    "insar_adamw_step": [_P, _P, _I, _I, _F, _F, _F, _F, _I, _P, _P],
     "insar_pixel_table_taps": [_P, _L, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "insar_conv7x7s2_fwd_rows": [_I, _I],
     "insar_conv7x7s2_fwd": [_P, _I, _I, _P, _AP, _P, _P],
