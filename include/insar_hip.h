@@ -625,6 +625,35 @@ int insar_regions_number(const uint8_t* mask, int32_t H, int32_t W, int64_t min_
 int insar_regions_relabel(const uint8_t* mask, const float* conf /*nullable*/, int32_t H, int32_t W, int32_t max_regions,
                           void* scratch, void* table, int32_t* labels, uint8_t* mask_out, void* stream);
 
+/* ---- overlaps of two label maps (build-side addition; the reference scores pixels only): csrc/overlap.hip ----------------
+ * pred, gt int32 [H][W] (row-major, H * W < 2^31): 0 or a region id >= 1, as insar_regions_relabel writes them. voidmap uint8
+ * [H][W], nullable: a pixel is dropped iff voidmap is given and voidmap[i] == void_value (0..255). Every remaining pixel with
+ * (pred[i], gt[i]) != (0, 0) is counted under the key (pred[i], gt[i]); the rows (p, 0) and columns (0, g) are part of the
+ * table, so the areas after voiding are its row and column sums. Call clear, count, compact in this order on one stream: one
+ * launch each, no allocation, no synchronisation, no work-group waits on another. Every argument is checked before the device is
+ * touched.
+ *   table: insar_overlap_scratch_bytes(...) bytes, 16-byte aligned: a 16-byte header {int64 overflow, int64 reserved}, then
+ *          `capacity` slots {uint64 key = pred << 32 | gt, int64 count}, capacity = the smallest power of two >= 2 * max_pairs;
+ *          open addressing, key 0 = empty. A contribution that finds no slot within `capacity` probe steps sets `overflow` and
+ *          is dropped.
+ *   out:   16-byte aligned: a header {int64 n_keys, int64 overflow}, then InsarOverlap [max_pairs]. n_keys is the TRUE number of
+ *          keys in the table, which may exceed max_pairs; records 0..min(n_keys, max_pairs) - 1 are written, in no specified
+ *          order (sort them; the counts are integer sums, so the sorted table is bitwise reproducible). */
+typedef struct InsarOverlap {
+  int32_t pred, gt;
+  int64_t count;
+} InsarOverlap;
+/* host only: bytes of the table and of the output for 1 <= max_pairs <= 2^24 */
+int insar_overlap_scratch_bytes(int64_t max_pairs, int64_t* table_bytes, int64_t* out_bytes);
+/* 1 launch: the table and the header of `out` zeroed. Once before every count + compact. */
+int insar_overlap_clear(void* table, void* out, int64_t max_pairs, void* stream);
+/* 1 launch: the counts added into the table; every access to the table is an agent-scope atomic. 16-byte loads of the label
+ * maps where H * W % 4 == 0 and the pointers allow it (voidmap: 4-byte), guarded scalars otherwise: misalignment is no error. */
+int insar_overlap_count(const int32_t* pred, const int32_t* gt, const uint8_t* voidmap /*nullable*/, int32_t void_value,
+                        int32_t H, int32_t W, void* table, int64_t max_pairs, void* stream);
+/* 1 launch: the non-empty slots written to `out`, its header filled in. */
+int insar_overlap_compact(const void* table, int64_t max_pairs, void* out, void* stream);
+
 /* ---- augmentation and test-time augmentation (build-side addition; the reference resizes and normalises, nothing else):
  * csrc/augment.hip ------------------------------------------------------------------------------------------------------
  * A parameter table is a device array int32 [n][4], 16-byte aligned; row s = {int32 op, float gain, float bias, float sigma}

@@ -10,8 +10,9 @@ from .spatial import SpatialAttention, UNet as UNetSpatialAttention  # noqa: F40
 from .optim import Adam, AdamW, LRSchedule, split_decay_groups  # noqa: F401
 from .graph import GraphedTrainStep  # noqa: F401
 from .train import compute_metrics, save_history, train_model, validate_model  # noqa: F401
-from .infer import ScenePredictor, detect_scene, gather_tiles, plan_tiles, predict_scene, stitch_logits, window_1d  # noqa: F401
+from .infer import ScenePredictor, detect_scene, evaluate_scene, gather_tiles, plan_tiles, predict_scene, stitch_logits, window_1d  # noqa: F401
 from .regions import label_regions  # noqa: F401
+from .score import DetectionScore, match_from_overlaps, match_regions, region_overlaps  # noqa: F401
 from .augment import Augment  # noqa: F401
 
 __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "ChannelAttentionModule", "MaxPool2d", "CrossEntropyLoss", "DiceLoss", "DiceCELoss", "Adam", "GraphedTrainStep",
@@ -20,4 +21,5 @@ __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "Cha
            "SpatialAttention", "UNetSpatialAttention", "FCN_SingleChannel", "FCN_SingleChannel_SE",
            "ScenePredictor", "predict_scene", "stitch_logits", "plan_tiles", "window_1d", "gather_tiles",
            "FocalLoss", "class_weights", "label_histogram", "label_regions", "detect_scene", "Augment",
-           "AdamW", "LRSchedule", "split_decay_groups"]
+           "AdamW", "LRSchedule", "split_decay_groups",
+           "region_overlaps", "match_regions", "match_from_overlaps", "DetectionScore", "evaluate_scene"]

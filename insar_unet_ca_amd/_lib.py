@@ -215,6 +215,10 @@ _SIGNATURES = {
     "insar_regions_flatten": [_I, _I, _P, _P],
     "insar_regions_number": [_P, _I, _I, _L, _I, _P, _P, _P],
     "insar_regions_relabel": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "insar_overlap_scratch_bytes": [_L, _P, _P],
+    "insar_overlap_clear": [_P, _P, _L, _P],
+    "insar_overlap_count": [_P, _P, _P, _I, _I, _I, _P, _L, _P],
+    "insar_overlap_compact": [_P, _L, _P, _P],
     "insar_aug_draw": [C.c_uint64, C.c_uint64, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P],
     "insar_aug_apply": [_P, _P, _I, _P, _I, _P, _I, _I, _I, _P, C.c_uint64, _P],
     "insar_adam_step": [_P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P],

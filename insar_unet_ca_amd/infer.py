@@ -22,6 +22,7 @@ from . import _lib
 from ._lib import InsarError, call, ptr
 from .augment import D4_INVERSE, apply_table, check_tta, constant_table
 from .regions import DEFAULT_MAX_REGIONS, RegionScratch, label_regions
+from .score import DEFAULT_MAX_PAIRS, OverlapScratch, match_regions
 
 MAX_CLASSES = 8          # SC_MAX_K of csrc/scene.hip: the per-thread accumulators stay in registers up to here
 
@@ -191,7 +192,10 @@ class ScenePredictor:
     fixed `batch` and `tta` the output is bitwise reproducible.
 
         det = pred.detect(scene, min_area=20, min_conf=0.6)      # predict + regions.label_regions on its mask / conf
-        det["labels"] int32 [H, W]   det["regions"] host table   det["count"] N   det["mask_clean"] uint8 [H, W]"""
+        det["labels"] int32 [H, W]   det["regions"] host table   det["count"] N   det["mask_clean"] uint8 [H, W]
+
+        ev = pred.evaluate(scene, gt_mask, iou_threshold=0.5, min_area=20)      # detect + the score against a ground truth
+        ev["score"]["overall"]["pq"]   ev["score"]["gt_match"]   ev["gt_labels"] int32 [H, W]   ev["gt_regions"]"""
 
     def __init__(self, model: torch.nn.Module, tile: int = 256, overlap: int = 32, batch: int = 16, num_classes: int = 2,
                  tta: int = 1):
@@ -205,6 +209,7 @@ class ScenePredictor:
         self._tiles: dict = {}           # device -> float32 [batch, 1, tile, tile]
         self._regions: dict = {}         # (H, W, device, max_regions) -> RegionScratch
         self._tta: dict = {}             # device -> (tables int32 [8, batch, 4], tiles' and logits' transformed copies)
+        self._overlaps: dict = {}        # (H, W, device, max_pairs) -> OverlapScratch
 
     def _buffers(self, H: int, W: int, device: torch.device):
         key = (H, W, device)
@@ -221,6 +226,7 @@ class ScenePredictor:
         self._tiles.clear()
         self._regions.clear()
         self._tta.clear()
+        self._overlaps.clear()
 
     def _tta_buffers(self, device: torch.device):
         if device not in self._tta:
@@ -285,6 +291,32 @@ class ScenePredictor:
         out.update(labels=reg["labels"], regions=reg["regions"], count=reg["count"], mask_clean=reg["mask"])
         return out
 
+    def evaluate(self, scene, gt_mask, *, iou_threshold: float = 0.5, gt_min_area: int = 1, max_pairs: int = DEFAULT_MAX_PAIRS,
+                 **region_kwargs) -> dict:
+        """`detect(scene, **region_kwargs)`, then `label_regions` of the ground-truth class map (`gt_mask` uint8 [H, W], numpy
+        or tensor, copied to the device once; 255 = ignore, labelled as background) with the same connectivity and
+        `min_area=gt_min_area`, then `score.match_regions` with `void=gt_mask, void_value=255`: the detect outputs unchanged,
+        plus "score" (the match result), "gt_labels", "gt_regions" and "gt_count"."""
+        out = self.detect(scene, **region_kwargs)
+        dev = out["mask"].device
+        H, W = out["mask"].shape
+        gt = torch.from_numpy(np.ascontiguousarray(gt_mask)) if isinstance(gt_mask, np.ndarray) else gt_mask
+        if not isinstance(gt, torch.Tensor) or gt.dtype != torch.uint8 or tuple(gt.shape) != (H, W):
+            raise InsarError(f"evaluate: gt_mask must be a uint8 [{H}, {W}] numpy array or tensor, got "
+                             f"{getattr(gt, 'dtype', type(gt).__name__)} {tuple(getattr(gt, 'shape', ()))}")
+        gt = gt.detach().to(dev).contiguous()
+        gt_cls = torch.where(gt == 255, torch.zeros_like(gt), gt)
+        max_regions = region_kwargs.get("max_regions", DEFAULT_MAX_REGIONS)
+        truth = label_regions(gt_cls, None, connectivity=region_kwargs.get("connectivity", 8), min_area=gt_min_area,
+                              max_regions=max_regions, scratch=self._regions.get((H, W, dev, max_regions)))
+        key = (H, W, dev, max_pairs)
+        if key not in self._overlaps and isinstance(max_pairs, int) and max_pairs >= 1:
+            self._overlaps[key] = OverlapScratch(dev, max_pairs)
+        score = match_regions(out, truth, void=gt, void_value=255, iou_threshold=iou_threshold, max_pairs=max_pairs,
+                              num_classes=self.num_classes, scratch=self._overlaps.get(key))
+        out.update(score=score, gt_labels=truth["labels"], gt_regions=truth["regions"], gt_count=truth["count"])
+        return out
+
 
 def predict_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw) -> Dict[str, torch.Tensor]:
     """One-shot ScenePredictor(model, **kw).predict(scene, return_prob)."""
@@ -296,3 +328,10 @@ def detect_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw)
     the predictor, every other keyword to `label_regions`."""
     pred_kw = {k: kw.pop(k) for k in ("tile", "overlap", "batch", "num_classes", "tta") if k in kw}
     return ScenePredictor(model, **pred_kw).detect(scene, return_prob=return_prob, **kw)
+
+
+def evaluate_scene(model: torch.nn.Module, scene, gt_mask, **kw) -> dict:
+    """One-shot ScenePredictor(model, ...).evaluate(scene, gt_mask, ...): tile / overlap / batch / num_classes / tta go to the
+    predictor, every other keyword to `evaluate`."""
+    pred_kw = {k: kw.pop(k) for k in ("tile", "overlap", "batch", "num_classes", "tta") if k in kw}
+    return ScenePredictor(model, **pred_kw).evaluate(scene, gt_mask, **kw)
