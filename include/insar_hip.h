@@ -654,6 +654,38 @@ int insar_overlap_count(const int32_t* pred, const int32_t* gt, const uint8_t* v
 /* 1 launch: the non-empty slots written to `out`, its header filled in. */
 int insar_overlap_compact(const void* table, int64_t max_pairs, void* out, void* stream);
 
+/* ---- distance transform (build-side addition; the reference has no post-processing): csrc/distance.hip --------------------
+ * The exact squared Euclidean distance from every pixel of a map m [B][H][W] (row-major; uint8 with INSAR_DIST_U8, int32 with
+ * INSAR_DIST_I32; B, H, W >= 1, H, W <= 32767, B * H * W < 2^31, no tile-multiple requirement) to the nearest SITE of the same
+ * image, and that site. Images of a batch never see each other. Sites by `site_mode` and `value`:
+ *   INSAR_DIST_EQ    the pixels with m == value
+ *   INSAR_DIST_NE    the pixels with m != value
+ *   INSAR_DIST_EDGE  the pixels p with m[p] != value that have a 4-neighbour q inside the image with m[q] != value and
+ *                    m[q] != m[p]: both sides of a class border, never the image border; `value` is the ignored value, < 0: none
+ *   d2:      int32 [B][H][W]: the squared distance, 0 on sites; INSAR_DIST_FAR where it exceeds max_distance^2 (a pixel at
+ *            exactly max_distance keeps its value) or the image has no site. max_distance <= 0: unbounded.
+ *   nearest: int32 [B][H][W], nullable: the index y * W + x within the image of a nearest site, -1 where d2 is FAR. Of several
+ *            nearest sites the one with the SMALLEST index: the outputs are bitwise defined.
+ *   scratch: insar_dist_scratch_bytes(...) bytes: int16 [B][H][W], the row of the nearest site of each pixel's column. Nothing in
+ *            it has to survive between calls or be cleared by the caller.
+ * Integers only, no atomics, two launches (columns, rows) on the caller's stream. Every argument is checked before the device
+ * is touched (null pointers, sizes, element type, site mode, alignment of the int32 buffers). */
+enum { INSAR_DIST_U8 = 0, INSAR_DIST_I32 = 1 };
+enum { INSAR_DIST_EQ = 0, INSAR_DIST_NE = 1, INSAR_DIST_EDGE = 2 };
+#define INSAR_DIST_FAR 0x7fffffff
+/* host only: bytes of scratch for a B x H x W map (a multiple of 16, monotone in every argument) */
+int insar_dist_scratch_bytes(int32_t B, int32_t H, int32_t W, int64_t* scratch_bytes);
+/* 2 launches. m is never written. */
+int insar_dist_transform(const void* m, int32_t elem_type, int32_t B, int32_t H, int32_t W, int32_t site_mode, int32_t value,
+                         int32_t max_distance, void* scratch, int32_t* d2, int32_t* nearest /*nullable*/, void* stream);
+/* Boundary-band counts of two class maps pred, gt uint8 [H][W] with their EDGE transforms d2_pred, d2_gt: over the pixels
+ * with gt != void_value (0..255, or -1: none), P_c = {pred == c and d2_pred <= r2}, G_c = {gt == c and d2_gt <= r2};
+ * counts int64 [K][3] = (|P_c & G_c|, |P_c|, |G_c|), 2 <= K <= 8, r2 >= 0 (FAR is in no band). 2 launches (a clear, the counts);
+ * integer adds, reduced per thread, wave and work-group before 3 K agent-scope atomics: independent of the launch geometry.
+ * 16-byte loads where H * W % 4 == 0 and the pointers allow it, guarded scalars otherwise: misalignment is no error. */
+int insar_dist_boundary_counts(const uint8_t* pred, const uint8_t* gt, const int32_t* d2_pred, const int32_t* d2_gt, int32_t H,
+                               int32_t W, int64_t r2, int32_t K, int32_t void_value, int64_t* counts, void* stream);
+
 /* ---- augmentation and test-time augmentation (build-side addition; the reference resizes and normalises, nothing else):
  * csrc/augment.hip ------------------------------------------------------------------------------------------------------
  * A parameter table is a device array int32 [n][4], 16-byte aligned; row s = {int32 op, float gain, float bias, float sigma}

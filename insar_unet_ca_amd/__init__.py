@@ -14,6 +14,7 @@ from .infer import ScenePredictor, detect_scene, evaluate_scene, gather_tiles, p
 from .regions import label_regions  # noqa: F401
 from .score import DetectionScore, match_from_overlaps, match_regions, region_overlaps  # noqa: F401
 from .augment import Augment  # noqa: F401
+from .distance import DistanceScratch, boundary_counts, boundary_iou, distance_transform, expand_labels, void_band  # noqa: F401
 
 __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "ChannelAttentionModule", "MaxPool2d", "CrossEntropyLoss", "DiceLoss", "DiceCELoss", "Adam", "GraphedTrainStep",
            "compute_metrics", "train_model", "validate_model", "save_history", "VOCSegDataset", "SyntheticTiles",
@@ -22,4 +23,5 @@ __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "Cha
            "ScenePredictor", "predict_scene", "stitch_logits", "plan_tiles", "window_1d", "gather_tiles",
            "FocalLoss", "class_weights", "label_histogram", "label_regions", "detect_scene", "Augment",
            "AdamW", "LRSchedule", "split_decay_groups",
-           "region_overlaps", "match_regions", "match_from_overlaps", "DetectionScore", "evaluate_scene"]
+           "region_overlaps", "match_regions", "match_from_overlaps", "DetectionScore", "evaluate_scene",
+           "DistanceScratch", "distance_transform", "void_band", "expand_labels", "boundary_counts", "boundary_iou"]

@@ -18,6 +18,9 @@ F32, BF16 = 0, 1
 ABI_VERSION = 8
 SCENE_U8, SCENE_F32 = 0, 1
 AUG_MASK_NONE, AUG_MASK_U8, AUG_MASK_I64 = 0, 1, 2
+DIST_U8, DIST_I32 = 0, 1
+DIST_EQ, DIST_NE, DIST_EDGE = 0, 1, 2
+DIST_FAR = 0x7FFFFFFF
 IGEMM_OOB_ZERO = 1
 IGEMM_PINGPONG = 2
 
@@ -219,6 +222,9 @@ _SIGNATURES = {
     "insar_overlap_clear": [_P, _P, _L, _P],
     "insar_overlap_count": [_P, _P, _P, _I, _I, _I, _P, _L, _P],
     "insar_overlap_compact": [_P, _L, _P, _P],
+    "insar_dist_scratch_bytes": [_I, _I, _I, _P],
+    "insar_dist_transform": [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "insar_dist_boundary_counts": [_P, _P, _P, _P, _I, _I, _L, _I, _I, _P, _P],
     "insar_aug_draw": [C.c_uint64, C.c_uint64, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P],
     "insar_aug_apply": [_P, _P, _I, _P, _I, _P, _I, _I, _I, _P, C.c_uint64, _P],
     "insar_adam_step": [_P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P],

@@ -21,6 +21,7 @@ import torch
 from . import _lib
 from ._lib import InsarError, call, ptr
 from .augment import D4_INVERSE, apply_table, check_tta, constant_table
+from .distance import DistanceScratch, boundary_counts, boundary_iou
 from .regions import DEFAULT_MAX_REGIONS, RegionScratch, label_regions
 from .score import DEFAULT_MAX_PAIRS, OverlapScratch, match_regions
 
@@ -210,6 +211,7 @@ class ScenePredictor:
         self._regions: dict = {}         # (H, W, device, max_regions) -> RegionScratch
         self._tta: dict = {}             # device -> (tables int32 [8, batch, 4], tiles' and logits' transformed copies)
         self._overlaps: dict = {}        # (H, W, device, max_pairs) -> OverlapScratch
+        self._distance: dict = {}        # (H, W, device) -> DistanceScratch
 
     def _buffers(self, H: int, W: int, device: torch.device):
         key = (H, W, device)
@@ -227,6 +229,7 @@ class ScenePredictor:
         self._regions.clear()
         self._tta.clear()
         self._overlaps.clear()
+        self._distance.clear()
 
     def _tta_buffers(self, device: torch.device):
         if device not in self._tta:
@@ -292,11 +295,13 @@ class ScenePredictor:
         return out
 
     def evaluate(self, scene, gt_mask, *, iou_threshold: float = 0.5, gt_min_area: int = 1, max_pairs: int = DEFAULT_MAX_PAIRS,
-                 **region_kwargs) -> dict:
+                 boundary_distance: Optional[int] = None, **region_kwargs) -> dict:
         """`detect(scene, **region_kwargs)`, then `label_regions` of the ground-truth class map (`gt_mask` uint8 [H, W], numpy
         or tensor, copied to the device once; 255 = ignore, labelled as background) with the same connectivity and
         `min_area=gt_min_area`, then `score.match_regions` with `void=gt_mask, void_value=255`: the detect outputs unchanged,
-        plus "score" (the match result), "gt_labels", "gt_regions" and "gt_count"."""
+        plus "score" (the match result), "gt_labels", "gt_regions" and "gt_count". With `boundary_distance` = d (an integer
+        >= 0) the score gains "boundary" = {"distance", "counts", "iou", "mean_iou"}: `distance.boundary_counts` of
+        "mask_clean" against `gt_mask` (void 255) at d pixels, and `boundary_iou` of them; with None nothing of it runs."""
         out = self.detect(scene, **region_kwargs)
         dev = out["mask"].device
         H, W = out["mask"].shape
@@ -314,6 +319,13 @@ class ScenePredictor:
             self._overlaps[key] = OverlapScratch(dev, max_pairs)
         score = match_regions(out, truth, void=gt, void_value=255, iou_threshold=iou_threshold, max_pairs=max_pairs,
                               num_classes=self.num_classes, scratch=self._overlaps.get(key))
+        if boundary_distance is not None:
+            key = (H, W, dev)
+            if key not in self._distance:
+                self._distance[key] = DistanceScratch(1, H, W, dev)
+            counts = boundary_counts(out["mask_clean"], gt, boundary_distance, self.num_classes, void_value=255,
+                                     scratch=self._distance[key])
+            score["boundary"] = {"distance": int(boundary_distance), "counts": counts, **boundary_iou(counts)}
         out.update(score=score, gt_labels=truth["labels"], gt_regions=truth["regions"], gt_count=truth["count"])
         return out
 

@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from ._lib import InsarError, call, ptr
+from .distance import boundary_iou
 
 DEFAULT_MAX_PAIRS = 262144
 MAX_PAIRS_LIMIT = 1 << 24
@@ -294,7 +295,10 @@ class DetectionScore:
         score = DetectionScore(num_classes=2, iou_threshold=0.5)
         for scene, gt_mask in scenes:
             score.update(predictor.evaluate(scene, gt_mask)["score"])
-        score.compute()["overall"]["pq"]"""
+        score.compute()["overall"]["pq"]
+
+    Results that carry boundary-band counts (`evaluate(..., boundary_distance=d)`: match_result["boundary"]) have them added up
+    too, and `compute()` then reports "boundary" = {"distance", "counts", "iou", "mean_iou", "scenes"} of the sums."""
 
     def __init__(self, num_classes: int, iou_threshold: float = 0.5):
         if int(num_classes) != num_classes or num_classes < 2:
@@ -307,6 +311,7 @@ class DetectionScore:
         self.tp, self.fp, self.fn = (np.zeros(K, dtype=np.int64) for _ in range(3))
         self.iou_sum = np.zeros(K, dtype=np.float64)
         self.scenes = 0
+        self.boundary_counts, self.boundary_distance, self.boundary_scenes = None, None, 0
 
     def update(self, match_result: dict) -> None:
         if match_result["num_classes"] != self.num_classes or match_result["iou_threshold"] != self.iou_threshold:
@@ -318,9 +323,22 @@ class DetectionScore:
         self.fn += pc["fn"]
         self.iou_sum += pc["iou_sum"]
         self.scenes += 1
+        b = match_result.get("boundary")
+        if b is not None:
+            counts = np.asarray(b["counts"], dtype=np.int64)
+            if counts.shape != (self.num_classes, 3) or self.boundary_distance not in (None, b["distance"]):
+                raise InsarError(f"DetectionScore(num_classes={self.num_classes}): boundary counts of {counts.shape} at distance "
+                                 f"{b['distance']} after counts at distance {self.boundary_distance}")
+            self.boundary_counts = counts.copy() if self.boundary_counts is None else self.boundary_counts + counts
+            self.boundary_distance = b["distance"]
+            self.boundary_scenes += 1
 
     def compute(self) -> dict:
         """{"per_class": ..., "overall": ..., "scenes": n}: `detection_scores` of the accumulated counts."""
-        return {"per_class": detection_scores(self.tp.copy(), self.fp.copy(), self.fn.copy(), self.iou_sum.copy()),
-                "overall": detection_scores(int(self.tp.sum()), int(self.fp.sum()), int(self.fn.sum()), float(self.iou_sum.sum())),
-                "scenes": self.scenes}
+        out = {"per_class": detection_scores(self.tp.copy(), self.fp.copy(), self.fn.copy(), self.iou_sum.copy()),
+               "overall": detection_scores(int(self.tp.sum()), int(self.fp.sum()), int(self.fn.sum()), float(self.iou_sum.sum())),
+               "scenes": self.scenes}
+        if self.boundary_counts is not None:
+            out["boundary"] = {"distance": self.boundary_distance, "counts": self.boundary_counts.copy(),
+                               "scenes": self.boundary_scenes, **boundary_iou(self.boundary_counts)}
+        return out

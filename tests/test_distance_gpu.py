@@ -1,0 +1,330 @@
+"""GPU: the distance transform (insar_unet_ca_amd/distance.py on csrc/distance.hip) and its consumers against the oracles of
+tests/distance_ref.py (pinned in tests/test_distance_host.py).
+
+Every comparison is exact: d2, nearest, counts and the maps are integers; iou is compared to rtol 1e-12 (the same integers
+divided in float64 on both sides). The base map is 200 x 264: ragged against 64 lanes, 256 threads and the 32-row bands of the
+column pass (200 = 6 bands + 8 rows, 264 = one work-group of columns + 8)."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from tests.distance_ref import (FAR, boundary_counts_oracle, cap, dist_oracle, expand_labels_oracle, nearest_oracle, sites_oracle,
+                                striped_random, void_band_oracle, void_map)
+
+pytestmark = pytest.mark.gpu
+H0, W0 = 200, 264
+MODES = {"eq2": (("eq", 2), None), "ne0": (("ne", 0), None), "edge": ("edge", None), "edge_ignore": ("edge", 255)}
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a ROCm device")
+    from insar_unet_ca_amd import _lib
+    _lib.load()
+    return torch.device("cuda:0")
+
+
+@functools.lru_cache(maxsize=None)
+def base_map(fill, with_void):
+    m = striped_random(H0, W0, fill, seed=int(fill * 1000))
+    if with_void:
+        m[void_map(H0, W0, seed=7)] = 255
+    m.setflags(write=False)
+    return m
+
+
+@functools.lru_cache(maxsize=None)
+def base_reference(fill, mode):
+    """(sites, uncapped d2 int64) of the base map: computed once, shared by every case that needs it."""
+    sites, ignore = MODES[mode]
+    site = sites_oracle(base_map(fill, ignore is not None), sites, ignore)
+    d2 = dist_oracle(site)
+    site.setflags(write=False), d2.setflags(write=False)
+    return site, d2
+
+
+def run(dev, m, **kw):
+    """(d2, nearest) as numpy arrays of distance_transform(..., return_nearest=True) on a host map; m must not be written."""
+    import insar_unet_ca_amd as iu
+    t = torch.from_numpy(np.ascontiguousarray(m)).to(dev)
+    before = t.clone()
+    out = iu.distance_transform(t, return_nearest=True, **kw)
+    assert out["d2"].dtype == torch.int32 and out["nearest"].dtype == torch.int32 and out["d2"].shape == t.shape
+    assert torch.equal(t, before), "the input was written"
+    return out["d2"].cpu().numpy(), out["nearest"].cpu().numpy()
+
+
+def check_nearest_is_consistent(site, d2, near):
+    """nearest names a site at exactly the distance d2 (its minimality is d2's; the index rule is checked on small maps)."""
+    H, W = site.shape
+    far = d2 == FAR
+    assert ((near == -1) == far).all()
+    ny, nx = np.divmod(np.where(far, 0, near), W)
+    yy, xx = np.indices((H, W))
+    ok = site[ny, nx] & ((yy - ny).astype(np.int64) ** 2 + (xx - nx).astype(np.int64) ** 2 == d2)
+    assert (ok | far).all()
+
+
+# ---- random maps ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [np.uint8, np.int32])
+@pytest.mark.parametrize("mode", list(MODES))
+@pytest.mark.parametrize("fill", [0.002, 0.05, 0.5])
+def test_random_maps(dev, fill, mode, dtype):
+    sites, ignore = MODES[mode]
+    m = base_map(fill, ignore is not None).astype(dtype)
+    site, want = base_reference(fill, mode)
+    for R in (1, 5, 32, None):
+        d2, near = run(dev, m, sites=sites, ignore_value=ignore, max_distance=R)
+        ref = cap(want, R)
+        bad = d2 != ref
+        print(f"fill {fill} {mode} {np.dtype(dtype).name} R={R}: {int(site.sum())} sites, largest d2 {int(ref[ref != FAR].max(initial=0))}, "
+              f"{int((ref == FAR).sum())} FAR, {int(bad.sum())} differ")
+        assert not bad.any()
+        if R is not None:                                             # every value <= R^2 is kept, every larger one is FAR
+            assert (d2[want <= R * R] == want[want <= R * R]).all() and (d2[want > R * R] == FAR).all()
+        check_nearest_is_consistent(site, d2, near)
+    assert (d2 == 0).sum() == site.sum()
+
+
+def test_a_pixel_at_exactly_max_distance_keeps_its_value(dev):
+    m = np.zeros((40, 40), dtype=np.uint8)
+    m[10, 10] = 1
+    d2, near = run(dev, m, sites=("eq", 1), max_distance=5)
+    assert d2[13, 14] == 25 and d2[14, 13] == 25 and d2[15, 10] == 25 and d2[10, 15] == 25 and d2[6, 7] == 25       # 3-4-5, 5-0
+    assert d2[10, 16] == FAR and d2[14, 14] == FAR and d2[16, 10] == FAR and near[10, 16] == -1                     # 36, 32, 36
+    assert near[13, 14] == 10 * 40 + 10 and d2[10, 10] == 0
+    assert (d2 == cap(dist_oracle(m == 1), 5)).all()
+
+
+# ---- degenerate shapes ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", [(1, 1), (1, 300), (300, 1), (3, 5), (7, 65)])
+def test_degenerate_shapes(dev, shape):
+    H, W = shape
+    zeros = np.zeros(shape, dtype=np.uint8)
+    for R in (3, None):
+        d2, near = run(dev, zeros, sites=("ne", 0), max_distance=R)          # no site
+        assert (d2 == FAR).all() and (near == -1).all()
+        d2, near = run(dev, zeros, sites="edge", max_distance=R)             # one class: no border, the image border is none
+        assert (d2 == FAR).all() and (near == -1).all()
+        d2, near = run(dev, zeros, sites=("eq", 0), max_distance=R)          # all sites
+        assert (d2 == 0).all() and (near == np.arange(H * W).reshape(shape)).all()
+    rng = np.random.default_rng(H * 1000 + W)
+    for fill in (0.02, 0.4):
+        m = (rng.random(shape) < fill).astype(np.int32) * 7
+        for R in (2, None):
+            d2, near = run(dev, m, sites=("eq", 7), max_distance=R)
+            wd, wn = nearest_oracle(m == 7, R)
+            assert (d2 == wd).all() and (near == wn).all(), (shape, fill, R)
+
+
+# ---- long distances across band joins -----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", [(70, 600), (600, 70)])
+def test_long_distances(dev, shape):
+    H, W = shape
+    yy, xx = np.indices(shape)
+    for cy, cx in ((0, 0), (H - 1, W - 1), (H - 1, 0)):
+        m = np.zeros(shape, dtype=np.uint8)
+        m[cy, cx] = 3
+        d2, near = run(dev, m, sites=("eq", 3), max_distance=None)
+        assert (d2 == (yy - cy) ** 2 + (xx - cx) ** 2).all() and (near == cy * W + cx).all()
+        assert d2.max() == 599 ** 2 + 69 ** 2
+    for axis in (0, 1):                                               # sites in the first and last row / column only
+        m = np.zeros(shape, dtype=np.uint8)
+        rng = np.random.default_rng(axis)
+        if axis == 0:
+            m[0, rng.random(W) < 0.2], m[-1, rng.random(W) < 0.2] = 1, 1
+        else:
+            m[rng.random(H) < 0.2, 0], m[rng.random(H) < 0.2, -1] = 1, 1
+        site = m == 1
+        d2, near = run(dev, m, sites=("ne", 0), max_distance=None)
+        assert (d2 == cap(dist_oracle(site), None)).all()
+        check_nearest_is_consistent(site, d2, near)
+        d2c, _ = run(dev, m, sites=("ne", 0), max_distance=40)
+        assert (d2c == cap(dist_oracle(site), 40)).all()
+
+
+def test_the_widest_row_of_the_contract(dev):
+    """1 x 32767, one site in a corner, unbounded: d2 reaches 32766^2 and every column but one holds no site, so FAR + k^2
+    would overflow int32 wherever it was formed."""
+    W = 32767
+    x = np.arange(W, dtype=np.int64)
+    for cx in (0, W - 1):
+        m = np.zeros((1, W), dtype=np.uint8)
+        m[0, cx] = 1
+        d2, near = run(dev, m, sites=("eq", 1), max_distance=None)
+        assert (d2[0] == (x - cx) ** 2).all() and (near == cx).all() and d2.max() == 32766 ** 2
+    d2, near = run(dev, m.T, sites=("eq", 1), max_distance=None)             # 32767 x 1: the column pass alone
+    assert (d2[:, 0] == (x - cx) ** 2).all() and (near == cx).all()
+
+
+# ---- ties ---------------------------------------------------------------------------------------------------------------------
+def test_ties_go_to_the_smallest_index(dev):
+    def at(points):
+        m = np.zeros((24, 24), dtype=np.uint8)
+        for y, x in points:
+            m[y, x] = 1
+        d2, near = run(dev, m, sites=("ne", 0), max_distance=None)
+        wd, wn = nearest_oracle(m != 0)
+        assert (d2 == wd).all() and (near == wn).all()
+        return d2, near
+    d2, near = at([(0, 10), (10, 0)])                                 # from (0, 0): k^2 == best when the loop reaches k = 10
+    assert d2[0, 0] == 100 and near[0, 0] == 10
+    d2, near = at([(5, 10), (5, 20)])
+    assert d2[5, 15] == 25 and near[5, 15] == 5 * 24 + 10
+    d2, near = at([(0, 5), (10, 5)])
+    assert d2[5, 5] == 25 and near[5, 5] == 5
+    d2, near = at([(3, 7), (7, 3), (3, 3), (7, 7), (11, 3), (3, 11)])
+    assert d2[5, 5] == 8 and near[5, 5] == 3 * 24 + 3
+
+
+@pytest.mark.parametrize("fill", [0.002, 0.05, 0.5])
+def test_nearest_in_full_on_random_maps(dev, fill):
+    m = striped_random(96, 130, fill, seed=int(fill * 1000) + 1)
+    for sites in (("ne", 0), "edge"):
+        site = sites_oracle(m, sites, None)
+        for R in (5, None):
+            d2, near = run(dev, m, sites=sites, max_distance=R)
+            wd, wn = nearest_oracle(site, R)
+            assert (d2 == wd).all() and (near == wn).all(), (fill, sites, R, int((near != wn).sum()))
+
+
+# ---- batch, reproducibility -----------------------------------------------------------------------------------------------------
+def test_images_of_a_batch_never_see_each_other(dev):
+    H, W = 100, 136
+    m = np.stack([striped_random(H, W, 0.01, seed=1), np.zeros((H, W), dtype=np.uint8), np.full((H, W), 2, dtype=np.uint8)])
+    for sites, R in ((("ne", 0), None), (("ne", 0), 6), ("edge", None)):
+        d2, near = run(dev, m, sites=sites, max_distance=R)
+        for b in range(3):
+            d1, n1 = run(dev, m[b], sites=sites, max_distance=R)
+            assert (d2[b] == d1).all() and (near[b] == n1).all(), (sites, R, b)
+    d2, near = run(dev, m, sites=("ne", 0), max_distance=None)
+    assert (d2[1] == FAR).all() and (near[1] == -1).all() and (d2[2] == 0).all() and (near[2] == np.arange(H * W).reshape(H, W)).all()
+    assert (d2[0] == cap(dist_oracle(m[0] != 0), None)).all()
+
+
+def test_calls_are_byte_identical_and_scratch_is_reusable(dev):
+    import insar_unet_ca_amd as iu
+    m = torch.from_numpy(base_map(0.05, True).copy()).to(dev)
+    kw = dict(sites="edge", ignore_value=255, max_distance=32, return_nearest=True)
+    first = iu.distance_transform(m, **kw)
+    sc = iu.DistanceScratch(1, H0, W0, dev)
+    sc.scratch.fill_(0xFF)                                            # nothing relies on cleared buffers
+    for k in range(3):
+        again = iu.distance_transform(m, scratch=sc if k % 2 == 0 else None, **kw)
+        assert torch.equal(first["d2"], again["d2"]) and torch.equal(first["nearest"], again["nearest"]), k
+    assert set(iu.distance_transform(m, sites="edge")) == {"d2"}
+    assert torch.equal(iu.distance_transform(m, sites="edge", ignore_value=255, scratch=sc)["d2"], first["d2"])
+
+
+# ---- the consumers ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("width", [0, 1, 3, 7])
+def test_void_band(dev, width):
+    import insar_unet_ca_amd as iu
+    m = np.stack([base_map(0.05, True), base_map(0.5, True)])
+    t = torch.from_numpy(m.copy()).to(dev)
+    got = iu.void_band(t, width)
+    assert got.dtype == torch.uint8 and got.shape == t.shape and (t.cpu().numpy() == m).all()
+    for b in range(2):
+        want = void_band_oracle(m[b], width)
+        assert (got[b].cpu().numpy() == want).all(), (width, b)
+        assert (want[m[b] == 255] == 255).all()
+    other = iu.void_band(t[0], width, void_value=9, ignore_value=None).cpu().numpy()
+    assert (other == void_band_oracle(m[0], width, void_value=9, ignore_value=None)).all()
+
+
+@pytest.mark.parametrize("distance", [0, 1, 3, 7])
+def test_expand_labels(dev, distance):
+    import insar_unet_ca_amd as iu
+    mask = torch.from_numpy(striped_random(96, 130, 0.03, seed=11)).to(dev)
+    labels = iu.label_regions(mask, connectivity=8)["labels"]
+    before = labels.clone()
+    got = iu.expand_labels(labels, distance)
+    assert got.dtype == torch.int32 and torch.equal(labels, before)
+    host = before.cpu().numpy()
+    assert (got.cpu().numpy() == expand_labels_oracle(host, distance)).all()
+    assert (got.cpu().numpy()[host != 0] == host[host != 0]).all()
+    # regions exactly 2 * distance + 1 apart meet without merging; the batch form gives the same
+    pair = np.zeros((2, 9, 40), dtype=np.int32)
+    pair[0, 4, 5], pair[0, 4, 5 + 2 * distance + 1] = 4, 9
+    pair[1, 2, 30] = 6
+    g = iu.expand_labels(torch.from_numpy(pair).to(dev), distance).cpu().numpy()
+    assert (g[0] == expand_labels_oracle(pair[0], distance)).all() and (g[1] == expand_labels_oracle(pair[1], distance)).all()
+    assert (g[0, 4, 5:5 + distance + 1] == 4).all() and (g[0, 4, 5 + distance + 1:5 + 2 * distance + 2] == 9).all()
+
+
+@pytest.mark.parametrize("shape", [(H0, W0), (199, 263)])
+def test_boundary_counts(dev, shape):
+    import insar_unet_ca_amd as iu
+    H, W = shape
+    pred = striped_random(H, W, 0.5, seed=31)
+    gt = np.roll(pred, (1, 2), axis=(0, 1))
+    gt[void_map(H, W, seed=32)] = 255
+    p, g = torch.from_numpy(pred).to(dev), torch.from_numpy(gt).to(dev)
+    sc = iu.DistanceScratch(1, H, W, dev)
+    for d in (0, 1, 3, 7):
+        want = boundary_counts_oracle(pred, gt, d, 4)
+        got = iu.boundary_counts(p, g, d, 4, scratch=sc if d % 2 else None)
+        print(f"{shape} d={d}: {got.tolist()}")
+        assert got.dtype == np.int64 and got.shape == (4, 3) and (got == want).all()
+        a, b = iu.boundary_iou(got), iu.boundary_iou(want)
+        np.testing.assert_allclose(a["iou"], b["iou"], rtol=1e-12)
+        assert a["mean_iou"] == pytest.approx(b["mean_iou"], rel=1e-12) and 0 < a["mean_iou"] < 1
+    assert (p.cpu().numpy() == pred).all() and (g.cpu().numpy() == gt).all()
+    # fewer classes than the maps hold: the others are in no set; no void map at all
+    assert (iu.boundary_counts(p, g, 3, 2) == boundary_counts_oracle(pred, gt, 3, 2)).all()
+    assert (iu.boundary_counts(p, g, 3, 4, void_value=None) == boundary_counts_oracle(pred, gt, 3, 4, void_value=None)).all()
+    same = iu.boundary_iou(iu.boundary_counts(p, p, 3, 4))
+    assert (same["iou"] == 1.0).all() and same["mean_iou"] == 1.0
+
+
+# ---- end to end -----------------------------------------------------------------------------------------------------------------
+def test_evaluate_with_and_without_the_boundary_score(dev):
+    import insar_unet_ca_amd as iu
+    from tests.test_score_gpu import blobs
+    T, o, H, W = 64, 8, 128, 192
+    torch.manual_seed(5)
+    net = iu.UNet(in_channels=1, num_classes=2, use_se=True).to(dev).eval()
+    pred = iu.ScenePredictor(net, tile=T, overlap=o, batch=4, num_classes=2)
+    scenes, truths = [], []
+    for k in range(2):
+        scenes.append(np.random.default_rng(91 + k).standard_normal((H, W)).astype(np.float32))
+        g = blobs(H, W, seed=92 + k)
+        g[g > 1] = 1
+        g[:6], g[-6:], g[:, :6], g[:, -6:] = 255, 255, 255, 255
+        truths.append(g)
+    kw = dict(connectivity=8, min_area=3, min_conf=float(pred.predict(scenes[0])["conf"].median()), iou_threshold=0.3, gt_min_area=2)
+    plain = pred.evaluate(scenes[0], truths[0], **kw)
+    assert set(plain) == {"mask", "conf", "labels", "regions", "count", "mask_clean", "score", "gt_labels", "gt_regions", "gt_count"}
+    score_keys = {"gt_match", "gt_iou", "pred_match", "pred_iou", "pred_area", "gt_area", "iou_threshold", "num_classes",
+                  "confusion", "per_class", "overall", "ap", "ap_mean", "overlaps"}
+    assert set(plain["score"]) == score_keys and not pred._distance
+    acc, total = iu.DetectionScore(2, 0.3), np.zeros((2, 3), dtype=np.int64)
+    for scene, g in zip(scenes, truths):
+        ev = pred.evaluate(scene, g, boundary_distance=3, **kw)
+        want = boundary_counts_oracle(ev["mask_clean"].cpu().numpy(), g, 3, 2)
+        b = ev["score"]["boundary"]
+        assert set(ev["score"]) == score_keys | {"boundary"} and set(b) == {"distance", "counts", "iou", "mean_iou"}
+        assert b["distance"] == 3 and (b["counts"] == want).all() and want[1, 1] > 0 and want[1, 2] > 0
+        np.testing.assert_allclose(b["iou"], iu.boundary_iou(want)["iou"], rtol=1e-12)
+        print(f"evaluate: boundary counts {want.tolist()}, iou {b['iou'].tolist()}")
+        acc.update(ev["score"])
+        total += want
+    # the same scene with and without: every output of today is unchanged
+    ev0 = pred.evaluate(scenes[0], truths[0], boundary_distance=3, **kw)
+    for k in ("mask", "conf", "labels", "mask_clean", "gt_labels"):
+        assert torch.equal(plain[k], ev0[k]), k
+    assert plain["count"] == ev0["count"] and plain["gt_count"] == ev0["gt_count"]
+    for k in ("gt_match", "gt_iou", "pred_match", "pred_iou", "pred_area", "gt_area", "confusion"):
+        assert plain["score"][k].tobytes() == ev0["score"][k].tobytes(), k
+    assert plain["score"]["overall"] == ev0["score"]["overall"] and plain["score"]["ap_mean"] == ev0["score"]["ap_mean"]
+    got = acc.compute()["boundary"]
+    assert (got["counts"] == total).all() and got["scenes"] == 2 and got["distance"] == 3
+    np.testing.assert_allclose(got["iou"], iu.boundary_iou(total)["iou"], rtol=1e-12)
+    one = iu.evaluate_scene(net, scenes[1], truths[1], tile=T, overlap=o, batch=4, num_classes=2, boundary_distance=3, **kw)
+    assert (one["score"]["boundary"]["counts"] == want).all()
+    assert len(pred._distance) == 1
+    pred.release()
+    assert not pred._distance
