@@ -12,24 +12,10 @@
 // image rows, whose X operand is still one contiguous run of <= 72 padded pixels): every level of the U-Net;
 // anything else keeps the per-tap kernel. Same LDS image (pixel rows, XOR-swizzled on the DMA source side,
 // ds_read_b64_tr_b16 transposing reads), same slab layout, same fold: bitwise reproducible.
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
+#include "wgrad3_common.h"
 
 #define W3_BKP 64       // pixels per K step
 #define W3_XR 72        // X rows staged per step: pixel p0 - 1 + r, r < 66 used
-
-struct Wgrad3Args {
-  const char* x; const char* dy; float* part;
-  long long ksteps;
-  int nsplit, steps_per_split;
-  int H, W, Wp;
-  int spr, rpk, lw;             // K steps per image row (W >= 64) / image rows per K step (W < 64) / log2(W) (6 if W >= 64)
-  int Cx, cx_off, Cin; int Cdy, cdy_off, Cout;
-  int mtc, ntc;
-};
 
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
@@ -44,18 +30,7 @@ __device__ __forceinline__ int w3_swz(int row) {
   else return ((row >> 1) & 3) << 1;
 }
 
-// Diagnostic build only (-DINSAR_STAMPS, tools/stamp_gemm.py)
-#ifdef INSAR_STAMPS
-__device__ unsigned long long g_wgrad3_stamps[1024 * 8];
-#define W3_STAMP(k) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); stamp_acc[k] += now_ - stamp_prev; stamp_prev = now_; } while (0)
-extern "C" int insar_debug_wgrad3_stamps(unsigned long long* out, int reset) {
-  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wgrad3_stamps), sizeof(g_wgrad3_stamps)) != hipSuccess) return -1;
-  if (reset) { static unsigned long long z[1024 * 8]; if (hipMemcpyToSymbol(HIP_SYMBOL(g_wgrad3_stamps), z, sizeof(z)) != hipSuccess) return -2; }
-  return 0;
-}
-#else
-#define W3_STAMP(k)
-#endif
+WGRAD3_STAMPS(wgrad3)
 
 template <typename T, int TM, int TN, int NW>
 struct Wgrad3Cfg {
@@ -178,10 +153,10 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 2 : 1)) void wgrad3_kernel(Wgra
   const int r16 = lane & 15, kq = lane >> 4;
 
   if (ks0 < ks1) {
-    W3_STAMP(0);        // set-up
+    WGRAD3_STAMP(0);        // set-up
     stage(0, next_pixel());
     dma_drain_and_barrier();
-    W3_STAMP(1);        // first step landed
+    WGRAD3_STAMP(1);        // first step landed
     for (int ks = ks0; ks < ks1; ++ks) {
       const int buf = (ks - ks0) & 1;
       if (ks + 1 < ks1) stage(buf ^ 1, next_pixel());
@@ -305,7 +280,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 2 : 1)) void wgrad3_kernel(Wgra
     }
   }
 
-  W3_STAMP(2);          // K loop
+  WGRAD3_STAMP(2);          // K loop
   if constexpr (MF == 32) {
     // C layout of a 32x32 accumulator: col (co) = lane & 31, row (ci) = (reg & 3) + 8*(reg >> 2) + 4*(lane >> 5)
 #pragma unroll
@@ -337,7 +312,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 2 : 1)) void wgrad3_kernel(Wgra
       }
   }
 #ifdef INSAR_STAMPS
-  W3_STAMP(3);          // slab stores
+  WGRAD3_STAMP(3);          // slab stores
   if (tid == 0) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) atomicAdd(&g_wgrad3_stamps[(blockIdx.x & 1023) * 8 + k], stamp_acc[k]);
@@ -348,17 +323,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 2 : 1)) void wgrad3_kernel(Wgra
 template <typename T, int TM, int TN, int NW, int MF = 16>
 static int launch_wgrad3(Wgrad3Args& a, hipStream_t s) {
   using Cfg = Wgrad3Cfg<T, TM, TN, NW>;
-  static std::atomic<uint64_t> attr_mask{0};     // per-device, see common.h
-  {
-    hipError_t e = insar_set_lds_once(attr_mask, (const void*)wgrad3_kernel<T, TM, TN, NW, MF>, Cfg::LDS_BYTES);
-    if (e != hipSuccess) INSAR_FAIL(-(int)e, "insar_wgrad_conv3: hipFuncSetAttribute: %s", hipGetErrorString(e));
-  }
-  a.mtc = a.Cin / TM; a.ntc = a.Cout / TN;
-  const long long grid = (long long)a.nsplit * 3 * a.mtc * a.ntc;
-  if (grid > 0x7fffffffLL) INSAR_FAIL(INSAR_E_SHAPE, "insar_wgrad_conv3: grid too large");
-  hipLaunchKernelGGL((wgrad3_kernel<T, TM, TN, NW, MF>), dim3((unsigned)grid), dim3(Cfg::THREADS), Cfg::LDS_BYTES, s, a);
-  INSAR_CHECK_LAUNCH("insar_wgrad_conv3");
-  return INSAR_OK;
+  return wgrad3_launch<wgrad3_kernel<T, TM, TN, NW, MF>>(a, TM, TN, Cfg::LDS_BYTES, Cfg::THREADS, "insar_wgrad_conv3", s);
 }
 
 // (tile(Cin) << 16) | tile(Cout) of the row-of-taps kernel for this layer, or 0 when the per-tap kernel (insar_wgrad)
@@ -380,26 +345,12 @@ extern "C" int insar_wgrad_conv3_tile(const InsarAct* x, int32_t Cout) {
 // part[split][tap][co][ci] (tap = 3*ty + tx, the layout insar_wgrad writes) for a 3x3 / stride-1 / pad-1 convolution:
 // x (B, H, W, Cin) and dy (B, H, W, Cout) on the same grid; nsplit splits of the B*H*W/64 K steps.
 extern "C" int insar_wgrad_conv3(const InsarAct* x, const InsarAct* dy, float* part, int32_t nsplit, void* stream) {
-  if (!x || !dy || !part) INSAR_FAIL(INSAR_E_ARG, "insar_wgrad_conv3: null pointer");
   int rc;
-  if ((rc = insar_check_act(x, "insar_wgrad_conv3", "x"))) return rc;
-  if ((rc = insar_check_act(dy, "insar_wgrad_conv3", "dy"))) return rc;
-  if (x->B != dy->B || x->H != dy->H || x->W != dy->W) INSAR_FAIL(INSAR_E_SHAPE, "insar_wgrad_conv3: x/dy grids differ");
-  if (x->dtype != dy->dtype) INSAR_FAIL(INSAR_E_DTYPE, "insar_wgrad_conv3: x/dy dtype differ");
+  if ((rc = wgrad3_check_operands("insar_wgrad_conv3", x, dy, part))) return rc;
   const int pair = insar_wgrad_conv3_tile(x, dy->c_len);
   if (!pair) INSAR_FAIL(INSAR_E_SHAPE, "insar_wgrad_conv3: unsupported layer (W %% 64 == 0, or W = 16 / 32 with whole K steps per image); use insar_wgrad");
-  if (nsplit < 1) INSAR_FAIL(INSAR_E_SHAPE, "insar_wgrad_conv3: nsplit");
   Wgrad3Args a;
-  a.x = (const char*)x->ptr; a.dy = (const char*)dy->ptr; a.part = part;
-  a.ksteps = (long long)x->B * x->H * x->W / W3_BKP;
-  a.nsplit = nsplit;
-  a.steps_per_split = (int)((a.ksteps + nsplit - 1) / nsplit);
-  a.H = x->H; a.W = x->W; a.Wp = x->W + 2;
-  a.spr = x->W >= W3_BKP ? x->W / W3_BKP : 1;
-  a.rpk = x->W >= W3_BKP ? 1 : W3_BKP / x->W;
-  a.lw = x->W >= W3_BKP ? 6 : (x->W == 32 ? 5 : 4);
-  a.Cx = x->C; a.cx_off = x->c_off; a.Cin = x->c_len;
-  a.Cdy = dy->C; a.cdy_off = dy->c_off; a.Cout = dy->c_len;
+  if ((rc = wgrad3_fill_args(a, "insar_wgrad_conv3", x, dy, part, nsplit, W3_BKP, 0, 0))) return rc;     // 64-bit DMA addresses: no pitch bound
   hipStream_t s = (hipStream_t)stream;
   const int tm = pair >> 16, tn = pair & 0xffff;
   if (x->dtype != INSAR_BF16) {          // fp32: 128 x 128 (8 waves) or 64 x 64, as insar_wgrad_tile_pair says

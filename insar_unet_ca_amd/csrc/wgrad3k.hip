@@ -20,28 +20,7 @@
 // is 64 wide reads both blocks of its two planes: a lane base register per (k half h, tap tx, block parity).
 // A K step lies inside one image row (W % (KS*32) == 0, checked by insar_wgrad_conv3k_tile): X row r of a step is padded
 // pixel p0 - 1 + r, dY row k is p0 + k, and tap tx of dY row k reads X row k + tx.
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-
-struct Wgrad3kArgs {
-  const char* x; const char* dy; float* part;
-  long long ksteps;             // B*H*W / PX
-  int nsplit, steps_per_split;
-  int H, W, Wp, spr;            // spr: K steps per image row
-  int Cx, cx_off, Cin; int Cdy, cdy_off, Cout;
-  int mtc, ntc;
-};
-
-__device__ __forceinline__ void wk_dma(const char* sbase, uint32_t voff, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ int wk_g(int row) { return (row >> 2) & 1; }
-template <int N> __device__ __forceinline__ void wk_wait_vm_lgkm() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory"); }
+#include "wgrad3_common.h"
 
 template <int TM, int TN>
 struct Wgrad3kCfg {
@@ -104,14 +83,14 @@ __global__ __launch_bounds__(512) void wgrad3k_kernel(Wgrad3kArgs a) {
     if (q < XP) {
       const int c = q * 64 + lane;
       const int plane = c / (XR * 4), row = (c >> 2) % XR, cc = c & 3;
-      const int blk = plane * 2 + ((cc >> 1) ^ wk_g(row));
+      const int blk = plane * 2 + ((cc >> 1) ^ wgrad3_slot<2>(row));
       const int srow = row < PX + 2 ? row : PX + 1;
       off_i[i] = (uint32_t)(srow * xpitch) + blk * 32 + (cc & 1) * 16;
       isx_i[i] = true;
     } else {
       const int c = (q - XP) * 64 + lane;
       const int plane = c / (PX * 4), row = (c >> 2) % PX, cc = c & 3;
-      const int blk = plane * 2 + ((cc >> 1) ^ wk_g(row));
+      const int blk = plane * 2 + ((cc >> 1) ^ wgrad3_slot<2>(row));
       off_i[i] = (uint32_t)(row * ypitch) + blk * 32 + (cc & 1) * 16;
       isx_i[i] = false;
     }
@@ -141,7 +120,7 @@ __global__ __launch_bounds__(512) void wgrad3k_kernel(Wgrad3kArgs a) {
   auto piece = [&](int slot, const char* sx, const char* sy, int j) {
     if (j == NPW - 1 && !full) return;
     // X pieces fill [0, X_STAGE) of the slot, dY pieces the rest: piece q lands at q * 1 KB either way
-    wk_dma(isx_i[j] ? sx : sy, off_i[j], lds0 + slot * Cfg::STAGE + j * 8192);
+    wgrad3_dma(isx_i[j] ? sx : sy, off_i[j], lds0 + slot * Cfg::STAGE + j * 8192);
   };
 
   f32x4_t acc[3][4][4];
@@ -168,9 +147,9 @@ __global__ __launch_bounds__(512) void wgrad3k_kernel(Wgrad3kArgs a) {
       const char* sx = xbase + p1 * xpitch; const char* sy = ybase + p1 * ypitch;
 #pragma unroll
       for (int j = 0; j < NPW; ++j) piece(1, sx, sy, j);
-      if (full) wk_wait_vm_lgkm<NPW>(); else wk_wait_vm_lgkm<NPW - 1>();       // step 0 landed, step 1 in flight
+      if (full) wgrad3_wait_vm_lgkm<NPW>(); else wgrad3_wait_vm_lgkm<NPW - 1>();       // step 0 landed, step 1 in flight
     } else {
-      wk_wait_vm_lgkm<0>();
+      wgrad3_wait_vm_lgkm<0>();
     }
     __builtin_amdgcn_s_barrier();
     if (grp == 1) __builtin_amdgcn_s_barrier();                       // group 1 runs one barrier behind
@@ -186,7 +165,7 @@ __global__ __launch_bounds__(512) void wgrad3k_kernel(Wgrad3kArgs a) {
 #pragma unroll
         for (int l = 0; l < NLY; ++l) {
           const int lo = NLY == 1 ? wn : l;
-          by[h][l] = ldsb + Cfg::X_STAGE + lr * 64 + ((lo ^ wk_g(lr)) << 5) + p8;
+          by[h][l] = ldsb + Cfg::X_STAGE + lr * 64 + ((lo ^ wgrad3_slot<2>(lr)) << 5) + p8;
         }
 #pragma unroll
         for (int t3 = 0; t3 < 3; ++t3) {
@@ -194,7 +173,7 @@ __global__ __launch_bounds__(512) void wgrad3k_kernel(Wgrad3kArgs a) {
 #pragma unroll
           for (int l = 0; l < NLX; ++l) {
             const int lo = NLX == 1 ? wm : l;
-            bx[h][t3][l] = ldsb + r * 64 + ((lo ^ wk_g(r)) << 5) + p8;
+            bx[h][t3][l] = ldsb + r * 64 + ((lo ^ wgrad3_slot<2>(r)) << 5) + p8;
           }
         }
       }
@@ -249,9 +228,9 @@ __global__ __launch_bounds__(512) void wgrad3k_kernel(Wgrad3kArgs a) {
         if (t3 == 2) {
           // the vector-memory wait of the step. Three slots: everything but the pieces issued during THIS step (they are
           // for the step after next) has landed; two slots: the next step's pieces were issued during this step.
-          if (NSLOT == 2 || !more) wk_wait_vm_lgkm<0>();
-          else if (full) wk_wait_vm_lgkm<NPW>();
-          else wk_wait_vm_lgkm<NPW - 1>();
+          if (NSLOT == 2 || !more) wgrad3_wait_vm_lgkm<0>();
+          else if (full) wgrad3_wait_vm_lgkm<NPW>();
+          else wgrad3_wait_vm_lgkm<NPW - 1>();
         } else {
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
@@ -303,17 +282,7 @@ __global__ __launch_bounds__(512) void wgrad3k_kernel(Wgrad3kArgs a) {
 template <int TM, int TN>
 static int launch_wgrad3k(Wgrad3kArgs& a, hipStream_t s) {
   using Cfg = Wgrad3kCfg<TM, TN>;
-  static std::atomic<uint64_t> attr_mask{0};     // per-device, see common.h
-  {
-    hipError_t e = insar_set_lds_once(attr_mask, (const void*)wgrad3k_kernel<TM, TN>, Cfg::LDS_BYTES);
-    if (e != hipSuccess) INSAR_FAIL(-(int)e, "insar_wgrad_conv3k: hipFuncSetAttribute: %s", hipGetErrorString(e));
-  }
-  a.mtc = a.Cin / TM; a.ntc = a.Cout / TN;
-  const long long grid = (long long)a.nsplit * 3 * a.mtc * a.ntc;
-  if (grid > 0x7fffffffLL) INSAR_FAIL(INSAR_E_SHAPE, "insar_wgrad_conv3k: grid too large");
-  hipLaunchKernelGGL((wgrad3k_kernel<TM, TN>), dim3((unsigned)grid), dim3(Cfg::THREADS), Cfg::LDS_BYTES, s, a);
-  INSAR_CHECK_LAUNCH("insar_wgrad_conv3k");
-  return INSAR_OK;
+  return wgrad3_launch<wgrad3k_kernel<TM, TN>>(a, TM, TN, Cfg::LDS_BYTES, Cfg::THREADS, "insar_wgrad_conv3k", s);
 }
 
 static int wgrad3k_pick(const InsarAct* x, int32_t Cout, int* tm, int* tn, int* ks) {
@@ -342,27 +311,14 @@ extern "C" int insar_wgrad_conv3k_slices(const InsarAct* x, int32_t Cout) {
 
 // part[nsplit * KS][tap][co][ci] (tap = 3*ty + tx; fold with insar_wgrad_reduce over nsplit * KS slabs)
 extern "C" int insar_wgrad_conv3k(const InsarAct* x, const InsarAct* dy, float* part, int32_t nsplit, void* stream) {
-  if (!x || !dy || !part) INSAR_FAIL(INSAR_E_ARG, "insar_wgrad_conv3k: null pointer");
   int rc;
-  if ((rc = insar_check_act(x, "insar_wgrad_conv3k", "x"))) return rc;
-  if ((rc = insar_check_act(dy, "insar_wgrad_conv3k", "dy"))) return rc;
-  if (x->B != dy->B || x->H != dy->H || x->W != dy->W) INSAR_FAIL(INSAR_E_SHAPE, "insar_wgrad_conv3k: x/dy grids differ");
-  if (x->dtype != dy->dtype) INSAR_FAIL(INSAR_E_DTYPE, "insar_wgrad_conv3k: x/dy dtype differ");
+  if ((rc = wgrad3_check_operands("insar_wgrad_conv3k", x, dy, part))) return rc;
   int tm, tn, ks;
   if (!wgrad3k_pick(x, dy->c_len, &tm, &tn, &ks))
     INSAR_FAIL(INSAR_E_SHAPE, "insar_wgrad_conv3k: unsupported layer (bf16, channel counts multiples of 64, W a multiple of the K step); use insar_wgrad_conv3");
-  if (nsplit < 1) INSAR_FAIL(INSAR_E_SHAPE, "insar_wgrad_conv3k: nsplit");
-  const int px = ks * 32;
-  if ((long long)(px + 16) * x->C * 2 >= 0x7fffffffLL || (long long)px * dy->C * 2 >= 0x7fffffffLL)
-    INSAR_FAIL(INSAR_E_SHAPE, "insar_wgrad_conv3k: channel pitch too large");
   Wgrad3kArgs a;
-  a.x = (const char*)x->ptr; a.dy = (const char*)dy->ptr; a.part = part;
-  a.ksteps = (long long)x->B * x->H * x->W / px;
-  a.nsplit = nsplit;
-  a.steps_per_split = (int)((a.ksteps + nsplit - 1) / nsplit);
-  a.H = x->H; a.W = x->W; a.Wp = x->W + 2; a.spr = x->W / px;
-  a.Cx = x->C; a.cx_off = x->c_off; a.Cin = x->c_len;
-  a.Cdy = dy->C; a.cdy_off = dy->c_off; a.Cout = dy->c_len;
+  const int px = ks * 32;       // Wgrad3kCfg::PX; X stages PX + 16 rows (XR); W % px == 0, so spr = W / px
+  if ((rc = wgrad3_fill_args(a, "insar_wgrad_conv3k", x, dy, part, nsplit, px, px + 16, px))) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (tm == 64 && tn == 64) return launch_wgrad3k<64, 64>(a, s);
   if (tm == 128 && tn == 64) return launch_wgrad3k<128, 64>(a, s);

@@ -25,60 +25,15 @@
 //        (lgkmcnt(0)) before group 1 arrived at g(12k); the first DMA into it is issued by group 0 after g(12k+2).
 // Same LDS image (pixel rows of 256 bytes, XOR-swizzled on the DMA source side, ds_read_b64_tr_b16), same products in the
 // same order per accumulator as wgrad3.hip's: the slabs are bit for bit that kernel's at the same split.
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
+#include "wgrad3_common.h"
 
 #define WX_BKP 64       // pixels per K step
 #define WX_XR 72        // X rows staged per step: padded pixel p0 - 1 + r
 #define WX_RB 256       // bytes per LDS row (128 channels)
 
-struct Wgrad3xArgs {
-  const char* x; const char* dy; float* part;
-  long long ksteps;
-  int nsplit, steps_per_split;
-  int H, W, Wp;
-  int spr, rpk, lw;             // K steps per image row (W >= 64) / image rows per K step (W < 64) / log2(W) (6 if W >= 64)
-  int Cx, cx_off, Cin; int Cdy, cdy_off, Cout;
-  int mtc, ntc;
-};
+WGRAD3_STAMPS(wgrad3x)
 
-#ifdef INSAR_STAMPS
-__device__ unsigned long long g_wgrad3x_stamps[1024 * 8];
-#define WX_STAMP(k) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); stamp_acc[k] += now_ - stamp_prev; stamp_prev = now_; } while (0)
-extern "C" int insar_debug_wgrad3x_stamps(unsigned long long* out, int reset) {
-  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wgrad3x_stamps), sizeof(g_wgrad3x_stamps)) != hipSuccess) return -1;
-  if (reset) { static unsigned long long z[1024 * 8]; if (hipMemcpyToSymbol(HIP_SYMBOL(g_wgrad3x_stamps), z, sizeof(z)) != hipSuccess) return -2; }
-  return 0;
-}
-#else
-#define WX_STAMP(k)
-#endif
-
-// LDS-DMA of one 1-KB piece: per-lane source = scalar base + 32-bit lane offset, wave-uniform LDS destination in M0
-__device__ __forceinline__ void wx_dma(const char* sbase, uint32_t voff, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-
-// LDS image of an operand tile (X: 72 pixel rows x TM channels, dY: 64 x TN), cut for ADDRESSES THAT NEED NO ARITHMETIC:
-// the wave at position w of NB (= 4 or 2) along the operand's channel dimension owns the 16-channel blocks t*NB + w,
-// t = 0..3 (its four MFMA tiles), and block t*NB + w lives in PLANE t: plane t = [rows][NB blocks x 32 bytes], the NB
-// adjacent blocks t*NB .. t*NB + NB - 1 of a pixel (one 128- or 64-byte run of the NHWC row: whole-line gathers). A tile
-// index is then a compile-time plane offset, and inside a plane row the 32-byte slot of block w is w ^ f(row) with
-// f(row) = (row / RPL) % NB, RPL = 8 / NB rows per 256-byte bank line: the eight pixel rows a 32-lane half of a
-// ds_read_b64_tr_b16 touches (r0 .. r0+3 from one 16-lane group, the other four residues mod 8 from its partner) land in
-// eight different 32-byte bank segments whatever r0 is — so the tap shift (row + tx) and the pixel half (row + 32) only
-// move r0. What depends on the lane — row base, f(row), the 8-byte column inside the block — is folded into ONE base
-// register per (k half h, tap tx) (and per pixel half where the halo rows make + 32 pixels a shift that is not a multiple
-// of 8 rows: W < 64), kept across the loop and advanced in place by one ring slot per step; every fragment read is that
-// register + an immediate. (The first build of this kernel recomputed XOR-swizzled addresses per phase, ~1.5 VALU
-// operations per MFMA in the load part: 41 % of its run time, profiles/r04_wgrad3x_ablation.txt.)
-template <int NB> __device__ __forceinline__ int wx_f(int row) { return NB == 4 ? (row >> 1) & 3 : (row >> 2) & 1; }
-
+// LDS image: the plane layout of wgrad3_common.h, NB = WM / WN blocks per plane row
 template <int TM, int TN>
 struct Wgrad3xCfg {
   static constexpr int THREADS = 512, NW = 8;
@@ -97,14 +52,12 @@ struct Wgrad3xCfg {
   static_assert(LDS_BYTES <= 160 * 1024, "three slots must fit the CU's LDS");
 };
 
-template <int N> __device__ __forceinline__ void wx_wait_vm_lgkm() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory"); }
-
 // SINV: W >= 64 — a K step lies inside one image row, + 32 pixels is + 32 staged rows for X too (an immediate).
 // VAR: 0 = the kernel. Experiment builds (-DINSAR_EXP_WX, tools/gemm_bench.py --what x3var) instantiate timing ablations of the
 // K loop, whose RESULTS ARE WRONG by construction: bit 0 = no LDS-DMA inside the loop, bit 2 = the two wave groups in
 // lockstep, bit 3 = no MFMAs, bit 4 = no fragment reads.
 template <int TM, int TN, bool SINV, int VAR = 0>
-__global__ __launch_bounds__(512) void wgrad3x_kernel(Wgrad3xArgs a) {
+__global__ __launch_bounds__(512) void wgrad3x_kernel(Wgrad3Args a) {
   using Cfg = Wgrad3xCfg<TM, TN>;
   constexpr int NXI = Cfg::NXI, NYI = Cfg::NYI, NPW = NXI + NYI;      // pieces per wave per step (waves beyond XTAIL: one less)
   constexpr int WM = Cfg::WM, WN = Cfg::WN, RBX = Cfg::RBX, RBY = Cfg::RBY;
@@ -148,7 +101,7 @@ __global__ __launch_bounds__(512) void wgrad3x_kernel(Wgrad3xArgs a) {
     constexpr int CPR = RBX / 16;
     const int c = (i * 8 + wave) * 64 + lane;
     const int plane = c / (WX_XR * CPR), row = (c / CPR) % WX_XR, cc = c % CPR;
-    const int blk = plane * WM + ((cc >> 1) ^ wx_f<WM>(row));
+    const int blk = plane * WM + ((cc >> 1) ^ wgrad3_slot<WM>(row));
     const int srow = row < xneed ? row : xneed - 1;
     xoff_i[i] = (uint32_t)(srow * xpitch) + blk * 32 + (cc & 1) * 16;
   }
@@ -157,7 +110,7 @@ __global__ __launch_bounds__(512) void wgrad3x_kernel(Wgrad3xArgs a) {
     constexpr int CPR = RBY / 16;
     const int c = (i * 8 + wave) * 64 + lane;
     const int plane = c / (WX_BKP * CPR), row = (c / CPR) % WX_BKP, cc = c % CPR;
-    const int blk = plane * WN + ((cc >> 1) ^ wx_f<WN>(row));
+    const int blk = plane * WN + ((cc >> 1) ^ wgrad3_slot<WN>(row));
     yoff_i[i] = (uint32_t)((row + 2 * (row >> a.lw)) * ypitch) + blk * 32 + (cc & 1) * 16;
   }
   // X row r of a step <-> padded pixel p0 + (ty-1)*Wp - 1 + r; dY row k <-> padded pixel p0 + k + 2*(k / W)
@@ -187,9 +140,9 @@ __global__ __launch_bounds__(512) void wgrad3x_kernel(Wgrad3xArgs a) {
   auto piece = [&](int slot, const char* sx, const char* sy, int j) {
     const uint32_t l = lds0 + slot * Cfg::STAGE;
     if (j < NXI) {
-      if (j < NXI - 1 || xtail) wx_dma(sx, xoff_i[j], l + j * 8192);
+      if (j < NXI - 1 || xtail) wgrad3_dma(sx, xoff_i[j], l + j * 8192);
     } else {
-      wx_dma(sy, yoff_i[j - NXI], l + Cfg::X_STAGE + (j - NXI) * 8192);
+      wgrad3_dma(sy, yoff_i[j - NXI], l + Cfg::X_STAGE + (j - NXI) * 8192);
     }
   };
 
@@ -205,7 +158,7 @@ __global__ __launch_bounds__(512) void wgrad3x_kernel(Wgrad3xArgs a) {
   const int r16 = lane & 15, kq = lane >> 4;
 
   if (nsteps > 0) {
-    WX_STAMP(0);        // set-up
+    WGRAD3_STAMP(0);        // set-up
     {
       const long long p0 = next_pixel();
       const char* sx = xbase + p0 * xpitch; const char* sy = ybase + p0 * ypitch;
@@ -217,12 +170,12 @@ __global__ __launch_bounds__(512) void wgrad3x_kernel(Wgrad3xArgs a) {
       const char* sx = xbase + p1 * xpitch; const char* sy = ybase + p1 * ypitch;
 #pragma unroll
       for (int j = 0; j < NPW; ++j) piece(1, sx, sy, j);
-      if (xtail) wx_wait_vm_lgkm<NPW>(); else wx_wait_vm_lgkm<NPW - 1>();      // step 0 landed, step 1 in flight
+      if (xtail) wgrad3_wait_vm_lgkm<NPW>(); else wgrad3_wait_vm_lgkm<NPW - 1>();      // step 0 landed, step 1 in flight
     } else {
-      wx_wait_vm_lgkm<0>();
+      wgrad3_wait_vm_lgkm<0>();
     }
     __builtin_amdgcn_s_barrier();
-    WX_STAMP(1);        // first step landed
+    WGRAD3_STAMP(1);        // first step landed
     if (grp == 1 && !(VAR & 4)) __builtin_amdgcn_s_barrier();          // group 1 runs one barrier behind
 
     // lane bases of the fragment reads (slot 0). A transposing read hands lane r16 of a 16-lane group channel r16 of the
@@ -238,14 +191,14 @@ __global__ __launch_bounds__(512) void wgrad3x_kernel(Wgrad3xArgs a) {
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int lr = kq * 8 + ((h ^ (kq & 1)) << 2) + (r16 >> 2);
-        by[h] = ldsb + Cfg::X_STAGE + lr * RBY + ((wn ^ wx_f<WN>(lr)) << 5) + p8;
+        by[h] = ldsb + Cfg::X_STAGE + lr * RBY + ((wn ^ wgrad3_slot<WN>(lr)) << 5) + p8;
         const int xr = lr + 2 * (lr >> a.lw);
 #pragma unroll
         for (int sx = 0; sx < NSX; ++sx)
 #pragma unroll
           for (int t3 = 0; t3 < 3; ++t3) {
             const int r = xr + sx * SS + t3;
-            bx[sx][h][t3] = ldsb + r * RBX + ((wm ^ wx_f<WM>(r)) << 5) + p8;
+            bx[sx][h][t3] = ldsb + r * RBX + ((wm ^ wgrad3_slot<WM>(r)) << 5) + p8;
           }
       }
     }
@@ -297,9 +250,9 @@ __global__ __launch_bounds__(512) void wgrad3x_kernel(Wgrad3xArgs a) {
           }
           if (ph == 5) {
             // the one vector-memory wait of the step: everything but the pieces issued during this step has landed
-            if (!more2 || (VAR & 1)) wx_wait_vm_lgkm<0>();
-            else if (xtail) wx_wait_vm_lgkm<NPW>();
-            else wx_wait_vm_lgkm<NPW - 1>();
+            if (!more2 || (VAR & 1)) wgrad3_wait_vm_lgkm<0>();
+            else if (xtail) wgrad3_wait_vm_lgkm<NPW>();
+            else wgrad3_wait_vm_lgkm<NPW - 1>();
           } else {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           }
@@ -341,7 +294,7 @@ __global__ __launch_bounds__(512) void wgrad3x_kernel(Wgrad3xArgs a) {
     if (grp == 0 && !(VAR & 4)) __builtin_amdgcn_s_barrier();          // group 0 meets group 1's last barrier
   }
 
-  WX_STAMP(2);          // K loop
+  WGRAD3_STAMP(2);          // K loop
   // C layout of a 16x16 accumulator: row (ci) = kq*4 + reg, col (co) = r16  ->  16-byte stores into [co][ci];
   // tile mt of wave wm is channel block mt*WM + wm (see the LDS image above)
 #pragma unroll
@@ -357,7 +310,7 @@ __global__ __launch_bounds__(512) void wgrad3x_kernel(Wgrad3xArgs a) {
       }
   }
 #ifdef INSAR_STAMPS
-  WX_STAMP(3);          // slab stores
+  WGRAD3_STAMP(3);          // slab stores
   stamp_acc[6] = __builtin_amdgcn_s_memtime() - stamp_t0;
   stamp_acc[7] = __builtin_amdgcn_s_memrealtime() - stamp_r0;
   if (tid == 0) {
@@ -368,22 +321,12 @@ __global__ __launch_bounds__(512) void wgrad3x_kernel(Wgrad3xArgs a) {
 }
 
 template <int TM, int TN, bool SINV, int VAR = 0>
-static int launch_wgrad3x_s(Wgrad3xArgs& a, hipStream_t s) {
+static int launch_wgrad3x_s(Wgrad3Args& a, hipStream_t s) {
   using Cfg = Wgrad3xCfg<TM, TN>;
-  static std::atomic<uint64_t> attr_mask{0};     // per-device, see common.h
-  {
-    hipError_t e = insar_set_lds_once(attr_mask, (const void*)wgrad3x_kernel<TM, TN, SINV, VAR>, Cfg::LDS_BYTES);
-    if (e != hipSuccess) INSAR_FAIL(-(int)e, "insar_wgrad_conv3x: hipFuncSetAttribute: %s", hipGetErrorString(e));
-  }
-  a.mtc = a.Cin / TM; a.ntc = a.Cout / TN;
-  const long long grid = (long long)a.nsplit * 3 * a.mtc * a.ntc;
-  if (grid > 0x7fffffffLL) INSAR_FAIL(INSAR_E_SHAPE, "insar_wgrad_conv3x: grid too large");
-  hipLaunchKernelGGL((wgrad3x_kernel<TM, TN, SINV, VAR>), dim3((unsigned)grid), dim3(Cfg::THREADS), Cfg::LDS_BYTES, s, a);
-  INSAR_CHECK_LAUNCH("insar_wgrad_conv3x");
-  return INSAR_OK;
+  return wgrad3_launch<wgrad3x_kernel<TM, TN, SINV, VAR>>(a, TM, TN, Cfg::LDS_BYTES, Cfg::THREADS, "insar_wgrad_conv3x", s);
 }
 template <int TM, int TN, int VAR = 0>
-static int launch_wgrad3x(Wgrad3xArgs& a, hipStream_t s) {
+static int launch_wgrad3x(Wgrad3Args& a, hipStream_t s) {
   return a.lw == 6 ? launch_wgrad3x_s<TM, TN, true, VAR>(a, s) : launch_wgrad3x_s<TM, TN, false, VAR>(a, s);
 }
 
@@ -401,29 +344,13 @@ extern "C" int insar_wgrad_conv3x_tile(const InsarAct* x, int32_t Cout) {
 
 // part[split][tap][co][ci] as insar_wgrad_conv3 writes it (same fold: insar_wgrad_reduce)
 extern "C" int insar_wgrad_conv3x(const InsarAct* x, const InsarAct* dy, float* part, int32_t nsplit, void* stream) {
-  if (!x || !dy || !part) INSAR_FAIL(INSAR_E_ARG, "insar_wgrad_conv3x: null pointer");
   int rc;
-  if ((rc = insar_check_act(x, "insar_wgrad_conv3x", "x"))) return rc;
-  if ((rc = insar_check_act(dy, "insar_wgrad_conv3x", "dy"))) return rc;
-  if (x->B != dy->B || x->H != dy->H || x->W != dy->W) INSAR_FAIL(INSAR_E_SHAPE, "insar_wgrad_conv3x: x/dy grids differ");
-  if (x->dtype != dy->dtype) INSAR_FAIL(INSAR_E_DTYPE, "insar_wgrad_conv3x: x/dy dtype differ");
+  if ((rc = wgrad3_check_operands("insar_wgrad_conv3x", x, dy, part))) return rc;
   const int pair = insar_wgrad_conv3x_tile(x, dy->c_len);
   if (!pair) INSAR_FAIL(INSAR_E_SHAPE, "insar_wgrad_conv3x: unsupported layer (bf16; W %% 64 == 0, or W = 16 / 32 with whole K steps per image; 256 x 128 or 128 x 256 channel tiles); use insar_wgrad_conv3");
-  if (nsplit < 1) INSAR_FAIL(INSAR_E_SHAPE, "insar_wgrad_conv3x: nsplit");
+  Wgrad3Args a;
   // 32-bit lane offsets of the DMA source: 72 pixel rows of the wider buffer
-  if ((long long)WX_XR * x->C * 2 >= 0x7fffffffLL || (long long)WX_XR * dy->C * 2 >= 0x7fffffffLL)
-    INSAR_FAIL(INSAR_E_SHAPE, "insar_wgrad_conv3x: channel pitch too large");
-  Wgrad3xArgs a;
-  a.x = (const char*)x->ptr; a.dy = (const char*)dy->ptr; a.part = part;
-  a.ksteps = (long long)x->B * x->H * x->W / WX_BKP;
-  a.nsplit = nsplit;
-  a.steps_per_split = (int)((a.ksteps + nsplit - 1) / nsplit);
-  a.H = x->H; a.W = x->W; a.Wp = x->W + 2;
-  a.spr = x->W >= WX_BKP ? x->W / WX_BKP : 1;
-  a.rpk = x->W >= WX_BKP ? 1 : WX_BKP / x->W;
-  a.lw = x->W >= WX_BKP ? 6 : (x->W == 32 ? 5 : 4);
-  a.Cx = x->C; a.cx_off = x->c_off; a.Cin = x->c_len;
-  a.Cdy = dy->C; a.cdy_off = dy->c_off; a.Cout = dy->c_len;
+  if ((rc = wgrad3_fill_args(a, "insar_wgrad_conv3x", x, dy, part, nsplit, WX_BKP, WX_XR, WX_XR))) return rc;
   hipStream_t s = (hipStream_t)stream;
 #ifdef INSAR_EXP_WX
   if ((pair >> 16) == 256) {

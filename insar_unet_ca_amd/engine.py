@@ -399,6 +399,17 @@ _TAPS3_DGRAD = [(1 - r, 1 - s) for r in range(3) for s in range(3)]
 _TAPS2 = [(a, b) for a in range(2) for b in range(2)]
 
 
+def _launch(tag, flops, fn, nbytes=0.0) -> None:
+    """Run the launch fn(): plainly, or timed by PROFILER where one is set. tag, flops and nbytes may be zero-argument
+    callables: they are evaluated under a profiler only (the unprofiled step pays for no tag, least of all for one that costs
+    ABI calls)."""
+    if PROFILER is None:
+        fn()
+        return
+    tag, flops, nbytes = (v() if callable(v) else v for v in (tag, flops, nbytes))
+    PROFILER.run(tag, flops, fn, nbytes)
+
+
 def _igemm(x: Act, y: Act, w, N: int, Ho: int, Wo: int, stride: int, taps, mode: int,
            bias: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None, oob: bool = False,
            add: Optional[Act] = None, out_stride: int = 1, out_off=(0, 0), bstat=None, gate: Optional[Act] = None) -> None:
@@ -486,19 +497,18 @@ def _conv3x3_flat(x: Act, y: Act, w: torch.Tensor, flip: int, stats: Optional[to
         fn = lambda: call("insar_conv3x3_flat_bstat", x.ref, y.ref, ptr(w), flags, ptr(stats), C.byref(bs), _lib.stream_ptr())
     else:
         fn = lambda: call("insar_conv3x3_flat", x.ref, y.ref, ptr(w), flags, ptr(stats), _lib.stream_ptr())
-    if PROFILER is not None:
-        flops = 2.0 * x.B * x.H * x.W * y.c_len * x.c_len * 9
-        tag = "conv3x3_flat_kernel<%s, %d>%s%s" % ("float" if x.code == _lib.F32 else "bf16_t",
-                                                   128 if (y.c_len % 128 == 0 and not (geo & 16)) else 64,
-                                                   (" row tiles" + (" dilated" if (geo >> 8) & 15 else "")) if geo else "", " +bstat" if bstat is not None else "")
+    def tag():
         if flags & 32:
-            tag = "conv3x3_flat2_kernel<%d, %s, %d>" % (128 if y.c_len % 128 == 0 else 64, "true" if bstat is not None else "false", (flags >> 3) & 1)
+            return "conv3x3_flat2_kernel<%d, %s, %d>" % (128 if y.c_len % 128 == 0 else 64, "true" if bstat is not None else "false", (flags >> 3) & 1)
+        return "conv3x3_flat_kernel<%s, %d>%s%s" % ("float" if x.code == _lib.F32 else "bf16_t",
+                                                    128 if (y.c_len % 128 == 0 and not (geo & 16)) else 64,
+                                                    (" row tiles" + (" dilated" if (geo >> 8) & 15 else "")) if geo else "", " +bstat" if bstat is not None else "")
+
+    def nbytes():
         # algorithmic bytes of the launch: the input and the output once, the nine weight slabs once (+ the consumer's y for +bstat)
         es = 2 if x.code == _lib.BF16 else 4
-        nbytes = float(x.B * x.H * x.W * (x.c_len + y.c_len * (2 if bstat is not None else 1)) * es + 9 * x.c_len * y.c_len * es)
-        PROFILER.run(tag, flops, fn, nbytes)
-        return
-    fn()
+        return float(x.B * x.H * x.W * (x.c_len + y.c_len * (2 if bstat is not None else 1)) * es + 9 * x.c_len * y.c_len * es)
+    _launch(tag, lambda: 2.0 * x.B * x.H * x.W * y.c_len * x.c_len * 9, fn, nbytes)
 
 
 def _conv3x3_c64(x: Act, y: Act, w: torch.Tensor, flip: int, stats: Optional[torch.Tensor], bstat=None) -> None:
@@ -507,10 +517,7 @@ def _conv3x3_c64(x: Act, y: Act, w: torch.Tensor, flip: int, stats: Optional[tor
         fn = lambda: call("insar_conv3x3_c64_bstat", x.ref, y.ref, ptr(w), flip, ptr(stats), C.byref(bs), _lib.stream_ptr())
     else:
         fn = lambda: call("insar_conv3x3_c64", x.ref, y.ref, ptr(w), flip, ptr(stats), _lib.stream_ptr())
-    if PROFILER is not None:
-        PROFILER.run("conv3x3_c64_kernel<2>" + (" +bstat" if bstat is not None else ""), 2.0 * x.B * x.H * x.W * 64 * 64 * 9, fn)
-        return
-    fn()
+    _launch(lambda: "conv3x3_c64_kernel<2>" + (" +bstat" if bstat is not None else ""), lambda: 2.0 * x.B * x.H * x.W * 64 * 64 * 9, fn)
 
 
 def _wgrad_tiles(cin: int, cout: int, code: int):
@@ -520,15 +527,12 @@ def _wgrad_tiles(cin: int, cout: int, code: int):
 
 
 def _launch_wgrad(d: InsarWgrad, M: int, cin: int, cout: int, ntaps: int, code: int) -> None:
-    if PROFILER is not None:
+    def tag():
         tm, tn = _wgrad_tiles(cin, cout, code)
-        tag = "wgrad_kernel<%s, %d, %d, %d>" % ("float" if code == _lib.F32 else "bf16_t", tm, tn,
-                                                  8 if max(tm, tn) == 256 or (code == _lib.F32 and tm == 128) else 4)
-        es = 2 if code == _lib.BF16 else 4
-        nbytes = es * M * (cin + cout) * 1.0 + 4.0 * d.nsplit * ntaps * cout * cin
-        PROFILER.run(tag, 2.0 * M * cin * cout * ntaps, lambda: call("insar_wgrad", C.byref(d), _lib.stream_ptr()), nbytes)
-        return
-    call("insar_wgrad", C.byref(d), _lib.stream_ptr())
+        return "wgrad_kernel<%s, %d, %d, %d>" % ("float" if code == _lib.F32 else "bf16_t", tm, tn,
+                                                   8 if max(tm, tn) == 256 or (code == _lib.F32 and tm == 128) else 4)
+    _launch(tag, lambda: 2.0 * M * cin * cout * ntaps, lambda: call("insar_wgrad", C.byref(d), _lib.stream_ptr()),
+            lambda: (2 if code == _lib.BF16 else 4) * M * (cin + cout) * 1.0 + 4.0 * d.nsplit * ntaps * cout * cin)
 
 
 def _side_fill(ctx: "Ctx", bf16_fill: float) -> float:
@@ -1017,71 +1021,47 @@ def _wgrad_conv3(ctx: Ctx, x: Act, dy: Act, grad: torch.Tensor) -> None:
     pairk = call("insar_wgrad_conv3k_tile", x.ref, cout) if (WGRAD_ROWS and WGRAD_K and not pairx) else 0
     if pairk and "%dx%d" % (pairk >> 16, pairk & 0xffff) not in WGRAD_K_TILES:
         pairk = 0
-    if pairk:
-        # 64 / 128 channels a side (csrc/wgrad3k.hip): one round of work-groups over the share of the chip the launch aims at;
-        # a work-group writes KS slabs (its waves split the pixels of a K step)
-        tm, tn = pairk >> 16, pairk & 0xffff
-        ks = call("insar_wgrad_conv3k_slices", x.ref, cout)
-        tiles = 3 * (cin // tm) * (cout // tn)
-        fill = _side_fill(ctx, WGRAD_FILL) if (ctx.side is not None and not (PROFILER is not None and PROFILER.alone)) else WGRAD_FILL_ALONE
-        ksteps = B * H * W // (ks * 32)
-        nsplit = max(1, min(int(256 * fill) // tiles, ksteps))
-        part = ctx.wgrad_part(nsplit * ks * 9 * cout * cin)
-        if PROFILER is not None:
-            nbytes = ctx.esize * B * H * W * (cin + cout) + 4.0 * nsplit * ks * 9 * cout * cin
-            PROFILER.run("wgrad3k_kernel<%d, %d>" % (tm, tn), 2.0 * B * H * W * cin * cout * 9,
-                         lambda: call("insar_wgrad_conv3k", x.ref, dy.ref, ptr(part), nsplit, _lib.stream_ptr()), nbytes)
-        else:
-            call("insar_wgrad_conv3k", x.ref, dy.ref, ptr(part), nsplit, _lib.stream_ptr())
-        ctx.wgrad_finish(part, grad, nsplit * ks, 9, cout, cin, 0)
-        return
-    if pairy:
-        # 128 x 128 tiles, two 4-wave work-groups per CU: the launch aims at twice the work-group count of the one-per-CU kernels
-        tiles = 3 * (cin // 128) * (cout // 128)
-        fill = _side_fill(ctx, WGRAD_FILL) if (ctx.side is not None and not (PROFILER is not None and PROFILER.alone)) else WGRAD_FILL_ALONE
-        ksteps = B * H * W // WG_BKP
-        nsplit = max(1, min(int(512 * fill) // tiles, ksteps // 4))
-        part = ctx.wgrad_part(nsplit * 9 * cout * cin)
-        if PROFILER is not None:
-            nbytes = ctx.esize * B * H * W * (cin + cout) + 4.0 * nsplit * 9 * cout * cin
-            PROFILER.run("wgrad3y_kernel<128, 128>", 2.0 * B * H * W * cin * cout * 9,
-                         lambda: call("insar_wgrad_conv3y", x.ref, dy.ref, ptr(part), nsplit, _lib.stream_ptr()), nbytes)
-        else:
-            call("insar_wgrad_conv3y", x.ref, dy.ref, ptr(part), nsplit, _lib.stream_ptr())
-        ctx.wgrad_finish(part, grad, nsplit, 9, cout, cin, 0)
-        return
-    if pair or pairx:
-        # three taps of a kernel row per work-group (csrc/wgrad3.hip): a third of the operand staging; where one side has
-        # 256 channels and the other 128, the 256 x 128 tile kernel with the six-phase K loop (csrc/wgrad3x.hip)
-        entry = "insar_wgrad_conv3x" if pairx else "insar_wgrad_conv3"
-        pair = pairx or pair
-        tm, tn = pair >> 16, pair & 0xffff
-        tiles = 3 * (cin // tm) * (cout // tn)
+    pick = pairk or pairy or pairx or pair
+    if pick:
+        tm, tn = pick >> 16, pick & 0xffff
+        tiles, ksteps, slabs = 3 * (cin // tm) * (cout // tn), B * H * W // WG_BKP, 1
         # Beside the dgrad chain (side stream) the weight gradient should fill about HALF the work-group slots: the
         # main stream's kernels keep CUs, there are half as many slabs to fold, and the launch still ends before the
         # next one is due (same-box sweep of the fill factor: 1.0 8.09-8.14, 0.7 7.86, 0.5 7.81-7.86, 0.35 7.86, 0.25
         # 9.26 ms/step). Alone on the GPU (single-stream runs, the per-kernel event pass of bench.py) it fills the chip.
-        fill = _side_fill(ctx, WGRAD_FILL if pairx else WGRAD_FILL_SMALL) if (ctx.side is not None and not (PROFILER is not None and PROFILER.alone)) else WGRAD_FILL_ALONE
-        nsplit = _wgrad_nsplit(tiles, B * H * W // WG_BKP, 9 * cout * cin, tm, tn, ctx.esize, taps_per_wg=3, fill=fill)
-        if WGRAD_GRID_CAP and fill < 1.0 and tm * tn >= 128 * 128:
-            # deep layers (48 - 192 tiles): the cost model lands on 240 - 384 one-per-CU work-groups; beside the dgrad chain a
-            # grid that leaves CUs to the main stream does better (same-box sweep, tiles/s: no cap 2 110, <= 256: 2 117,
-            # <= 200: 2 126, <= 160: 2 082, <= 128: 2 054)
-            nsplit = min(nsplit, max(1, WGRAD_GRID_CAP // tiles))
-        part = ctx.wgrad_part(nsplit * 9 * cout * cin)
-        if PROFILER is not None:
-            if pairx:
-                tag = "wgrad3x_kernel<%d, %d>" % (tm, tn)
-            else:
-                tag = "wgrad3_kernel<%s, %d, %d, %d>" % ("float" if ctx.code == _lib.F32 else "bf16_t", tm, tn,
-                                                         8 if tm == 128 and tn == 128 else 4)
-            # algorithmic bytes: both operands read once, the split-K slabs written once
-            nbytes = ctx.esize * B * H * W * (cin + cout) + 4.0 * nsplit * 9 * cout * cin
-            PROFILER.run(tag, 2.0 * B * H * W * cin * cout * 9,
-                         lambda: call(entry, x.ref, dy.ref, ptr(part), nsplit, _lib.stream_ptr()), nbytes)
+        fill = (_side_fill(ctx, WGRAD_FILL if (pairk or pairy or pairx) else WGRAD_FILL_SMALL)
+                if (ctx.side is not None and not (PROFILER is not None and PROFILER.alone)) else WGRAD_FILL_ALONE)
+        # per kernel: entry, profiler tag, slabs a work-group writes, nsplit
+        if pairk:
+            # 64 / 128 channels a side (csrc/wgrad3k.hip): one round of work-groups over the share of the chip the launch aims at;
+            # a work-group writes KS slabs (its waves split the pixels of a K step of KS * 32 pixels)
+            slabs = call("insar_wgrad_conv3k_slices", x.ref, cout)
+            entry, tag = "insar_wgrad_conv3k", lambda: "wgrad3k_kernel<%d, %d>" % (tm, tn)
+            nsplit = min(int(256 * fill) // tiles, B * H * W // (slabs * 32))
+        elif pairy:
+            # 128 x 128 tiles, two 4-wave work-groups per CU: the launch aims at twice the work-group count of the one-per-CU kernels
+            entry, tag = "insar_wgrad_conv3y", lambda: "wgrad3y_kernel<128, 128>"
+            nsplit = min(int(512 * fill) // tiles, ksteps // 4)
         else:
-            call(entry, x.ref, dy.ref, ptr(part), nsplit, _lib.stream_ptr())
-        ctx.wgrad_finish(part, grad, nsplit, 9, cout, cin, 0)
+            # three taps of a kernel row per work-group (csrc/wgrad3.hip): a third of the operand staging; where one side has
+            # 256 channels and the other 128, the 256 x 128 tile kernel with the six-phase K loop (csrc/wgrad3x.hip)
+            if pairx:
+                entry, tag = "insar_wgrad_conv3x", lambda: "wgrad3x_kernel<%d, %d>" % (tm, tn)
+            else:
+                entry, tag = "insar_wgrad_conv3", lambda: "wgrad3_kernel<%s, %d, %d, %d>" % (
+                    "float" if ctx.code == _lib.F32 else "bf16_t", tm, tn, 8 if tm == 128 and tn == 128 else 4)
+            nsplit = _wgrad_nsplit(tiles, ksteps, 9 * cout * cin, tm, tn, ctx.esize, taps_per_wg=3, fill=fill)
+            if WGRAD_GRID_CAP and fill < 1.0 and tm * tn >= 128 * 128:
+                # deep layers (48 - 192 tiles): the cost model lands on 240 - 384 one-per-CU work-groups; beside the dgrad chain a
+                # grid that leaves CUs to the main stream does better (same-box sweep, tiles/s: no cap 2 110, <= 256: 2 117,
+                # <= 200: 2 126, <= 160: 2 082, <= 128: 2 054)
+                nsplit = min(nsplit, WGRAD_GRID_CAP // tiles)
+        nsplit = max(1, nsplit)
+        part = ctx.wgrad_part(nsplit * slabs * 9 * cout * cin)
+        # algorithmic bytes: both operands read once, the split-K slabs written once
+        _launch(tag, lambda: 2.0 * B * H * W * cin * cout * 9, lambda: call(entry, x.ref, dy.ref, ptr(part), nsplit, _lib.stream_ptr()),
+                lambda: ctx.esize * B * H * W * (cin + cout) + 4.0 * nsplit * slabs * 9 * cout * cin)
+        ctx.wgrad_finish(part, grad, nsplit * slabs, 9, cout, cin, 0)
         return
     tabx = ctx.pixel_table(B, H, W, 1, H, W, W + 3)      # taps move on x: tail = first interior pixel
     tabdy = ctx.pixel_table(B, H, W, 1, H, W, 0)         # tail = zero halo pixel
