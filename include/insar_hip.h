@@ -713,6 +713,42 @@ int insar_aug_draw(uint64_t seed, uint64_t step, int32_t n, int32_t ops_mask, fl
 int insar_aug_apply(const float* x, float* xo, int32_t C, const void* m, int32_t m_dtype /*INSAR_AUG_MASK_**/, int64_t* mo,
                     int32_t n, int32_t H, int32_t W, const int32_t* table, uint64_t noise_seed, void* stream);
 
+/* ---- training from whole scenes: class-balanced crops drawn on the device (build-side addition; the reference trains from
+ * pre-cut tiles): csrc/crops.hip ----------------------------------------------------------------------------------------------
+ * labels: uint8 [H][W], H * W < 2^31. With a cell size g >= 1 (g <= H, W), Hc = H / g and Wc = W / g (floor: the ragged rows
+ * and columns at the far edges belong to no cell) and K classes, 2 <= K <= 8, the TABLE is int32 [K + 1][Hc + 1][Wc + 1].
+ * Plane p < K counts the pixels with label p; plane K counts the void pixels: label 255 and every other label >= K.
+ * Integers only, no atomics, nothing read back: every output below is bitwise defined. Every argument is checked before the
+ * device is touched (INSAR_E_ARG: null pointers, tries; INSAR_E_SHAPE: K, g, T, H, W; INSAR_E_DTYPE; INSAR_E_ALIGN). */
+/* table[p][1 + i][1 + j] = the pixels of cell (i, j) (rows i g .. i g + g - 1, columns j g .. j g + g - 1) in plane p; row 0
+ * and column 0 = 0. 1 launch. 16-byte loads where g is 1, 2, 4, 8 or 16, W % 16 == 0 and labels is 16-byte aligned, byte
+ * loads otherwise: misalignment is no error. */
+int insar_crops_cells(const uint8_t* labels, int32_t H, int32_t W, int32_t K, int32_t g, int32_t* table, void* stream);
+/* In place: table[p][a][b] <- the sum of the cells (i, j) with i < a, j < b (the exclusive 2-D prefix sums), so that the
+ * cells [a0, a1) x [b0, b1) hold table[p][a1][b1] - table[p][a0][b1] - table[p][a1][b0] + table[p][a0][b0] pixels of plane p.
+ * 2 launches (rows, columns). Exact for any Hc, Wc >= 1 with (Hc + 1) * (Wc + 1) < 2^31. */
+int insar_crops_sat(int32_t* table, int32_t K, int32_t Hc, int32_t Wc, void* stream);
+/* Draw n tile origins from the summed table `sat` of a scene: T x T tiles, T % g == 0, T <= H, W; 1 <= tries <= 64;
+ * cum: HOST array of K floats, the cumulative class probabilities (read before the launch); origins int32 [n][2] = (y0, x0);
+ * info int32 [n][4] = {target class, accepted try or -1, pixels of that class in the chosen tile, void pixels in it}.
+ * One wave per sample, lane t evaluates try t. With h(i) = aug_hash64(key, i) (below) sample s uses counter base b = s * 65.
+ *   Target class: u = float32(h(b) >> 40) * 2^-24; the target is the first c with u < cum[c]; the last class is the default.
+ *   Origin of try t: with r = h(b + 1 + t), ny = Hc - T/g + 1 and nx = Wc - T/g + 1:
+ *     cy = ((r >> 32) * ny) >> 32, cx = ((r & 0xffffffff) * nx) >> 32, origin = (cy * g, cx * g).
+ *   Acceptance: a try is accepted if its tile holds >= min_count pixels of the target class and <= max_void void pixels. The
+ *     lowest accepted t wins (a ballot).
+ *   Fallback when no try is accepted: the try with the most target-class pixels among those within the void cap; if no try is
+ *     within the void cap, the try with the fewest void pixels. Ties go to the lowest t. The accepted-try field of info is -1.
+ * 1 launch. */
+int insar_crops_draw(uint64_t key, int32_t n, int32_t K, int32_t tries, const float* cum, int32_t min_count, int32_t max_void,
+                     int32_t T, int32_t g, int32_t H, int32_t W, const int32_t* sat, int32_t* origins, int32_t* info, void* stream);
+/* images float32 [n][1][T][T] <- the tiles of `scene` (uint8 or float32 [H][W], INSAR_SCENE_*) at `origins`, normalised as
+ * insar_scene_gather does and bitwise equal to its result; masks [n][T][T], int64 or uint8 (INSAR_AUG_MASK_I64 / _U8) <- the
+ * tiles of `labels` at the same origins, labels copied unchanged. Either output may be null (then its source may be too), not
+ * both. T % 4 == 0, T <= H, W. A tile whose origin leaves the scene is zero-filled, its labels are 255. 1 launch. */
+int insar_crops_gather(const void* scene, int32_t scene_dtype, const uint8_t* labels, int32_t H, int32_t W, const int32_t* origins,
+                       int32_t n, int32_t T, float* images, void* masks, int32_t mask_dtype, void* stream);
+
 /* ---- optimizer: optim.Adam(lr=1e-4) (:466,346), multi-tensor ------------------------------------
  * table: int64[ntensors][5] = {param*, grad*, exp_avg*, exp_avg_sq*, numel}; chunks: int32[nchunks][2]
  * = {tensor index, chunk index}; each chunk covers `chunk_elems` elements. */

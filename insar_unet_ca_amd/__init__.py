@@ -15,6 +15,7 @@ from .regions import label_regions  # noqa: F401
 from .score import DetectionScore, match_from_overlaps, match_regions, region_overlaps  # noqa: F401
 from .augment import Augment  # noqa: F401
 from .distance import DistanceScratch, boundary_counts, boundary_iou, distance_transform, expand_labels, void_band  # noqa: F401
+from .crops import CropIndex, SceneCrops, draw_crops, gather_crops  # noqa: F401
 
 __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "ChannelAttentionModule", "MaxPool2d", "CrossEntropyLoss", "DiceLoss", "DiceCELoss", "Adam", "GraphedTrainStep",
            "compute_metrics", "train_model", "validate_model", "save_history", "VOCSegDataset", "SyntheticTiles",
@@ -24,4 +25,5 @@ __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "Cha
            "FocalLoss", "class_weights", "label_histogram", "label_regions", "detect_scene", "Augment",
            "AdamW", "LRSchedule", "split_decay_groups",
            "region_overlaps", "match_regions", "match_from_overlaps", "DetectionScore", "evaluate_scene",
-           "DistanceScratch", "distance_transform", "void_band", "expand_labels", "boundary_counts", "boundary_iou"]
+           "DistanceScratch", "distance_transform", "void_band", "expand_labels", "boundary_counts", "boundary_iou",
+           "CropIndex", "SceneCrops", "draw_crops", "gather_crops"]

@@ -227,6 +227,10 @@ _SIGNATURES = {
     "insar_dist_boundary_counts": [_P, _P, _P, _P, _I, _I, _L, _I, _I, _P, _P],
     "insar_aug_draw": [C.c_uint64, C.c_uint64, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P],
     "insar_aug_apply": [_P, _P, _I, _P, _I, _P, _I, _I, _I, _P, C.c_uint64, _P],
+    "insar_crops_cells": [_P, _I, _I, _I, _I, _P, _P],
+    "insar_crops_sat": [_P, _I, _I, _I, _P],
+    "insar_crops_draw": [C.c_uint64, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "insar_crops_gather": [_P, _I, _P, _I, _I, _P, _I, _I, _P, _P, _I, _P],
     "insar_adam_step": [_P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P],
     "insar_scale_f32": [_P, _L, _F, _P],
     "insar_mul_dev_f32": [_P, _P, _L, _P, _P],
