@@ -1,7 +1,8 @@
 // Training-time augmentation and test-time augmentation (TTA): the eight flips / rotations of the square (the dihedral
 // group D4) applied to images and their masks together, a per-sample gain / bias and additive noise on the images.
-// insar_aug_draw fills a per-sample parameter table on the device from a counter-based hash; insar_aug_apply carries it
-// out. Both are pure functions of their arguments: no state, no atomics, bitwise reproducible.
+// insar_aug_draw fills a per-sample parameter table on the device from a counter-based hash (insar_hash64 of scene_common.h,
+// the aug_hash64 of include/insar_hip.h); insar_aug_apply carries it out. Both are pure functions of their arguments: no
+// state, no atomics, bitwise reproducible.
 //
 // apply is an HBM-bound permutation. A work-group owns one 64 x 64 tile of one OUTPUT plane (an image channel or a mask)
 // of one sample, so the op is uniform per work-group and no branch on it diverges.
@@ -15,7 +16,7 @@
 //     ds_write_b32 / ds_read_b32, which do not conflict. int64 masks use two such planes (low and high dword), so the
 //     bank picture is the same for every element type.
 #include <math.h>
-#include "common.h"
+#include "scene_common.h"
 
 // the contract of this file is bitwise (tests/augment_ref.py restates it rounding for rounding)
 #pragma clang fp contract(off)
@@ -26,14 +27,6 @@
 #define AUG_PLANE (AUG_TILE * AUG_LDS_STRIDE)
 #define AUG_MAX_SIDE 32768
 #define AUG_ZS 0x1.bb67aep-16f          // float32(1 / sqrt((65536^2 - 1) / 3)): the sum of four uniform 16-bit fields has this deviation
-
-// splitmix64's finalizer over key + golden * (i + 1) (dl_hash of deeplab.hip, restated: that one is local to its file)
-__host__ __device__ __forceinline__ uint64_t aug_hash64(uint64_t key, uint64_t i) {
-  uint64_t z = key + 0x9E3779B97F4A7C15ull * (i + 1ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 // ---------------------------------------------------------------------------------------------
 // draw: one thread per sample, row s of the table = {op, gain, bias, sigma}
@@ -47,7 +40,7 @@ aug_draw_kernel(uint64_t key, int n, int ops_mask, float gain_lo, float gain_d, 
   if (s >= n) return;
   uint32_t h[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) h[j] = (uint32_t)(aug_hash64(key, 4ull * (uint64_t)s + j) >> 32);
+  for (int j = 0; j < 4; ++j) h[j] = (uint32_t)(insar_hash64(key, 4ull * (uint64_t)s + j) >> 32);
   int k = (int)(h[0] % (uint32_t)__popc((unsigned)ops_mask));
   int op = 0;
   for (int b = 0; b < 8; ++b) {
@@ -98,8 +91,6 @@ struct AugArgs {
   int xvec, mvec;          // 16-byte path allowed for the images / the masks
 };
 
-struct __attribute__((aligned(16))) aug_i64x2 { int64_t a, b; };
-
 // t = gain * v; t = t + bias; t = t + sigma * z(lin): three separate roundings
 struct AugPhoto {
   float gain, bias, sigma;
@@ -109,7 +100,7 @@ struct AugPhoto {
     float t = gain * v;
     t = t + bias;
     if (noisy) {
-      const uint64_t h = aug_hash64(seed, lin);
+      const uint64_t h = insar_hash64(seed, lin);
       const int S = (int)(h & 0xffffu) + (int)((h >> 16) & 0xffffu) + (int)((h >> 32) & 0xffffu) + (int)(h >> 48);
       const float z = (float)(S - 131070) * AUG_ZS;
       const float nz = sigma * z;
@@ -133,8 +124,8 @@ template <> struct AugMask<INSAR_AUG_MASK_I64> {
   typedef int64_t T;
   __device__ __forceinline__ static int64_t widen(int64_t v) { return v; }
   __device__ __forceinline__ static void quad(const int64_t* p, int64_t* v) {
-    const aug_i64x2 lo = *reinterpret_cast<const aug_i64x2*>(p);
-    const aug_i64x2 hi = *reinterpret_cast<const aug_i64x2*>(p + 2);
+    const insar_i64x2 lo = *reinterpret_cast<const insar_i64x2*>(p);
+    const insar_i64x2 hi = *reinterpret_cast<const insar_i64x2*>(p + 2);
     v[0] = lo.a; v[1] = lo.b; v[2] = hi.a; v[3] = hi.b;
   }
 };
@@ -251,11 +242,7 @@ __global__ void __launch_bounds__(AUG_THREADS) aug_apply_kernel(AugArgs a) {
             int64_t q[4];
             AugMask<MD>::quad(src + (int64_t)si * W + sj, q);
             if (fh) { const int64_t t0 = q[0], t1 = q[1]; q[0] = q[3]; q[1] = q[2]; q[2] = t1; q[3] = t0; }
-            aug_i64x2* o = reinterpret_cast<aug_i64x2*>(dst + (int64_t)i * W + j);
-            aug_i64x2 lo, hi;
-            lo.a = q[0]; lo.b = q[1]; hi.a = q[2]; hi.b = q[3];
-            o[0] = lo;
-            o[1] = hi;
+            quad_store_i64(dst + (int64_t)i * W + j, q);
           }
         }
       } else {

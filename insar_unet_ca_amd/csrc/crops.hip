@@ -7,23 +7,15 @@
 // All arithmetic that decides anything is integer, nothing is read back, there are no atomics: every output is bitwise
 // defined (tests/crops_ref.py restates it). Plane p < K counts label p; plane K counts the void pixels: label 255 and
 // every other label >= K.
-#include "common.h"
+#include "scene_common.h"
 
-// the image path of gather is insar_scene_gather's arithmetic rounding for rounding
+// nothing below is meant to fuse (the image path of gather, image_quad of scene_common.h, turns contraction off by itself)
 #pragma clang fp contract(off)
 
 #define CR_THREADS 256
 #define CR_MAX_K 8
 #define CR_MAX_TRIES 64
 #define CR_SCAN_WAVES 16
-
-// aug_hash64 of augment.hip, restated (that one is local to its file; include/insar_hip.h gives the definition)
-__host__ __device__ __forceinline__ uint64_t crops_hash64(uint64_t key, uint64_t i) {
-  uint64_t z = key + 0x9E3779B97F4A7C15ull * (i + 1ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 // ---------------------------------------------------------------------------------------------
 // cells
@@ -176,13 +168,7 @@ __global__ void __launch_bounds__(CR_THREADS) crops_scan_rows_kernel(int32_t* __
     int32_t carry = 0;
     for (int64_t c0 = 0; c0 < pitch; c0 += 64) {
       const int64_t c = c0 + lane;
-      int32_t v = c < pitch ? p[c] : 0;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int32_t u = __shfl_up(v, o, 64);
-        if (lane >= o) v += u;
-      }
-      v += carry;
+      const int32_t v = wave_incl_scan(c < pitch ? p[c] : 0, lane) + carry;
       if (c < pitch) p[c] = v;
       carry = __shfl(v, 63, 64);
     }
@@ -233,18 +219,10 @@ extern "C" int insar_crops_sat(int32_t* table, int32_t K, int32_t Hc, int32_t Wc
 }
 
 // ---------------------------------------------------------------------------------------------
-// draw: one wave per sample, lane t evaluates try t. The rule is stated in include/insar_hip.h.
+// draw: one wave per sample, lane t evaluates try t. The rule is stated in include/insar_hip.h; its aug_hash64 is insar_hash64
+// of scene_common.h.
 // ---------------------------------------------------------------------------------------------
 struct CropCum { float c[CR_MAX_K]; };
-
-__device__ __forceinline__ unsigned long long crops_wave_max(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long u = __shfl_xor(v, o, 64);
-    v = u > v ? u : v;
-  }
-  return v;
-}
 
 __global__ void __launch_bounds__(CR_THREADS)
 crops_draw_kernel(uint64_t key, int n, int K, int tries, CropCum cum, int min_count, int max_void, int tg, int g, int Hc, int Wc,
@@ -253,13 +231,13 @@ crops_draw_kernel(uint64_t key, int n, int K, int tries, CropCum cum, int min_co
   const int s = blockIdx.x * (CR_THREADS / 64) + (threadIdx.x >> 6);
   if (s >= n) return;                                                // wave-uniform
   const uint64_t b = (uint64_t)s * 65ull;
-  const float u = (float)(crops_hash64(key, b) >> 40) * 0x1p-24f;
+  const float u = (float)(insar_hash64(key, b) >> 40) * 0x1p-24f;
   int cls = K - 1;
 #pragma unroll
   for (int c = CR_MAX_K - 2; c >= 0; --c)
     if (c < K - 1 && u < cum.c[c]) cls = c;                          // descending: the first such c stays
   const bool act = lane < tries;
-  const uint64_t r = crops_hash64(key, b + 1ull + (uint64_t)lane);
+  const uint64_t r = insar_hash64(key, b + 1ull + (uint64_t)lane);
   const uint64_t ny = (uint64_t)(Hc - tg + 1), nx = (uint64_t)(Wc - tg + 1);
   const int cy = (int)(((r >> 32) * ny) >> 32), cx = (int)(((r & 0xffffffffull) * nx) >> 32);
   const int64_t pitch = (int64_t)Wc + 1, plane = ((int64_t)Hc + 1) * pitch;
@@ -280,9 +258,9 @@ crops_draw_kernel(uint64_t key, int n, int K, int tries, CropCum cum, int min_co
   } else {
     // most target pixels among the tries within the void cap, else fewest void pixels; 63 - lane in the low byte: ties to
     // the lowest try. Lane 0 is always a try, so the second key is never all zero.
-    unsigned long long best = crops_wave_max(capped ? (((unsigned long long)cnt + 1ull) << 8) | (unsigned)(63 - lane) : 0ull);
+    unsigned long long best = wave_max(capped ? (((unsigned long long)cnt + 1ull) << 8) | (unsigned)(63 - lane) : 0ull);
     if (best == 0ull)
-      best = crops_wave_max(act ? ((0x80000000ull - (unsigned long long)vd) << 8) | (unsigned)(63 - lane) : 0ull);
+      best = wave_max(act ? ((0x80000000ull - (unsigned long long)vd) << 8) | (unsigned)(63 - lane) : 0ull);
     win = 63 - (int)(best & 0xffull);
     acc = -1;
   }
@@ -319,37 +297,10 @@ extern "C" int insar_crops_draw(uint64_t key, int32_t n, int32_t K, int32_t trie
 // ---------------------------------------------------------------------------------------------
 // gather: one launch for the image tiles and the label tiles of a batch. One thread per four adjacent output pixels
 // (T % 4 == 0: a quad never leaves its tile row); the first n * T * T / 4 work items are image quads, the rest label quads,
-// so a wave is of one kind except at the one boundary. The image arithmetic is SceneLoad's of scene.hip, restated. A tile whose
-// origin leaves the scene (no table insar_crops_draw writes holds one) is zero-filled, its labels are 255.
+// so a wave is of one kind except at the one boundary. The image arithmetic is image_quad of scene_common.h, the one that
+// insar_scene_gather runs. A tile whose origin leaves the scene (no table insar_crops_draw writes holds one) is zero-filled,
+// its labels are 255.
 // ---------------------------------------------------------------------------------------------
-struct __attribute__((aligned(16))) crops_i64x2 { int64_t a, b; };
-
-__device__ __forceinline__ uint32_t crops_load4(const uint8_t* p) {
-  if ((((uintptr_t)p) & 3u) == 0) return *reinterpret_cast<const uint32_t*>(p);
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-
-template <typename S>
-__device__ __forceinline__ void crops_image_quad(const S* p, float* f);
-template <>
-__device__ __forceinline__ void crops_image_quad<uint8_t>(const uint8_t* p, float* f) {
-  const uint32_t u = crops_load4(p);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float x = (float)((u >> (8 * j)) & 0xffu) / 255.0f;
-    f[j] = (x - 0.5f) / 0.5f;
-  }
-}
-template <>
-__device__ __forceinline__ void crops_image_quad<float>(const float* p, float* f) {
-  if ((((uintptr_t)p) & 15u) == 0) {
-    const float4 v = *reinterpret_cast<const float4*>(p);
-    f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-  } else {
-    f[0] = p[0]; f[1] = p[1]; f[2] = p[2]; f[3] = p[3];
-  }
-}
-
 template <typename S, int MD>
 __global__ void __launch_bounds__(CR_THREADS)
 crops_gather_kernel(const S* __restrict__ scene, const uint8_t* __restrict__ labels, int H, int W, const int32_t* __restrict__ origins,
@@ -370,18 +321,14 @@ crops_gather_kernel(const S* __restrict__ scene, const uint8_t* __restrict__ lab
     const int64_t at = (int64_t)(y0 + ty) * W + x0 + tx;
     if (is_img) {
       float f[4] = {0.f, 0.f, 0.f, 0.f};
-      if (inside) crops_image_quad<S>(scene + at, f);
+      if (inside) image_quad<S>(scene + at, f);
       *reinterpret_cast<float4*>(images + (q << 2)) = make_float4(f[0], f[1], f[2], f[3]);
     } else if constexpr (MD != INSAR_AUG_MASK_NONE) {
-      const uint32_t u = inside ? crops_load4(labels + at) : 0xffffffffu;
+      const uint32_t u = inside ? load4_u8_any(labels + at) : 0xffffffffu;
       if constexpr (MD == INSAR_AUG_MASK_U8) {
         *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(masks) + (q << 2)) = u;
       } else {
-        crops_i64x2* o = reinterpret_cast<crops_i64x2*>(reinterpret_cast<int64_t*>(masks) + (q << 2));
-        crops_i64x2 lo, hi;
-        lo.a = u & 0xffu; lo.b = (u >> 8) & 0xffu; hi.a = (u >> 16) & 0xffu; hi.b = u >> 24;
-        o[0] = lo;
-        o[1] = hi;
+        labels4_store_i64(reinterpret_cast<int64_t*>(masks) + (q << 2), u);
       }
     }
   }

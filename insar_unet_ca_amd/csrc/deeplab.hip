@@ -10,7 +10,7 @@
 // Every 1x1 / 3x3 / strided / dilated convolution of the backbone and head runs on the implicit-GEMM kernels
 // (igemm.hip with INSAR_IGEMM_OOB_ZERO, wgrad.hip with per-tap pixel tables built here).
 // All kernels are HBM- or latency-bound helpers: 16-byte accesses, one block per image row, deterministic sums.
-#include "common.h"
+#include "scene_common.h"
 
 #define DL_THREADS 256
 
@@ -568,10 +568,7 @@ static int broadcast_hw_impl(const InsarAct* src, const InsarAct* dst, const Ins
 // Philox stream cannot be reproduced, so the oracle is given this mask.
 // ---------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t dl_hash(uint64_t seed, uint64_t i) {
-  uint64_t z = seed + 0x9E3779B97F4A7C15ull * (i + 1);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return (uint32_t)((z ^ (z >> 31)) >> 32);
+  return (uint32_t)(insar_hash64(seed, i) >> 32);
 }
 
 template <typename T>

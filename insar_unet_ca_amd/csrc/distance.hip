@@ -23,7 +23,7 @@
 // P_c = {pred == c, d2_pred <= r2} and G_c = {gt == c, d2_gt <= r2}. Per thread 3 K int32 counters in registers, summed over
 // the wave with shuffles, over the work-group in LDS, then 3 K agent-scope int64 atomic adds per work-group (the pattern of
 // overlap.hip): integer sums, independent of the launch geometry.
-#include "common.h"
+#include "scene_common.h"
 #include <limits.h>
 
 #define DT_THREADS 256
@@ -142,27 +142,6 @@ dist_rows_kernel(const int16_t* __restrict__ sy, int H, int W, int R, int64_t np
 }
 
 // ---- boundary-band counts -----------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void dt_load4(const int* p, int64_t i, int64_t n, bool vec, int* v) {
-  if (vec) {
-    const int4 q = *reinterpret_cast<const int4*>(p + i);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = (i + j < n) ? p[i + j] : INSAR_DIST_FAR;
-  }
-}
-// pixels past the end read as `fill`
-__device__ __forceinline__ void dt_load4_u8(const uint8_t* p, int64_t i, int64_t n, bool vec, int fill, int* v) {
-  if (vec) {
-    const uint32_t u = *reinterpret_cast<const uint32_t*>(p + i);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = (int)((u >> (8 * j)) & 0xffu);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = (i + j < n) ? (int)p[i + j] : fill;
-  }
-}
-
 __global__ void __launch_bounds__(DT_THREADS)
 dist_counts_clear_kernel(long long* __restrict__ counts, int n) {
   if ((int)threadIdx.x < n) counts[threadIdx.x] = 0;
@@ -178,10 +157,10 @@ dist_counts_kernel(const uint8_t* __restrict__ pred, const uint8_t* __restrict__
   const int64_t nquads = (npix + 3) >> 2;
   for (int64_t q = blockIdx.x * (int64_t)DT_THREADS + threadIdx.x; q < nquads; q += (int64_t)gridDim.x * DT_THREADS) {
     int p[4], g[4], dp[4], dg[4];
-    dt_load4_u8(pred, q << 2, npix, vec, 0, p);
-    dt_load4_u8(gt, q << 2, npix, vec, void_value, g);              // past the end: void, dropped
-    dt_load4(d2p, q << 2, npix, vec, dp);
-    dt_load4(d2g, q << 2, npix, vec, dg);
+    quad_load_u8(pred, q << 2, npix, vec, 0, p);
+    quad_load_u8(gt, q << 2, npix, vec, void_value, g);              // past the end: void, dropped
+    quad_load(d2p, q << 2, npix, vec, INSAR_DIST_FAR, dp);
+    quad_load(d2g, q << 2, npix, vec, INSAR_DIST_FAR, dg);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (g[j] == void_value) continue;
@@ -198,7 +177,7 @@ dist_counts_kernel(const uint8_t* __restrict__ pred, const uint8_t* __restrict__
   const int lane = (int)__lane_id(), wave = threadIdx.x / INSAR_WAVE;
 #pragma unroll
   for (int i = 0; i < 3 * DT_MAX_K; ++i) {
-    int v = cnt[i];
+    int v = cnt[i];          // written out: through a shared wave_sum(int) the compiler allocates 60 VGPRs here instead of 52
 #pragma unroll
     for (int o = INSAR_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, INSAR_WAVE);
     if (lane == 0) part[wave][i] = v;

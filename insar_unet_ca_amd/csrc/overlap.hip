@@ -18,7 +18,7 @@
 // key, the lanes of a wave reduce over runs of equal keys with shuffles, only the first lane of a run probes and adds.
 // Reproducibility: which slot a key lands in depends on arrival order, the counts (integer sums) do not; the host sorts the
 // records by (gt, pred).
-#include "common.h"
+#include "scene_common.h"
 
 #define OV_THREADS 256
 #define OV_MAX_PAIRS ((int64_t)1 << 24)
@@ -28,15 +28,6 @@ struct OvHeader { long long overflow, reserved; };          // of the table; the
 static_assert(sizeof(OvSlot) == 16 && sizeof(OvHeader) == 16, "16-byte header, 16-byte slots");
 static_assert(sizeof(InsarOverlap) == 16, "InsarOverlap is one 16-byte store");
 
-__device__ __forceinline__ void ov_load4(const int* p, int64_t i, int64_t n, bool vec, int* v) {
-  if (vec) {
-    const int4 q = *reinterpret_cast<const int4*>(p + i);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = (i + j < n) ? p[i + j] : 0;
-  }
-}
 // 1 where the pixel is dropped; pixels past the end are dropped too
 __device__ __forceinline__ void ov_void4(const uint8_t* p, int void_value, int64_t i, int64_t n, bool vec, bool* drop) {
   if (vec) {
@@ -49,38 +40,11 @@ __device__ __forceinline__ void ov_void4(const uint8_t* p, int void_value, int64
   }
 }
 
-// ---- runs of equal 64-bit keys over the lanes of a wave; the sum of a run collected at its first lane -------------------
-struct OvRuns { int lane, id; bool head; };
-__device__ __forceinline__ OvRuns ov_runs(unsigned long long key) {
-  OvRuns r;
-  r.lane = (int)__lane_id();
-  const unsigned long long prev = __shfl_up(key, 1, INSAR_WAVE);
-  r.head = r.lane == 0 || prev != key;
-  const unsigned long long heads = __ballot(r.head);
-  r.id = __popcll(heads & ((2ull << r.lane) - 1ull));          // lane 63: 2 << 63 wraps to 0, the mask is all ones
-  return r;
-}
-__device__ __forceinline__ int ov_run_sum(const OvRuns& r, int v) {
-#pragma unroll
-  for (int d = 1; d < INSAR_WAVE; d <<= 1) {
-    const int o = __shfl_down(v, d, INSAR_WAVE);
-    const int oid = __shfl_down(r.id, d, INSAR_WAVE);
-    if (r.lane + d < INSAR_WAVE && oid == r.id) v += o;
-  }
-  return v;
-}
-
-__device__ __forceinline__ unsigned long long ov_hash(unsigned long long z) {          // the finaliser of splitmix64
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 // add n under `key` (!= 0): at most `mask + 1` probe steps, every access to the table an agent-scope atomic. Slots are never
 // freed, so the overflow word is only ever raised on a table with no empty slot left: a probe that sees it raised gives up (every
 // 64th step looks), which keeps the calls that are going to be refused anyway short.
 __device__ __forceinline__ void ov_insert(OvHeader* hdr, OvSlot* slots, unsigned int mask, unsigned long long key, int n) {
-  unsigned int s = (unsigned int)ov_hash(key) & mask;
+  unsigned int s = (unsigned int)insar_mix64(key) & mask;
   for (unsigned int step = 0; step <= mask; ++step) {
     unsigned long long cur = __hip_atomic_load(&slots[s].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (cur == 0ull)           // on failure `cur` receives the key that another thread has put there since
@@ -113,8 +77,8 @@ overlap_count_kernel(const int* __restrict__ pred, const int* __restrict__ gt, c
     if (q < nquads) {
       int p[4], g[4];
       bool drop[4];
-      ov_load4(pred, q << 2, npix, vec, p);
-      ov_load4(gt, q << 2, npix, vec, g);
+      quad_load(pred, q << 2, npix, vec, 0, p);
+      quad_load(gt, q << 2, npix, vec, 0, g);
       ov_void4(voidmap, void_value, q << 2, npix, vec, drop);
 #pragma unroll
       for (int j = 0; j < 4; ++j)
@@ -129,8 +93,8 @@ overlap_count_kernel(const int* __restrict__ pred, const int* __restrict__ gt, c
     for (int j = 0; j < 4; ++j) {
       const unsigned long long key = cnt[j] > 0 ? k[j] : 0ull;
       if (__ballot(key != 0ull) == 0) continue;
-      const OvRuns runs = ov_runs(key);
-      const int total = ov_run_sum(runs, cnt[j]);
+      const WaveRuns runs = wave_runs(key);
+      const int total = wave_run_reduce(runs, cnt[j], WaveAdd());
       if (runs.head && key != 0ull) ov_insert(hdr, slots, mask, key, total);
     }
   }

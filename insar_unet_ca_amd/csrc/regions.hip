@@ -18,7 +18,7 @@
 // agent-scope atomic (relaxed load / fetch_min); everywhere else a kernel boundary lies between writer and reader.
 // Reproducibility: integers only (int64 sums, min / max boxes, confidence as sum of llrint(clamp(conf, 0, 1) * 2^30));
 // integer addition commutes, so the atomics' arrival order changes nothing.
-#include "common.h"
+#include "scene_common.h"
 #include <limits.h>
 
 #define RG_THREADS 256
@@ -30,70 +30,6 @@
 
 static_assert(sizeof(InsarRegion) == 64, "InsarRegion is four 16-byte stores");
 static_assert(RG_TW == INSAR_WAVE && RG_THREADS % INSAR_WAVE == 0, "one tile row per wave in the run pass of `tiles`");
-
-// ---- four consecutive elements per thread: one 16-byte (4-byte for uint8) access where `vec`, guarded scalars otherwise ----
-__device__ __forceinline__ void rg_load4(const int* p, int64_t i, int64_t n, bool vec, int fill, int* v) {
-  if (vec) {
-    const int4 q = *reinterpret_cast<const int4*>(p + i);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = (i + j < n) ? p[i + j] : fill;
-  }
-}
-__device__ __forceinline__ void rg_store4(int* p, int64_t i, int64_t n, bool vec, const int* v) {
-  if (vec) {
-    *reinterpret_cast<int4*>(p + i) = make_int4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (i + j < n) p[i + j] = v[j];
-  }
-}
-__device__ __forceinline__ void rg_load4_u8(const uint8_t* p, int64_t i, int64_t n, bool vec, int* v) {
-  if (vec) {
-    const uint32_t u = *reinterpret_cast<const uint32_t*>(p + i);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = (int)((u >> (8 * j)) & 0xffu);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = (i + j < n) ? (int)p[i + j] : 0;
-  }
-}
-__device__ __forceinline__ void rg_load4_f32(const float* p, int64_t i, int64_t n, bool vec, float* v) {
-  if (vec) {
-    const float4 q = *reinterpret_cast<const float4*>(p + i);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = (i + j < n) ? p[i + j] : 0.f;
-  }
-}
-
-// ---- runs of equal keys over the lanes of a wave; sums / minima / maxima of a run collected at its first lane ----------
-struct RgRuns { int lane, id; bool head; };
-__device__ __forceinline__ RgRuns rg_runs(int key) {
-  RgRuns r;
-  r.lane = (int)__lane_id();
-  const int prev = __shfl_up(key, 1, INSAR_WAVE);
-  r.head = r.lane == 0 || prev != key;
-  const unsigned long long heads = __ballot(r.head);
-  r.id = __popcll(heads & ((2ull << r.lane) - 1ull));          // lane 63: 2 << 63 wraps to 0, the mask is all ones
-  return r;
-}
-template <typename T, typename Op>
-__device__ __forceinline__ T rg_run_reduce(const RgRuns& r, T v, Op op) {
-#pragma unroll
-  for (int d = 1; d < INSAR_WAVE; d <<= 1) {
-    const T o = __shfl_down(v, d, INSAR_WAVE);
-    const int oid = __shfl_down(r.id, d, INSAR_WAVE);
-    if (r.lane + d < INSAR_WAVE && oid == r.id) v = op(v, o);
-  }
-  return v;
-}
-struct RgAdd { template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; } };
-struct RgMin { __device__ __forceinline__ int operator()(int a, int b) const { return a < b ? a : b; } };
-struct RgMax { __device__ __forceinline__ int operator()(int a, int b) const { return a > b ? a : b; } };
 
 // ---------------------------------------------------------------------------------------------
 // tiles: union-find in LDS. lab[i] <= i always; a union links the larger root to the smaller with atomicMin and, where
@@ -133,10 +69,10 @@ regions_tile_kernel(const uint8_t* __restrict__ mask, const float* __restrict__ 
     if (gy < H && gx < W) {
       const int64_t g = (int64_t)gy * W + gx;
       const int64_t row_end = (int64_t)(gy + 1) * W;            // the scalar path must not run into the next row
-      rg_load4_u8(mask, g, vec ? npix : row_end, vec, c);
+      quad_load_u8(mask, g, vec ? npix : row_end, vec, 0, c);
       if (conf) {
         float f[4];
-        rg_load4_f32(conf, g, vec ? npix : row_end, vec, f);
+        quad_load(conf, g, vec ? npix : row_end, vec, 0.f, f);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
           if (!(f[j] >= min_conf)) c[j] = 0;
@@ -185,8 +121,8 @@ regions_tile_kernel(const uint8_t* __restrict__ mask, const float* __restrict__ 
     }
     const int64_t g = (int64_t)gy * W + gx;
     const int64_t lim = vec ? npix : (int64_t)(gy + 1) * W;
-    rg_store4(parent, g, lim, vec, out);
-    rg_store4(area, g, lim, vec, zero);
+    quad_store(parent, g, lim, vec, out);
+    quad_store(area, g, lim, vec, zero);
   }
 }
 
@@ -260,7 +196,7 @@ regions_flatten_kernel(int* parent, int* __restrict__ area, int64_t npix, int ve
     const int64_t q = q0 + threadIdx.x;                          // the loop bound is uniform over the block: shuffles below
     int r[4] = {-1, -1, -1, -1}, cnt[4];
     if (q < nquads) {
-      rg_load4(parent, q << 2, npix, vec, -1, r);
+      quad_load(parent, q << 2, npix, vec, -1, r);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         int a = r[j];
@@ -268,7 +204,7 @@ regions_flatten_kernel(int* parent, int* __restrict__ area, int64_t npix, int ve
         for (;;) { const int p = parent[a]; if (p >= a) break; a = p; }
         r[j] = a;
       }
-      rg_store4(parent, q << 2, npix, vec, r);
+      quad_store(parent, q << 2, npix, vec, r);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) cnt[j] = r[j] >= 0;
@@ -279,8 +215,8 @@ regions_flatten_kernel(int* parent, int* __restrict__ area, int64_t npix, int ve
     for (int j = 0; j < 4; ++j) {
       const int key = cnt[j] > 0 ? r[j] : -1;
       if (__ballot(key >= 0) == 0) continue;
-      const RgRuns runs = rg_runs(key);
-      const int total = rg_run_reduce(runs, cnt[j], RgAdd());
+      const WaveRuns runs = wave_runs(key);
+      const int total = wave_run_reduce(runs, cnt[j], WaveAdd());
       if (runs.head && key >= 0) atomicAdd(area + key, total);
     }
   }
@@ -289,27 +225,17 @@ regions_flatten_kernel(int* parent, int* __restrict__ area, int64_t npix, int ve
 // ---------------------------------------------------------------------------------------------
 // count / scan / number: ids 1..N in ascending root order by a three-launch prefix sum over blocks of RG_NB pixels.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int rg_wave_incl_scan(int v) {
-  const int lane = (int)__lane_id();
-#pragma unroll
-  for (int d = 1; d < INSAR_WAVE; d <<= 1) {
-    const int o = __shfl_up(v, d, INSAR_WAVE);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-
 __global__ void __launch_bounds__(RG_THREADS)
 regions_count_kernel(const int* __restrict__ parent, const int* __restrict__ area, int64_t npix, int64_t min_area, int vec,
                      int* __restrict__ counts, InsarRegion* __restrict__ table, int max_regions) {
   __shared__ int wsum[RG_THREADS / INSAR_WAVE];
   const int64_t i = (int64_t)blockIdx.x * RG_NB + threadIdx.x * 4;
   int p[4], a[4], c = 0;
-  rg_load4(parent, i, npix, vec && i < npix, -1, p);
-  rg_load4(area, i, npix, vec && i < npix, 0, a);
+  quad_load(parent, i, npix, vec && i < npix, -1, p);
+  quad_load(area, i, npix, vec && i < npix, 0, a);
 #pragma unroll
   for (int j = 0; j < 4; ++j) c += (i + j < npix && p[j] == i + j && (int64_t)a[j] >= min_area);
-  c = rg_wave_incl_scan(c);
+  c = wave_incl_scan(c);
   if ((threadIdx.x & (INSAR_WAVE - 1)) == INSAR_WAVE - 1) wsum[threadIdx.x / INSAR_WAVE] = c;
   __syncthreads();
   if (threadIdx.x == 0) counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
@@ -330,7 +256,7 @@ regions_scan_kernel(int* __restrict__ counts, int nblk, InsarRegion* __restrict_
   for (int base = 0; base < nblk; base += RG_SCAN_THREADS) {
     const int i = base + threadIdx.x;
     const int v = i < nblk ? counts[i] : 0;
-    const int incl = rg_wave_incl_scan(v);
+    const int incl = wave_incl_scan(v);
     if ((threadIdx.x & (INSAR_WAVE - 1)) == INSAR_WAVE - 1) wsum[threadIdx.x / INSAR_WAVE] = incl;
     __syncthreads();
     int woff = 0, total = 0;
@@ -359,15 +285,15 @@ regions_number_kernel(const int* __restrict__ parent, int* __restrict__ area, co
   const bool v4 = vec && i < npix;
   int p[4], a[4], c = 0;
   bool root[4], keep[4];
-  rg_load4(parent, i, npix, v4, -1, p);
-  rg_load4(area, i, npix, v4, 0, a);
+  quad_load(parent, i, npix, v4, -1, p);
+  quad_load(area, i, npix, v4, 0, a);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     root[j] = i + j < npix && p[j] == i + j;
     keep[j] = root[j] && (int64_t)a[j] >= min_area;
     c += keep[j];
   }
-  const int incl = rg_wave_incl_scan(c);
+  const int incl = wave_incl_scan(c);
   const int wave = threadIdx.x / INSAR_WAVE;
   if ((threadIdx.x & (INSAR_WAVE - 1)) == INSAR_WAVE - 1) wsum[wave] = incl;
   __syncthreads();
@@ -382,7 +308,7 @@ regions_number_kernel(const int* __restrict__ parent, int* __restrict__ area, co
       if (id <= max_regions) *reinterpret_cast<int2*>(&table[id].root) = make_int2((int)(i + j), (int)mask[i + j]);
     }
   }
-  if (i < npix) rg_store4(area, i, npix, v4, a);
+  if (i < npix) quad_store(area, i, npix, v4, a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -403,9 +329,9 @@ regions_relabel_kernel(const int* __restrict__ parent, const int* __restrict__ i
       const int64_t i = q << 2;
       int p[4], m[4];
       float f[4] = {0.f, 0.f, 0.f, 0.f};
-      rg_load4(parent, i, npix, vec, -1, p);
-      rg_load4_u8(mask, i, npix, vec, m);
-      if (conf) rg_load4_f32(conf, i, npix, vec, f);
+      quad_load(parent, i, npix, vec, -1, p);
+      quad_load_u8(mask, i, npix, vec, 0, m);
+      if (conf) quad_load(conf, i, npix, vec, 0.f, f);
       int y = (int)((uint32_t)i / (uint32_t)W), x = (int)((uint32_t)i - (uint32_t)y * (uint32_t)W) - 1;      // i < 2^31
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -416,7 +342,7 @@ regions_relabel_kernel(const int* __restrict__ parent, const int* __restrict__ i
         sy[j] = y; sx[j] = x;
         sc[j] = conf ? __float2ll_rn(fminf(fmaxf(f[j], 0.f), 1.f) * 1073741824.0f) : 0;
       }
-      rg_store4(labels, i, npix, vec, id);
+      quad_store(labels, i, npix, vec, id);
       if (vec) {
         *reinterpret_cast<uint32_t*>(mask_out + i) = (uint32_t)m[0] | ((uint32_t)m[1] << 8) | ((uint32_t)m[2] << 16) | ((uint32_t)m[3] << 24);
       } else {
@@ -439,13 +365,13 @@ regions_relabel_kernel(const int* __restrict__ parent, const int* __restrict__ i
     for (int j = 0; j < 4; ++j) {
       const int key = cnt[j] > 0 ? id[j] : 0;
       if (__ballot(key > 0) == 0) continue;
-      const RgRuns runs = rg_runs(key);
-      const long long n = rg_run_reduce(runs, (long long)cnt[j], RgAdd());
-      const long long ty = rg_run_reduce(runs, sy[j], RgAdd());
-      const long long tx = rg_run_reduce(runs, sx[j], RgAdd());
-      const long long tc = conf ? rg_run_reduce(runs, sc[j], RgAdd()) : 0;
-      const int by0 = rg_run_reduce(runs, y0[j], RgMin()), by1 = rg_run_reduce(runs, y1[j], RgMax());
-      const int bx0 = rg_run_reduce(runs, x0[j], RgMin()), bx1 = rg_run_reduce(runs, x1[j], RgMax());
+      const WaveRuns runs = wave_runs(key);
+      const long long n = wave_run_reduce(runs, (long long)cnt[j], WaveAdd());
+      const long long ty = wave_run_reduce(runs, sy[j], WaveAdd());
+      const long long tx = wave_run_reduce(runs, sx[j], WaveAdd());
+      const long long tc = conf ? wave_run_reduce(runs, sc[j], WaveAdd()) : 0;
+      const int by0 = wave_run_reduce(runs, y0[j], WaveMin()), by1 = wave_run_reduce(runs, y1[j], WaveMax());
+      const int bx0 = wave_run_reduce(runs, x0[j], WaveMin()), bx1 = wave_run_reduce(runs, x1[j], WaveMax());
       if (runs.head && key > 0 && key <= max_regions) {
         InsarRegion* r = table + key;
         atomicAdd(reinterpret_cast<unsigned long long*>(&r->area), (unsigned long long)n);

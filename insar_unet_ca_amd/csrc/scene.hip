@@ -7,7 +7,7 @@
 // the origin table and adds their contributions in ascending tile index, so that a pixel's sum is one fixed chain of
 // fp32 operations (acc = fma(w, p, acc); wsum = wsum + w) whatever the batch size: the chain is merely cut at batch
 // boundaries, where acc / wsum pass through memory unchanged. No atomics, no dependence on scheduling.
-#include "common.h"
+#include "scene_common.h"
 
 // every multiply-add below is written out (fmaf) or meant to stay two roundings: the bitwise contract of the blend must not
 // hang on where the compiler chooses to fuse
@@ -26,33 +26,9 @@ __device__ __forceinline__ float scene_ramp(int i, int T, int o) {
 
 // ---------------------------------------------------------------------------------------------
 // gather: out[t][0][ty][tx] = norm(scene[y0_t + ty][x0_t + tx]); uint8 scenes get the reference's ToTensor + Normalize
-// (x = v / 255; (x - 0.5) / 0.5, data.reference_transforms), float32 scenes are copied. One thread per four output
+// (x = v / 255; (x - 0.5) / 0.5, data.reference_transforms), float32 scenes are copied (image_quad). One thread per four output
 // pixels (T % 4 == 0: a quad never leaves its tile row). A tile whose origin lies outside the scene is zero-filled.
 // ---------------------------------------------------------------------------------------------
-template <typename S> struct SceneLoad;
-template <> struct SceneLoad<uint8_t> {
-  __device__ __forceinline__ static void quad(const uint8_t* p, float* f) {
-    uint32_t u;
-    if ((((uintptr_t)p) & 3u) == 0) u = *reinterpret_cast<const uint32_t*>(p);
-    else u = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float x = (float)((u >> (8 * j)) & 0xffu) / 255.0f;
-      f[j] = (x - 0.5f) / 0.5f;
-    }
-  }
-};
-template <> struct SceneLoad<float> {
-  __device__ __forceinline__ static void quad(const float* p, float* f) {
-    if ((((uintptr_t)p) & 15u) == 0) {
-      const float4 v = *reinterpret_cast<const float4*>(p);
-      f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-    } else {
-      f[0] = p[0]; f[1] = p[1]; f[2] = p[2]; f[3] = p[3];
-    }
-  }
-};
-
 template <typename S>
 __global__ void __launch_bounds__(SC_THREADS)
 scene_gather_kernel(const S* __restrict__ scene, int H, int W, const int32_t* __restrict__ origins, int n, int T,
@@ -67,7 +43,7 @@ scene_gather_kernel(const S* __restrict__ scene, int H, int W, const int32_t* __
     const int y0 = origins[2 * t], x0 = origins[2 * t + 1];
     float f[4] = {0.f, 0.f, 0.f, 0.f};
     if (y0 >= 0 && x0 >= 0 && y0 + T <= H && x0 + T <= W)
-      SceneLoad<S>::quad(scene + (int64_t)(y0 + ty) * W + x0 + tx, f);
+      image_quad<S>(scene + (int64_t)(y0 + ty) * W + x0 + tx, f);
     *reinterpret_cast<float4*>(out + (q << 2)) = make_float4(f[0], f[1], f[2], f[3]);
   }
 }

@@ -1,0 +1,148 @@
+// What the scene pipeline (scene.hip, regions.hip, augment.hip, overlap.hip, distance.hip, crops.hip) and the dropout kernel of
+// deeplab.hip share: the counter hash, the guarded four-element access, the wave primitives (runs of equal keys, scan,
+// max) and the image / label quads of the two gather kernels. Each file's kernels, launch geometry and argument checks are
+// its own.
+#pragma once
+#include "common.h"
+
+// ---- hash ---------------------------------------------------------------------------------------------------------------
+// insar_hash64(key, i) is aug_hash64 of include/insar_hip.h: splitmix64's finaliser over key + golden * (i + 1), uint64 with
+// wrap-around. Everything random in the library (dropout masks, augmentation tables and noise, crop draws) is this function
+// of a key and a counter; insar_unet_ca_amd/augment.py and the tests' references restate it in Python.
+__host__ __device__ __forceinline__ uint64_t insar_mix64(uint64_t z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__host__ __device__ __forceinline__ uint64_t insar_hash64(uint64_t key, uint64_t i) {
+  return insar_mix64(key + 0x9E3779B97F4A7C15ull * (i + 1ull));
+}
+
+// ---- four consecutive elements per thread: one 16-byte (4-byte for uint8) access where `vec`, guarded scalars otherwise ----
+// `vec` promises i + 4 <= n and an aligned p + i; without it, elements at or past n read as `fill` and are not written.
+__device__ __forceinline__ void quad_load(const int* p, int64_t i, int64_t n, bool vec, int fill, int* v) {
+  if (vec) {
+    const int4 q = *reinterpret_cast<const int4*>(p + i);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (i + j < n) ? p[i + j] : fill;
+  }
+}
+__device__ __forceinline__ void quad_load(const float* p, int64_t i, int64_t n, bool vec, float fill, float* v) {
+  if (vec) {
+    const float4 q = *reinterpret_cast<const float4*>(p + i);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (i + j < n) ? p[i + j] : fill;
+  }
+}
+__device__ __forceinline__ void quad_load_u8(const uint8_t* p, int64_t i, int64_t n, bool vec, int fill, int* v) {
+  if (vec) {
+    const uint32_t u = *reinterpret_cast<const uint32_t*>(p + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (int)((u >> (8 * j)) & 0xffu);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (i + j < n) ? (int)p[i + j] : fill;
+  }
+}
+__device__ __forceinline__ void quad_store(int* p, int64_t i, int64_t n, bool vec, const int* v) {
+  if (vec) {
+    *reinterpret_cast<int4*>(p + i) = make_int4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (i + j < n) p[i + j] = v[j];
+  }
+}
+
+// ---- wave primitives, all over the INSAR_WAVE lanes of a full wave -----------------------------------------------------------
+// runs of equal keys over the lanes; wave_run_reduce collects op over a run at its first lane (`head`)
+struct WaveRuns { int lane, id; bool head; };
+template <typename K>
+__device__ __forceinline__ WaveRuns wave_runs(K key) {
+  WaveRuns r;
+  r.lane = (int)__lane_id();
+  const K prev = __shfl_up(key, 1, INSAR_WAVE);
+  r.head = r.lane == 0 || prev != key;
+  const unsigned long long heads = __ballot(r.head);
+  r.id = __popcll(heads & ((2ull << r.lane) - 1ull));          // lane 63: 2 << 63 wraps to 0, the mask is all ones
+  return r;
+}
+template <typename T, typename Op>
+__device__ __forceinline__ T wave_run_reduce(const WaveRuns& r, T v, Op op) {
+#pragma unroll
+  for (int d = 1; d < INSAR_WAVE; d <<= 1) {
+    const T o = __shfl_down(v, d, INSAR_WAVE);
+    const int oid = __shfl_down(r.id, d, INSAR_WAVE);
+    if (r.lane + d < INSAR_WAVE && oid == r.id) v = op(v, o);
+  }
+  return v;
+}
+struct WaveAdd { template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; } };
+struct WaveMin { template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a < b ? a : b; } };
+struct WaveMax { template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a > b ? a : b; } };
+
+// lane: a caller that already keeps threadIdx.x & 63 passes it; taking __lane_id() again costs crops_scan_rows_kernel 0.4 %
+__device__ __forceinline__ int wave_incl_scan(int v, int lane = (int)__lane_id()) {
+#pragma unroll
+  for (int d = 1; d < INSAR_WAVE; d <<= 1) {
+    const int o = __shfl_up(v, d, INSAR_WAVE);
+    if (lane >= d) v += o;
+  }
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
+#pragma unroll
+  for (int o = INSAR_WAVE / 2; o > 0; o >>= 1) {
+    const unsigned long long u = __shfl_xor(v, o, INSAR_WAVE);
+    v = u > v ? u : v;
+  }
+  return v;
+}
+
+// ---- image and label quads of the gather kernels (insar_scene_gather, insar_crops_gather) ---------------------------------------
+// four uint8 at any address as one dword, element 0 in the low byte
+__device__ __forceinline__ uint32_t load4_u8_any(const uint8_t* p) {
+  if ((((uintptr_t)p) & 3u) == 0) return *reinterpret_cast<const uint32_t*>(p);
+  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+// four adjacent scene pixels as network input: uint8 gets the reference's ToTensor + Normalize (x = v / 255; (x - 0.5) / 0.5,
+// data.reference_transforms), float32 is copied. The gathers' contract is bitwise: contraction is off whatever the includer set.
+template <typename S>
+__device__ __forceinline__ void image_quad(const S* p, float* f);
+template <>
+__device__ __forceinline__ void image_quad<uint8_t>(const uint8_t* p, float* f) {
+#pragma clang fp contract(off)
+  const uint32_t u = load4_u8_any(p);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float x = (float)((u >> (8 * j)) & 0xffu) / 255.0f;
+    f[j] = (x - 0.5f) / 0.5f;
+  }
+}
+template <>
+__device__ __forceinline__ void image_quad<float>(const float* p, float* f) {
+  if ((((uintptr_t)p) & 15u) == 0) {
+    const float4 v = *reinterpret_cast<const float4*>(p);
+    f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
+  } else {
+    f[0] = p[0]; f[1] = p[1]; f[2] = p[2]; f[3] = p[3];
+  }
+}
+
+// int64 masks move as 16-byte pairs; four labels packed in a dword (element 0 in the low byte) widen into two of them
+struct __attribute__((aligned(16))) insar_i64x2 { int64_t a, b; };
+__device__ __forceinline__ void quad_store_i64(int64_t* p, const int64_t* v) {          // p 16-byte aligned
+  insar_i64x2* o = reinterpret_cast<insar_i64x2*>(p);
+  insar_i64x2 lo, hi;
+  lo.a = v[0]; lo.b = v[1]; hi.a = v[2]; hi.b = v[3];
+  o[0] = lo;
+  o[1] = hi;
+}
+__device__ __forceinline__ void labels4_store_i64(int64_t* p, uint32_t u) {
+  const int64_t v[4] = {(int64_t)(u & 0xffu), (int64_t)((u >> 8) & 0xffu), (int64_t)((u >> 16) & 0xffu), (int64_t)(u >> 24)};
+  quad_store_i64(p, v);
+}

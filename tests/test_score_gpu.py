@@ -131,6 +131,18 @@ def test_scene_off_the_vector_width(dev):
     _check_table(dev, pred["labels"], gt["labels"], what="199x263, no void")
 
 
+@pytest.mark.parametrize("with_void", [False, True])
+def test_small_scene_off_the_vector_width(dev, with_void):
+    """33 x 65 = 2 145 pixels, H * W % 4 == 1: 537 quads, every one through the guarded scalar loads of the count kernel, the
+    last with one pixel in it; 2.1 work-groups, 8.4 waves."""
+    H, W = 33, 65
+    m = striped_random(H, W, 0.55, seed=65)
+    pred, gt = _label(dev, m, connectivity=8), _label(dev, np.roll(m, (1, 2), axis=(0, 1)), connectivity=8)
+    got = _check_table(dev, pred["labels"], gt["labels"], void_map(H, W, seed=11) if with_void else None,
+                       what=f"33x65, void={with_void}")
+    assert len(got[0]) > 20
+
+
 def test_views_off_a_16_byte_boundary(dev):
     import insar_unet_ca_amd as iu
     m = striped_random(H0, W0, 0.55, seed=71)
