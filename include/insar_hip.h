@@ -625,6 +625,59 @@ int insar_regions_number(const uint8_t* mask, int32_t H, int32_t W, int64_t min_
 int insar_regions_relabel(const uint8_t* mask, const float* conf /*nullable*/, int32_t H, int32_t W, int32_t max_regions,
                           void* scratch, void* table, int32_t* labels, uint8_t* mask_out, void* stream);
 
+/* ---- region outlines (build-side addition; the reference has no post-processing): csrc/outline.hip ------------------------
+ * The exact pixel-edge ("crack") outline of every region of a label map `labels` int32 [H][W] (row-major; 0 or an id >= 1, as
+ * insar_regions_relabel writes it, but any int32 map is legal; H, W >= 1, H * W < 2^29), as ordered, closed rings of lattice
+ * vertices. Vertex (y, x), 0 <= y <= H, 0 <= x <= W, is the top-left corner of pixel (y, x).
+ *   edge:      side s (0 top, 1 right, 2 bottom, 3 left) of a pixel p = (y, x) with label L != 0 whose 4-neighbour across s
+ *              carries another label or lies outside the scene; id 4 * (y * W + x) + s; directed with the region on its right:
+ *              top east (y, x) -> (y, x+1), right south (y, x+1) -> (y+1, x+1), bottom west (y+1, x+1) -> (y+1, x), left north
+ *              (y+1, x) -> (y, x). A crack between two non-zero labels belongs to both regions, once in each direction.
+ *   successor: with A = p + d(s) the pixel ahead on the region side and B = A's neighbour across side s (outside the scene: 0),
+ *              a = (A carries L), b = (B carries L): a && b: left, (B, (s+3)%4); a && !b: straight, (A, s); !a && !b: right,
+ *              (p, (s+1)%4); !a && b (a saddle): left with connectivity 8, right with connectivity 4. A permutation of the edges.
+ *   ring:      one cycle of the successor map; its leader is its smallest edge id; rings are numbered 0..R-1 in ascending leader
+ *              order; an edge's rank is its distance from the leader along the successor. area2 = sum over the ring of
+ *              x_i * y_{i+1} - x_{i+1} * y_i of the edges' tail vertices: positive for exteriors, negative for holes.
+ *   vertices:  int32 [max_vertices][2] as (y, x), 8-byte aligned, ring after ring: the tails of a ring's edges in rank order. With
+ *              corners_only only the tails of edges whose side differs from their predecessor's are kept, in the same order.
+ *   table:     InsarRing [1 + max_rings], 16-byte aligned. Record 0 is the header: label = R, count = V, edges = E, the TRUE
+ *              numbers of rings, vertices written and boundary edges, which may exceed the capacities; record 1 + r is ring r.
+ *   scratch:   insar_outline_scratch_bytes(...) bytes, 16-byte aligned; nothing in it has to survive between calls or be cleared.
+ * Call edges, lead, rank, rings, write in this order on one stream, with the same H, W and max_edges; read E from the header
+ * after `edges` and pass it on as n_edges (lead .. write refuse n_edges > max_edges). 12 + 2 ceil(log2 E) launches in all, a
+ * function of E alone; one launch per step, no work-group waits on another, integers only (bitwise reproducible). No kernel
+ * writes an edge slot >= max_edges, a record > max_rings or a vertex >= max_vertices. Every argument is checked before the
+ * device is touched (null pointers, H * W, connectivity, capacities, alignment). */
+typedef struct InsarRing {
+  int64_t area2;           /* signed doubled area */
+  int32_t label, leader;   /* the region's label; the ring's smallest edge id (header record: label = R) */
+  int32_t start, count;    /* first vertex and number of vertices in the vertex array (header: count = V) */
+  int32_t edges;           /* crack length of the ring before corner compaction (header: E) */
+  int32_t y0, x0, y1, x1;  /* half-open vertex box: y0 <= y < y1, x0 <= x < x1 over the ring's vertices */
+  int32_t _pad;
+} InsarRing;
+/* host only: bytes of scratch for an H x W scene with max_edges edge slots, and of a table of max_rings rings */
+int insar_outline_scratch_bytes(int32_t H, int32_t W, int32_t max_rings, int32_t max_edges, int64_t* scratch_bytes,
+                                int64_t* table_bytes);
+/* host only: the launches of the five calls below for n_edges boundary edges: 12 + 2 ceil(log2 n_edges) (n_edges < 1: 6) */
+int insar_outline_launches(int32_t n_edges);
+/* 4 launches (side masks and block counts; one-work-group scan, E to the header, the rest of it cleared; per-pixel offsets;
+ * successor, id and turn flag of every edge below max_edges). 1 <= max_edges <= 2^30. */
+int insar_outline_edges(const int32_t* labels, int32_t H, int32_t W, int32_t connectivity, int32_t max_edges, void* scratch,
+                        void* table, void* stream);
+/* ceil(log2 n_edges) launches: pointer doubling with a running minimum; every edge learns its ring's leader. */
+int insar_outline_lead(int32_t H, int32_t W, int32_t n_edges, int32_t max_edges, void* scratch, void* stream);
+/* 1 + ceil(log2 n_edges) launches: every ring cut in front of its leader, then Wyllie list ranking. */
+int insar_outline_rank(int32_t H, int32_t W, int32_t n_edges, int32_t max_edges, void* scratch, void* stream);
+/* 3 launches (leaders and ring lengths per block; one-work-group scan, R to the header; ring numbers, records initialised) */
+int insar_outline_rings(const int32_t* labels, int32_t H, int32_t W, int32_t n_edges, int32_t max_rings, int32_t max_edges,
+                        void* scratch, void* table, void* stream);
+/* 4 launches (tails scattered into ring order; area2, box and vertex count per ring; one-work-group scan, V to the header; the
+ * kept vertices and every ring's start written) */
+int insar_outline_write(int32_t H, int32_t W, int32_t n_edges, int32_t corners_only, int32_t max_rings, int32_t max_vertices,
+                        int32_t max_edges, void* scratch, void* table, int32_t* vertices, void* stream);
+
 /* ---- overlaps of two label maps (build-side addition; the reference scores pixels only): csrc/overlap.hip ----------------
  * pred, gt int32 [H][W] (row-major, H * W < 2^31): 0 or a region id >= 1, as insar_regions_relabel writes them. voidmap uint8
  * [H][W], nullable: a pixel is dropped iff voidmap is given and voidmap[i] == void_value (0..255). Every remaining pixel with

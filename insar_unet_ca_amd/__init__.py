@@ -16,6 +16,7 @@ from .score import DetectionScore, match_from_overlaps, match_regions, region_ov
 from .augment import Augment  # noqa: F401
 from .distance import DistanceScratch, boundary_counts, boundary_iou, distance_transform, expand_labels, void_band  # noqa: F401
 from .crops import CropIndex, SceneCrops, draw_crops, gather_crops  # noqa: F401
+from .outlines import OutlineScratch, region_outlines, to_geojson, to_polygons  # noqa: F401
 
 __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "ChannelAttentionModule", "MaxPool2d", "CrossEntropyLoss", "DiceLoss", "DiceCELoss", "Adam", "GraphedTrainStep",
            "compute_metrics", "train_model", "validate_model", "save_history", "VOCSegDataset", "SyntheticTiles",
@@ -26,4 +27,5 @@ __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "Cha
            "AdamW", "LRSchedule", "split_decay_groups",
            "region_overlaps", "match_regions", "match_from_overlaps", "DetectionScore", "evaluate_scene",
            "DistanceScratch", "distance_transform", "void_band", "expand_labels", "boundary_counts", "boundary_iou",
-           "CropIndex", "SceneCrops", "draw_crops", "gather_crops"]
+           "CropIndex", "SceneCrops", "draw_crops", "gather_crops",
+           "OutlineScratch", "region_outlines", "to_polygons", "to_geojson"]

@@ -1,0 +1,550 @@
+// Region outlines: the exact pixel-edge ("crack") boundary of every region of an int32 label map [H][W], as ordered, closed
+// rings of lattice vertices (exteriors with positive, holes with negative doubled area). Semantics: include/insar_hip.h.
+// A boundary edge is a side (0 top, 1 right, 2 bottom, 3 left) of a labelled pixel whose neighbour across it differs; its id
+// is 4 * pixel + side, its COMPACT index k the number of boundary edges with a smaller id, so "smallest id" and "smallest
+// index" are the same thing and every array below is indexed by k. With E edges and L = ceil(log2 E):
+//
+//   edges   mark     per pixel: the 4-bit side mask; boundary edges per block of 1024 pixels
+//           scan     one work-group: exclusive prefix sum of the block counts; E goes to the table header
+//           offsets  per pixel: the compact index of its first edge
+//           link     per edge: successor (the turn rule), id, "the successor turns" flag; pair (succ, k) for `lead`
+//   lead    L rounds of pointer doubling on pairs (jump, min): (j, m)[k] <- (j[j[k]], min(m[k], m[j[k]])); after them m[k]
+//           is the smallest edge of k's ring, its leader
+//   rank    cut      every ring is cut in front of its leader: pair (next, d) = (succ, 1), or (-1, 0) for the last edge
+//           L rounds of Wyllie list ranking on the pairs: d[k] becomes the distance from k to the last edge of its ring
+//   rings   count    leaders and their ring lengths per block of 1024 edges
+//           scan     one work-group: both prefix sums; R goes to the header
+//           number   per leader: ring number and first position in the ordered array; the ring's record is initialised
+//   write   scatter  per edge: position = ring start + rank; tail vertex, ring number and side go there, the corner flag of
+//                    the SUCCESSOR goes to the successor's position
+//           reduce   over the ordered array, where a ring is one contiguous run: area2, box and kept-vertex count (combined
+//                    over the runs of a wave before the atomics); kept vertices per block of 256 positions
+//           scan     one work-group: prefix sum of the kept counts; V goes to the header
+//           compact  kept vertices to their final place; every ring's `start`
+//
+// 12 + 2 L launches, a function of E alone. One launch per step and no work-group ever waits on another: every round reads one
+// buffer and writes the other, ordered by kernel boundaries on the caller's stream. Integers only: the atomics add int64 /
+// take int32 minima and maxima, so their arrival order changes nothing. A round moves 24 bytes per edge: 8 read in index
+// order, 8 gathered, 8 written; the pair packing makes the gather one 8-byte access instead of two 4-byte ones.
+// Capacity: no kernel writes an edge slot >= max_edges, a record > max_rings or a vertex >= max_vertices; lead / rank / rings /
+// write take the edge count read back from the header and refuse one above max_edges.
+#include "scene_common.h"
+#include <limits.h>
+
+#define OL_THREADS 256
+#define OL_NB 1024                        // pixels / edges per numbering block (256 threads x 4)
+#define OL_SCAN_THREADS 1024
+#define OL_MAX_EDGES (1 << 30)
+#define OL_MAX_PIX ((int64_t)1 << 29)
+
+static_assert(sizeof(InsarRing) == 48, "InsarRing is three 16-byte stores");
+static_assert(OL_THREADS == 4 * INSAR_WAVE, "four waves per work-group in ol_block_excl");
+// int32 slots of the header record (InsarRing: area2 0-1, label 2, leader 3, start 4, count 5, edges 6, ...)
+#define OL_HDR_RINGS 2
+#define OL_HDR_VERTS 5
+#define OL_HDR_EDGES 6
+
+// exclusive prefix of v over the work-group's threads; *total is the work-group's sum. wsum: OL_THREADS / INSAR_WAVE ints of LDS.
+__device__ __forceinline__ int ol_block_excl(int v, int* wsum, int* total) {
+  const int lane = threadIdx.x & (INSAR_WAVE - 1), wave = threadIdx.x / INSAR_WAVE;
+  const int incl = wave_incl_scan(v, lane);
+  if (lane == INSAR_WAVE - 1) wsum[wave] = incl;
+  __syncthreads();
+  int off = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < OL_THREADS / INSAR_WAVE; ++w) {
+    if (w < wave) off += wsum[w];
+    tot += wsum[w];
+  }
+  *total = tot;
+  __syncthreads();                                               // wsum is free again
+  return off + incl - v;
+}
+__device__ __forceinline__ int ol_below(int mask, int s) { return __popc(mask & ((1 << s) - 1)); }
+
+// ---------------------------------------------------------------------------------------------
+// edges: mark / scan / offsets / link
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(OL_THREADS)
+outline_mark_kernel(const int* __restrict__ labels, int H, int W, int npix, int vec, uint8_t* __restrict__ mask,
+                    int* __restrict__ counts) {
+  __shared__ int wsum[OL_THREADS / INSAR_WAVE];
+  const int i = blockIdx.x * OL_NB + threadIdx.x * 4;
+  int v[4];
+  quad_load(labels, i, npix, vec && i < npix, 0, v);
+  uint32_t m4 = 0;
+  if (i < npix) {
+    int y = (int)((uint32_t)i / (uint32_t)W), x = i - y * W;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = v[j];
+      if (i + j < npix && c != 0) {                              // x + 1 < W implies i + j + 1 < npix
+        const int up = y > 0 ? labels[i + j - W] : 0, dn = y + 1 < H ? labels[i + j + W] : 0;
+        const int lf = x > 0 ? (j > 0 ? v[j > 0 ? j - 1 : 0] : labels[i + j - 1]) : 0;
+        const int rt = x + 1 < W ? (j < 3 ? v[j < 3 ? j + 1 : 3] : labels[i + j + 1]) : 0;
+        const uint32_t m = (uint32_t)(up != c) | ((uint32_t)(rt != c) << 1) | ((uint32_t)(dn != c) << 2) | ((uint32_t)(lf != c) << 3);
+        m4 |= m << (8 * j);
+      }
+      if (++x == W) { x = 0; ++y; }
+    }
+    if (vec) {
+      *reinterpret_cast<uint32_t*>(mask + i) = m4;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (i + j < npix) mask[i + j] = (uint8_t)((m4 >> (8 * j)) & 0xffu);
+    }
+  }
+  int total;
+  ol_block_excl(__popc(m4), wsum, &total);
+  if (threadIdx.x == 0) counts[blockIdx.x] = total;
+}
+
+// One work-group: a[] (and b[], nullable) become their exclusive prefix sums; the totals go to the header's int32 slots.
+// `clear`: the other slots of the header are zeroed first (the first scan of a call).
+__global__ void __launch_bounds__(OL_SCAN_THREADS)
+outline_scan_kernel(int* __restrict__ a, int* __restrict__ b, int nblk, int* __restrict__ hdr, int slot_a, int slot_b, int clear) {
+  __shared__ int wa[OL_SCAN_THREADS / INSAR_WAVE], wb[OL_SCAN_THREADS / INSAR_WAVE];
+  int carry_a = 0, carry_b = 0;                                  // every thread keeps the same running totals (< 2^31)
+  for (int base = 0; base < nblk; base += OL_SCAN_THREADS) {
+    const int i = base + threadIdx.x;
+    const int va = i < nblk ? a[i] : 0, vb = (b && i < nblk) ? b[i] : 0;
+    const int ia = wave_incl_scan(va), ib = wave_incl_scan(vb);
+    if ((threadIdx.x & (INSAR_WAVE - 1)) == INSAR_WAVE - 1) { wa[threadIdx.x / INSAR_WAVE] = ia; wb[threadIdx.x / INSAR_WAVE] = ib; }
+    __syncthreads();
+    int oa = 0, ta = 0, ob = 0, tb = 0;
+#pragma unroll
+    for (int w = 0; w < OL_SCAN_THREADS / INSAR_WAVE; ++w) {
+      if (w < (int)(threadIdx.x / INSAR_WAVE)) { oa += wa[w]; ob += wb[w]; }
+      ta += wa[w]; tb += wb[w];
+    }
+    if (i < nblk) {
+      a[i] = carry_a + oa + ia - va;
+      if (b) b[i] = carry_b + ob + ib - vb;
+    }
+    carry_a += ta; carry_b += tb;
+    __syncthreads();
+  }
+  if (threadIdx.x < (int)(sizeof(InsarRing) / 4)) {
+    const int t = threadIdx.x;
+    if (t == slot_a) hdr[t] = carry_a;
+    else if (b && t == slot_b) hdr[t] = carry_b;
+    else if (clear) hdr[t] = 0;
+  }
+}
+
+__global__ void __launch_bounds__(OL_THREADS)
+outline_offsets_kernel(const uint8_t* __restrict__ mask, int npix, int vec, const int* __restrict__ counts, int* __restrict__ off) {
+  __shared__ int wsum[OL_THREADS / INSAR_WAVE];
+  const int i = blockIdx.x * OL_NB + threadIdx.x * 4;
+  int m[4];
+  quad_load_u8(mask, i, npix, vec && i < npix, 0, m);
+  const int c = __popc(m[0]) + __popc(m[1]) + __popc(m[2]) + __popc(m[3]);
+  int total;
+  int o = counts[blockIdx.x] + ol_block_excl(c, wsum, &total);
+  int out[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { out[j] = o; o += __popc(m[j]); }
+  if (i < npix) quad_store(off, i, npix, vec, out);
+}
+
+__device__ __forceinline__ int ol_label_at(const int* __restrict__ labels, int y, int x, int H, int W) {
+  return ((unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W) ? labels[y * W + x] : 0;
+}
+
+__global__ void __launch_bounds__(OL_THREADS)
+outline_link_kernel(const int* __restrict__ labels, const uint8_t* __restrict__ mask, const int* __restrict__ off, int H, int W,
+                    int npix, int conn8, int cap, int* __restrict__ succ0, int* __restrict__ eid, uint8_t* __restrict__ turn,
+                    int2* __restrict__ pair) {
+  const int p = blockIdx.x * OL_THREADS + threadIdx.x;           // one pixel per thread: neighbouring lanes, neighbouring edges
+  if (p >= npix) return;
+  const int m = mask[p];
+  if (!m) return;
+  const int c = labels[p], base = off[p];
+  const int y = (int)((uint32_t)p / (uint32_t)W), x = p - y * W;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    if (!((m >> s) & 1)) continue;
+    const int k = base + ol_below(m, s);
+    if (k >= cap) continue;
+    // travel direction d(s): east, south, west, north; the outer side lies towards d((s + 3) % 4)
+    const int dy = (s == 1) - (s == 3), dx = (s == 0) - (s == 2);
+    const int n = (s + 3) & 3;
+    const int ny = (n == 1) - (n == 3), nx = (n == 0) - (n == 2);
+    const int ay = y + dy, ax = x + dx, by = ay + ny, bx = ax + nx;
+    const bool a = ol_label_at(labels, ay, ax, H, W) == c, b = ol_label_at(labels, by, bx, H, W) == c;
+    int q, s2, t = 1;
+    if (b && (a || conn8)) { q = by * W + bx; s2 = n; }          // left
+    else if (a) { q = ay * W + ax; s2 = s; t = 0; }              // straight
+    else { q = p; s2 = (s + 1) & 3; }                            // right
+    int k2 = off[q] + ol_below(mask[q], s2);
+    if (k2 >= cap) k2 = k;                                       // more edges than slots: the caller reads E and stops
+    succ0[k] = k2;
+    eid[k] = 4 * p + s;
+    turn[k] = (uint8_t)t;
+    pair[k] = make_int2(k2, k);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// lead / rank: one round per launch, from one pair buffer into the other
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(OL_THREADS)
+outline_lead_round_kernel(const int2* __restrict__ in, int2* __restrict__ out, int n) {
+  const int k = blockIdx.x * OL_THREADS + threadIdx.x;
+  if (k >= n) return;
+  const int2 a = in[k];
+  const int2 b = in[a.x];
+  out[k] = make_int2(b.x, min(a.y, b.y));
+}
+
+__global__ void __launch_bounds__(OL_THREADS)
+outline_cut_kernel(const int2* __restrict__ in, const int* __restrict__ succ0, int* __restrict__ lead, int2* __restrict__ out, int n) {
+  const int k = blockIdx.x * OL_THREADS + threadIdx.x;
+  if (k >= n) return;
+  const int m = in[k].y, s = succ0[k];
+  lead[k] = m;
+  out[k] = s == m ? make_int2(-1, 0) : make_int2(s, 1);          // the successor of a ring's last edge is its leader
+}
+
+__global__ void __launch_bounds__(OL_THREADS)
+outline_rank_round_kernel(const int2* __restrict__ in, int2* __restrict__ out, int n) {
+  const int k = blockIdx.x * OL_THREADS + threadIdx.x;
+  if (k >= n) return;
+  int2 a = in[k];
+  if (a.x >= 0) {
+    const int2 b = in[a.x];
+    a = make_int2(b.x, a.y + b.y);
+  }
+  out[k] = a;
+}
+
+// ---------------------------------------------------------------------------------------------
+// rings: count / scan / number
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(OL_THREADS)
+outline_ring_count_kernel(const int* __restrict__ lead, const int2* __restrict__ dist, int n, int* __restrict__ rcnt,
+                          int* __restrict__ rlen) {
+  __shared__ int wsum[OL_THREADS / INSAR_WAVE];
+  const int k0 = blockIdx.x * OL_NB + threadIdx.x * 4;
+  int c = 0, l = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int k = k0 + j;
+    if (k < n && lead[k] == k) { ++c; l += dist[k].y + 1; }
+  }
+  int tc, tl;
+  ol_block_excl(c, wsum, &tc);
+  ol_block_excl(l, wsum, &tl);
+  if (threadIdx.x == 0) { rcnt[blockIdx.x] = tc; rlen[blockIdx.x] = tl; }
+}
+
+__global__ void __launch_bounds__(OL_THREADS)
+outline_ring_number_kernel(const int* __restrict__ lead, const int2* __restrict__ dist, const int* __restrict__ eid,
+                           const int* __restrict__ labels, int n, const int* __restrict__ rcnt, const int* __restrict__ rlen,
+                           int2* __restrict__ info, InsarRing* __restrict__ rings, int max_rings) {
+  __shared__ int wsum[OL_THREADS / INSAR_WAVE];
+  const int k0 = blockIdx.x * OL_NB + threadIdx.x * 4;
+  bool is[4];
+  int len[4], c = 0, l = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int k = k0 + j;
+    is[j] = k < n && lead[k] == k;
+    len[j] = is[j] ? dist[k].y + 1 : 0;
+    c += is[j]; l += len[j];
+  }
+  int tc, tl;
+  int r = rcnt[blockIdx.x] + ol_block_excl(c, wsum, &tc);
+  int st = rlen[blockIdx.x] + ol_block_excl(l, wsum, &tl);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (!is[j]) continue;
+    const int k = k0 + j;
+    info[k] = make_int2(r, st);
+    if (r < max_rings) {                                         // area2 0, start / count by `write`, an empty box
+      const int e = eid[k];
+      int4* t4 = reinterpret_cast<int4*>(rings + 1 + r);
+      t4[0] = make_int4(0, 0, labels[e >> 2], e);
+      t4[1] = make_int4(0, 0, len[j], INT_MAX);
+      t4[2] = make_int4(INT_MAX, 0, 0, 0);
+    }
+    ++r; st += len[j];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// write: scatter / reduce / scan / compact
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(OL_THREADS)
+outline_scatter_kernel(const int* __restrict__ lead, const int2* __restrict__ dist, const int2* __restrict__ info,
+                       const int* __restrict__ succ0, const int* __restrict__ eid, const uint8_t* __restrict__ turn, int n, int W,
+                       int corners_only, int2* __restrict__ overt, int* __restrict__ ometa, uint8_t* __restrict__ ocorner) {
+  const int k = blockIdx.x * OL_THREADS + threadIdx.x;
+  if (k >= n) return;
+  const int m = lead[k];
+  const int2 ri = info[m];
+  const int pos = ri.y + dist[m].y - dist[k].y;
+  if ((unsigned)pos >= (unsigned)n) return;                      // cannot happen on a permutation; never leave the arrays
+  const int e = eid[k], s = e & 3, p = e >> 2;
+  const int y = (int)((uint32_t)p / (uint32_t)W), x = p - y * W;
+  overt[pos] = make_int2(y + (s >= 2), x + (s == 1 || s == 2));  // the tail: (y, x), (y, x+1), (y+1, x+1), (y+1, x)
+  ometa[pos] = ri.x * 4 + s;                                     // a ring has four edges or more: ring * 4 < E
+  const int ps = succ0[k] == m ? ri.y : pos + 1;
+  if ((unsigned)ps < (unsigned)n) ocorner[ps] = corners_only ? turn[k] : (uint8_t)1;
+}
+
+__global__ void __launch_bounds__(OL_THREADS)
+outline_reduce_kernel(const int2* __restrict__ overt, const int* __restrict__ ometa, const uint8_t* __restrict__ ocorner, int n,
+                      InsarRing* __restrict__ rings, int max_rings, int* __restrict__ ccnt) {
+  __shared__ int wsum[OL_THREADS / INSAR_WAVE];
+  const int i = blockIdx.x * OL_THREADS + threadIdx.x;
+  int key = -1, vy = 0, vx = 0, flag = 0;
+  long long a2 = 0;
+  if (i < n) {
+    const int meta = ometa[i], s = meta & 3;
+    const int2 v = overt[i];
+    key = meta >> 2; vy = v.x; vx = v.y; flag = ocorner[i];
+    a2 = s == 0 ? -vy : s == 1 ? vx : s == 2 ? vy : -vx;         // x_i * y_{i+1} - x_{i+1} * y_i with the head one step along d(s)
+  }
+  const WaveRuns runs = wave_runs(key);
+  const long long ta = wave_run_reduce(runs, a2, WaveAdd());
+  const int tc = wave_run_reduce(runs, flag, WaveAdd());
+  const int y0 = wave_run_reduce(runs, vy, WaveMin()), y1 = wave_run_reduce(runs, vy + 1, WaveMax());
+  const int x0 = wave_run_reduce(runs, vx, WaveMin()), x1 = wave_run_reduce(runs, vx + 1, WaveMax());
+  if (runs.head && key >= 0 && key < max_rings) {
+    InsarRing* r = rings + 1 + key;
+    atomicAdd(reinterpret_cast<unsigned long long*>(&r->area2), (unsigned long long)ta);
+    atomicAdd(&r->count, tc);
+    // the box only tightens: a stale read can cost a redundant atomic, never lose an update
+    if (y0 < __hip_atomic_load(&r->y0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&r->y0, y0);
+    if (x0 < __hip_atomic_load(&r->x0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&r->x0, x0);
+    if (y1 > __hip_atomic_load(&r->y1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&r->y1, y1);
+    if (x1 > __hip_atomic_load(&r->x1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&r->x1, x1);
+  }
+  int total;
+  ol_block_excl(flag, wsum, &total);
+  if (threadIdx.x == 0) ccnt[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(OL_THREADS)
+outline_compact_kernel(const int2* __restrict__ overt, const int* __restrict__ ometa, const uint8_t* __restrict__ ocorner, int n,
+                       const int* __restrict__ ccnt, InsarRing* __restrict__ rings, int max_rings, int2* __restrict__ vertices,
+                       int max_vertices) {
+  __shared__ int wsum[OL_THREADS / INSAR_WAVE];
+  const int i = blockIdx.x * OL_THREADS + threadIdx.x;
+  const int flag = i < n ? ocorner[i] : 0;
+  int total;
+  const int o = ccnt[blockIdx.x] + ol_block_excl(flag, wsum, &total);
+  if (i >= n) return;
+  const int key = ometa[i] >> 2;
+  if ((i == 0 || (ometa[i - 1] >> 2) != key) && key < max_rings) rings[1 + key].start = o;
+  if (flag && o < max_vertices) vertices[o] = overt[i];
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side: scratch layout and the entry points
+// ---------------------------------------------------------------------------------------------
+struct OlLayout {
+  int npix, nblk, cap, eblk, cblk;
+  int64_t mask, off, counts, succ0, eid, turn, lead, p0, p1, overt, ometa, ocorner, rcnt, rlen, ccnt, bytes;
+};
+
+static int outline_layout(const char* who, int32_t H, int32_t W, int32_t max_edges, OlLayout* L) {
+  if (H < 1 || W < 1) INSAR_FAIL(INSAR_E_SHAPE, "%s: empty scene %d x %d", who, H, W);
+  const int64_t npix = (int64_t)H * W;
+  if (npix >= OL_MAX_PIX) INSAR_FAIL(INSAR_E_SHAPE, "%s: scene %d x %d has 2^29 pixels or more", who, H, W);
+  if (max_edges < 1 || max_edges > OL_MAX_EDGES) INSAR_FAIL(INSAR_E_SHAPE, "%s: max_edges %d outside 1 .. 2^30", who, max_edges);
+  L->npix = (int)npix;
+  L->nblk = (int)((npix + OL_NB - 1) / OL_NB);
+  L->cap = max_edges;
+  L->eblk = (max_edges + OL_NB - 1) / OL_NB;
+  L->cblk = (max_edges + OL_THREADS - 1) / OL_THREADS;
+  int64_t at = 0;
+  auto take = [&at](int64_t bytes) { const int64_t o = at; at += (bytes + 15) & ~(int64_t)15; return o; };
+  const int64_t cap = max_edges;
+  L->mask = take(npix);        L->off = take(npix * 4);    L->counts = take((int64_t)L->nblk * 4);
+  L->succ0 = take(cap * 4);    L->eid = take(cap * 4);     L->turn = take(cap);
+  L->lead = take(cap * 4);     L->p0 = take(cap * 8);      L->p1 = take(cap * 8);
+  L->overt = take(cap * 8);    L->ometa = take(cap * 4);   L->ocorner = take(cap);
+  L->rcnt = take((int64_t)L->eblk * 4);  L->rlen = take((int64_t)L->eblk * 4);  L->ccnt = take((int64_t)L->cblk * 4);
+  L->bytes = at;
+  return INSAR_OK;
+}
+static int outline_check_buf(const char* who, const void* p, const char* what) {
+  if (!p) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer", who);
+  if (!insar_aligned16(p)) INSAR_FAIL(INSAR_E_ALIGN, "%s: %s not 16-byte aligned", who, what);
+  return INSAR_OK;
+}
+static int outline_check_rings(const char* who, const void* table, int32_t max_rings) {
+  if (max_rings < 1 || max_rings > OL_MAX_EDGES) INSAR_FAIL(INSAR_E_SHAPE, "%s: max_rings %d outside 1 .. 2^30", who, max_rings);
+  return outline_check_buf(who, table, "table");
+}
+static int outline_check_count(const char* who, int32_t n_edges, const OlLayout& L) {
+  if (n_edges < 0 || n_edges > L.cap) INSAR_FAIL(INSAR_E_SHAPE, "%s: n_edges %d outside 0 .. max_edges=%d", who, n_edges, L.cap);
+  return INSAR_OK;
+}
+static inline int outline_rounds(int n) {                        // ceil(log2 n)
+  int r = 0;
+  while (((int64_t)1 << r) < n) ++r;
+  return r;
+}
+template <typename T>
+static inline T* ol_at(void* scratch, int64_t off) { return reinterpret_cast<T*>((char*)scratch + off); }
+static inline unsigned ol_grid(int n, int per) { return (unsigned)((n + per - 1) / per); }
+
+extern "C" int insar_outline_scratch_bytes(int32_t H, int32_t W, int32_t max_rings, int32_t max_edges, int64_t* scratch_bytes,
+                                           int64_t* table_bytes) {
+  const char* who = "insar_outline_scratch_bytes";
+  if (!scratch_bytes || !table_bytes) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer", who);
+  OlLayout L;
+  if (int rc = outline_layout(who, H, W, max_edges, &L)) return rc;
+  if (max_rings < 1 || max_rings > OL_MAX_EDGES) INSAR_FAIL(INSAR_E_SHAPE, "%s: max_rings %d outside 1 .. 2^30", who, max_rings);
+  *scratch_bytes = L.bytes;
+  *table_bytes = (int64_t)sizeof(InsarRing) * ((int64_t)max_rings + 1);
+  return INSAR_OK;
+}
+
+extern "C" int insar_outline_launches(int32_t n_edges) {
+  return n_edges < 1 ? 6 : 12 + 2 * outline_rounds(n_edges);
+}
+
+extern "C" int insar_outline_edges(const int32_t* labels, int32_t H, int32_t W, int32_t connectivity, int32_t max_edges,
+                                   void* scratch, void* table, void* stream) {
+  const char* who = "insar_outline_edges";
+  if (!labels) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer", who);
+  OlLayout L;
+  if (int rc = outline_layout(who, H, W, max_edges, &L)) return rc;
+  if (connectivity != 4 && connectivity != 8) INSAR_FAIL(INSAR_E_ARG, "%s: connectivity %d (4 or 8)", who, connectivity);
+  if (int rc = outline_check_buf(who, scratch, "scratch")) return rc;
+  if (int rc = outline_check_buf(who, table, "table")) return rc;
+  if (((uintptr_t)labels) & 3u) INSAR_FAIL(INSAR_E_ALIGN, "%s: labels not 4-byte aligned", who);
+  hipStream_t s = (hipStream_t)stream;
+  const int vec = L.npix % 4 == 0;
+  const int lvec = vec && insar_aligned16(labels);
+  uint8_t* mask = ol_at<uint8_t>(scratch, L.mask);
+  int *off = ol_at<int>(scratch, L.off), *counts = ol_at<int>(scratch, L.counts);
+  hipLaunchKernelGGL(outline_mark_kernel, dim3((unsigned)L.nblk), dim3(OL_THREADS), 0, s, labels, H, W, L.npix, lvec, mask, counts);
+  INSAR_CHECK_LAUNCH(who);
+  hipLaunchKernelGGL(outline_scan_kernel, dim3(1), dim3(OL_SCAN_THREADS), 0, s, counts, (int*)nullptr, L.nblk, (int*)table,
+                     OL_HDR_EDGES, -1, 1);
+  INSAR_CHECK_LAUNCH(who);
+  hipLaunchKernelGGL(outline_offsets_kernel, dim3((unsigned)L.nblk), dim3(OL_THREADS), 0, s, mask, L.npix, vec, counts, off);
+  INSAR_CHECK_LAUNCH(who);
+  hipLaunchKernelGGL(outline_link_kernel, dim3(ol_grid(L.npix, OL_THREADS)), dim3(OL_THREADS), 0, s, labels, mask, off, H, W,
+                     L.npix, connectivity == 8, L.cap, ol_at<int>(scratch, L.succ0), ol_at<int>(scratch, L.eid),
+                     ol_at<uint8_t>(scratch, L.turn), ol_at<int2>(scratch, L.p0));
+  INSAR_CHECK_LAUNCH(who);
+  return INSAR_OK;
+}
+
+// The pair buffers: `link` fills p0; round r of `lead` reads p[r & 1] and writes the other; `cut` reads p[L & 1] and writes
+// the other; round r of `rank` goes on from there, so the final distances are in p1 whatever L is, and p0 is free for `rings`.
+extern "C" int insar_outline_lead(int32_t H, int32_t W, int32_t n_edges, int32_t max_edges, void* scratch, void* stream) {
+  const char* who = "insar_outline_lead";
+  OlLayout L;
+  if (int rc = outline_layout(who, H, W, max_edges, &L)) return rc;
+  if (int rc = outline_check_count(who, n_edges, L)) return rc;
+  if (int rc = outline_check_buf(who, scratch, "scratch")) return rc;
+  if (n_edges == 0) return INSAR_OK;
+  int2* p[2] = {ol_at<int2>(scratch, L.p0), ol_at<int2>(scratch, L.p1)};
+  const int rounds = outline_rounds(n_edges);
+  for (int r = 0; r < rounds; ++r) {
+    hipLaunchKernelGGL(outline_lead_round_kernel, dim3(ol_grid(n_edges, OL_THREADS)), dim3(OL_THREADS), 0, (hipStream_t)stream,
+                       (const int2*)p[r & 1], p[(r & 1) ^ 1], n_edges);
+    INSAR_CHECK_LAUNCH(who);
+  }
+  return INSAR_OK;
+}
+
+extern "C" int insar_outline_rank(int32_t H, int32_t W, int32_t n_edges, int32_t max_edges, void* scratch, void* stream) {
+  const char* who = "insar_outline_rank";
+  OlLayout L;
+  if (int rc = outline_layout(who, H, W, max_edges, &L)) return rc;
+  if (int rc = outline_check_count(who, n_edges, L)) return rc;
+  if (int rc = outline_check_buf(who, scratch, "scratch")) return rc;
+  if (n_edges == 0) return INSAR_OK;
+  int2* p[2] = {ol_at<int2>(scratch, L.p0), ol_at<int2>(scratch, L.p1)};
+  const int rounds = outline_rounds(n_edges);
+  int cur = rounds & 1;
+  const unsigned grid = ol_grid(n_edges, OL_THREADS);
+  hipLaunchKernelGGL(outline_cut_kernel, dim3(grid), dim3(OL_THREADS), 0, (hipStream_t)stream, (const int2*)p[cur],
+                     (const int*)ol_at<int>(scratch, L.succ0), ol_at<int>(scratch, L.lead), p[cur ^ 1], n_edges);
+  INSAR_CHECK_LAUNCH(who);
+  cur ^= 1;
+  for (int r = 0; r < rounds; ++r, cur ^= 1) {
+    hipLaunchKernelGGL(outline_rank_round_kernel, dim3(grid), dim3(OL_THREADS), 0, (hipStream_t)stream, (const int2*)p[cur],
+                       p[cur ^ 1], n_edges);
+    INSAR_CHECK_LAUNCH(who);
+  }
+  return INSAR_OK;
+}
+
+extern "C" int insar_outline_rings(const int32_t* labels, int32_t H, int32_t W, int32_t n_edges, int32_t max_rings,
+                                   int32_t max_edges, void* scratch, void* table, void* stream) {
+  const char* who = "insar_outline_rings";
+  if (!labels) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer", who);
+  OlLayout L;
+  if (int rc = outline_layout(who, H, W, max_edges, &L)) return rc;
+  if (int rc = outline_check_count(who, n_edges, L)) return rc;
+  if (int rc = outline_check_rings(who, table, max_rings)) return rc;
+  if (int rc = outline_check_buf(who, scratch, "scratch")) return rc;
+  if (((uintptr_t)labels) & 3u) INSAR_FAIL(INSAR_E_ALIGN, "%s: labels not 4-byte aligned", who);
+  hipStream_t s = (hipStream_t)stream;
+  const int nblk = (int)ol_grid(n_edges, OL_NB);
+  int *lead = ol_at<int>(scratch, L.lead), *rcnt = ol_at<int>(scratch, L.rcnt), *rlen = ol_at<int>(scratch, L.rlen);
+  const int2* dist = ol_at<int2>(scratch, L.p1);
+  if (nblk > 0) {
+    hipLaunchKernelGGL(outline_ring_count_kernel, dim3((unsigned)nblk), dim3(OL_THREADS), 0, s, (const int*)lead, dist, n_edges,
+                       rcnt, rlen);
+    INSAR_CHECK_LAUNCH(who);
+  }
+  hipLaunchKernelGGL(outline_scan_kernel, dim3(1), dim3(OL_SCAN_THREADS), 0, s, rcnt, rlen, nblk, (int*)table, OL_HDR_RINGS, -1, 0);
+  INSAR_CHECK_LAUNCH(who);
+  if (nblk > 0) {
+    hipLaunchKernelGGL(outline_ring_number_kernel, dim3((unsigned)nblk), dim3(OL_THREADS), 0, s, (const int*)lead, dist,
+                       (const int*)ol_at<int>(scratch, L.eid), labels, n_edges, (const int*)rcnt, (const int*)rlen,
+                       ol_at<int2>(scratch, L.p0), (InsarRing*)table, max_rings);
+    INSAR_CHECK_LAUNCH(who);
+  }
+  return INSAR_OK;
+}
+
+extern "C" int insar_outline_write(int32_t H, int32_t W, int32_t n_edges, int32_t corners_only, int32_t max_rings,
+                                   int32_t max_vertices, int32_t max_edges, void* scratch, void* table, int32_t* vertices,
+                                   void* stream) {
+  const char* who = "insar_outline_write";
+  OlLayout L;
+  if (int rc = outline_layout(who, H, W, max_edges, &L)) return rc;
+  if (int rc = outline_check_count(who, n_edges, L)) return rc;
+  if (int rc = outline_check_rings(who, table, max_rings)) return rc;
+  if (max_vertices < 1) INSAR_FAIL(INSAR_E_SHAPE, "%s: max_vertices %d < 1", who, max_vertices);
+  if (!vertices) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer", who);
+  if (((uintptr_t)vertices) & 7u) INSAR_FAIL(INSAR_E_ALIGN, "%s: vertices not 8-byte aligned", who);
+  if (int rc = outline_check_buf(who, scratch, "scratch")) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int nblk = (int)ol_grid(n_edges, OL_THREADS);
+  int2* overt = ol_at<int2>(scratch, L.overt);
+  int *ometa = ol_at<int>(scratch, L.ometa), *ccnt = ol_at<int>(scratch, L.ccnt);
+  uint8_t* ocorner = ol_at<uint8_t>(scratch, L.ocorner);
+  if (nblk > 0) {
+    hipLaunchKernelGGL(outline_scatter_kernel, dim3((unsigned)nblk), dim3(OL_THREADS), 0, s, (const int*)ol_at<int>(scratch, L.lead),
+                       (const int2*)ol_at<int2>(scratch, L.p1), (const int2*)ol_at<int2>(scratch, L.p0),
+                       (const int*)ol_at<int>(scratch, L.succ0), (const int*)ol_at<int>(scratch, L.eid),
+                       (const uint8_t*)ol_at<uint8_t>(scratch, L.turn), n_edges, W, corners_only != 0, overt, ometa, ocorner);
+    INSAR_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(outline_reduce_kernel, dim3((unsigned)nblk), dim3(OL_THREADS), 0, s, (const int2*)overt, (const int*)ometa,
+                       (const uint8_t*)ocorner, n_edges, (InsarRing*)table, max_rings, ccnt);
+    INSAR_CHECK_LAUNCH(who);
+  }
+  hipLaunchKernelGGL(outline_scan_kernel, dim3(1), dim3(OL_SCAN_THREADS), 0, s, ccnt, (int*)nullptr, nblk, (int*)table,
+                     OL_HDR_VERTS, -1, 0);
+  INSAR_CHECK_LAUNCH(who);
+  if (nblk > 0) {
+    hipLaunchKernelGGL(outline_compact_kernel, dim3((unsigned)nblk), dim3(OL_THREADS), 0, s, (const int2*)overt, (const int*)ometa,
+                       (const uint8_t*)ocorner, n_edges, (const int*)ccnt, (InsarRing*)table, max_rings,
+                       reinterpret_cast<int2*>(vertices), max_vertices);
+    INSAR_CHECK_LAUNCH(who);
+  }
+  return INSAR_OK;
+}

@@ -281,9 +281,11 @@ class ScenePredictor:
             self.model.train(was_training)
         return _finalize(acc, wsum, return_prob)
 
-    def detect(self, scene, return_prob: bool = False, **region_kwargs) -> dict:
+    def detect(self, scene, return_prob: bool = False, outlines: bool = False, **region_kwargs) -> dict:
         """`predict(scene)` followed by `label_regions(out["mask"], out["conf"], **region_kwargs)`: the predict outputs
-        unchanged, plus "labels", "regions", "count" and the cleaned class map under "mask_clean"."""
+        unchanged, plus "labels", "regions", "count" and the cleaned class map under "mask_clean". With `outlines=True` also
+        "outlines" = `outlines.region_outlines(out["labels"])` with the connectivity the regions were labelled with, and
+        out["regions"]["perimeter"], the crack length of each region over all of its rings."""
         out = dict(self.predict(scene, return_prob=return_prob))
         H, W = out["mask"].shape
         max_regions = region_kwargs.get("max_regions", DEFAULT_MAX_REGIONS)
@@ -292,7 +294,19 @@ class ScenePredictor:
             self._regions[key] = RegionScratch(H, W, out["mask"].device, max_regions)
         reg = label_regions(out["mask"], out["conf"], scratch=self._regions.get(key), **region_kwargs)
         out.update(labels=reg["labels"], regions=reg["regions"], count=reg["count"], mask_clean=reg["mask"])
+        if outlines:
+            self._trace(out, region_kwargs.get("connectivity", 8))
         return out
+
+    def _trace(self, out: dict, connectivity: int) -> None:
+        from .outlines import OutlineScratch, perimeters, region_outlines
+        H, W = out["labels"].shape
+        cache = self.__dict__.setdefault("_outlines", {})
+        key = (H, W, out["labels"].device)
+        if key not in cache:
+            cache[key] = OutlineScratch(H, W, out["labels"].device)
+        out["outlines"] = region_outlines(out["labels"], connectivity=connectivity, scratch=cache[key])
+        out["regions"]["perimeter"] = perimeters(out["outlines"]["rings"], out["regions"]["id"])
 
     def evaluate(self, scene, gt_mask, *, iou_threshold: float = 0.5, gt_min_area: int = 1, max_pairs: int = DEFAULT_MAX_PAIRS,
                  boundary_distance: Optional[int] = None, **region_kwargs) -> dict:
@@ -337,7 +351,7 @@ def predict_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw
 
 def detect_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw) -> dict:
     """One-shot ScenePredictor(model, ...).detect(scene, return_prob, ...): tile / overlap / batch / num_classes / tta go to
-    the predictor, every other keyword to `label_regions`."""
+    the predictor, `outlines` to `detect`, every other keyword to `label_regions`."""
     pred_kw = {k: kw.pop(k) for k in ("tile", "overlap", "batch", "num_classes", "tta") if k in kw}
     return ScenePredictor(model, **pred_kw).detect(scene, return_prob=return_prob, **kw)
 
