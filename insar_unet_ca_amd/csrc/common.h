@@ -152,6 +152,13 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// XCD-aware tile order: work-groups that share an XCD (id % 8) get consecutive tiles, so that the operand rows / halo rows
+// neighbouring tiles share hit in that XCD's L2. Bijective remap of work-group id bid of nwg onto tile indices.
+__device__ __forceinline__ int xcd_tile(int bid, int nwg) {
+  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+
 // ---- per-device one-time launch setup --------------------------------------------------------
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of the loaded code object: the flag that
 // remembers "already set" is kept per device (a std::atomic bitmask, one bit per ordinal; devices >= 64 simply set

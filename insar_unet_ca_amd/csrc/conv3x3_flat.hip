@@ -17,7 +17,7 @@
 //     rows): the three dx taps still share one staged A tile, no halo pixel is computed, and the tile count is the per-tap
 //     kernel's (M / 256: exactly one round of work-groups where that kernel has one) — the flat geometry's 254-pixel step
 //     gives 275 / 292 tiles where 256 fit, and loses there to tile quantisation what it wins on operand traffic.
-#include "common.h"
+#include "conv_epilogue.h"
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
@@ -99,6 +99,7 @@ __global__ __launch_bounds__(FL_THREADS, 2) void conv3x3_flat_kernel(FlatArgs a)
   using Cfg = FlatCfg<T, BN, GEO>;
   constexpr int ES = Cfg::ES, BKe = Cfg::BKe, CH = Chunk<T>::N;
   constexpr int NT = BN / 32, MT = 4;
+  constexpr int CPR = BN * ES / 16;                        // 16-byte chunks per row of the epilogue tile
   constexpr int AD = Cfg::A_DMA, BD = Cfg::B_DMA;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   long long* rowOut = (long long*)(smem + Cfg::MAIN);
@@ -111,16 +112,15 @@ __global__ __launch_bounds__(FL_THREADS, 2) void conv3x3_flat_kernel(FlatArgs a)
   // persistent work-groups with one N tile: the BatchNorm partial sums of all of a work-group's tiles are carried in
   // registers (a thread owns the same channel chunk in every tile) and folded ONCE, into row blockIdx.x of the slab:
   // gridDim.x rows instead of one per tile (no pre-fold launch before bn_finalize), no per-tile fold and barrier
-  constexpr int CHc = Chunk<T>::N;
-  float cs1[CHc], cs2[CHc];
+  float cs1[CH], cs2[CH];
 #pragma unroll
-  for (int j = 0; j < CHc; ++j) { cs1[j] = 0.f; cs2[j] = 0.f; }
+  for (int j = 0; j < CH; ++j) { cs1[j] = 0.f; cs2[j] = 0.f; }
   // LDS_CARRY only: 16-byte slot q of thread t at [q][t] (consecutive lanes, consecutive slots: no bank conflict)
   float4* carry = (float4*)(smem + Cfg::MAIN + Cfg::ROWINFO + Cfg::STATB) + threadIdx.x;
   constexpr int CST = FL_THREADS;      // stride between a thread's slots
   if constexpr (Cfg::LDS_CARRY) {
 #pragma unroll
-    for (int j = 0; j < 2 * CHc / 4; ++j) carry[j * CST] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int j = 0; j < 2 * CH / 4; ++j) carry[j * CST] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
 #ifdef INSAR_STAMPS
   unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // wave-uniform (scalar registers)
@@ -128,12 +128,7 @@ __global__ __launch_bounds__(FL_THREADS, 2) void conv3x3_flat_kernel(FlatArgs a)
 #endif
   for (int vb = blockIdx.x; vb < a.total_tiles; vb += gridDim.x) {
   FL_STAMP(7);          // loop turn-around (+ kernel start for the first tile)
-  int t;
-  {
-    const int nwg = a.total_tiles, bid = vb;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int t = xcd_tile(vb, a.total_tiles);
   const int mtile = t / a.num_ntiles, ntile = t - mtile * a.num_ntiles;
   const int n0 = ntile * BN;
   const int Wp = a.W + 2;
@@ -404,76 +399,13 @@ __global__ __launch_bounds__(FL_THREADS, 2) void conv3x3_flat_kernel(FlatArgs a)
   __syncthreads();
   FL_STAMP(4);          // K loop
 
-  // ---- epilogue (as igemm.hip): registers -> LDS tile -> 16-byte NHWC stores + BN partial sums ------
+  // ---- epilogue (conv_epilogue.h): registers -> LDS tile -> 16-byte NHWC stores + BN partial sums (BS: see igemm.hip) ------
   char* tile = smem;
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      const int row = wm * 64 + mt * 16 + r16;
-      const int col = wn * (BN / 2) + nt * 16 + kq * 4;
-      char* p = tile + row * Cfg::PITCH + col * ES;
-      if constexpr (ES == 2) {
-        uint2 v;
-        v.x = pack2_bf16(acc[nt][mt][0], acc[nt][mt][1]);
-        v.y = pack2_bf16(acc[nt][mt][2], acc[nt][mt][3]);
-        *(uint2*)p = v;
-      } else {
-        *(f32x4_t*)p = acc[nt][mt];
-      }
-    }
+  acc_to_tile<ES, Cfg::PITCH>(tile, acc, wm * 64, wn * (BN / 2), r16, kq);
   __syncthreads();
 
-  constexpr int CPR = BN * ES / 16;
-  constexpr int ITER = FL_BM * CPR / FL_THREADS;
-  constexpr int RSTEP = FL_THREADS / CPR;
-  const int cc = tid % CPR;
-  const long long col_off = n0 + cc * CH;
   float s1[CH], s2[CH];
-#pragma unroll
-  for (int j = 0; j < CH; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
-  // BS (see igemm.hip): the consumer unit's y at the output's positions, half of this thread's chunks requested at a time
-  float bsc[BS ? CH : 1], bsh[BS ? CH : 1];
-  if constexpr (BS) {
-#pragma unroll
-    for (int j = 0; j < CH; ++j) { bsc[j] = a.bscale[col_off + j]; bsh[j] = a.bshift[col_off + j]; }
-  }
-  constexpr int HALF = ITER / 2;
-  static_assert(ITER % 2 == 0, "epilogue chunk batches");
-#pragma unroll
-  for (int i0 = 0; i0 < ITER; i0 += HALF) {
-    uint4 yv[BS ? HALF : 1];
-    if constexpr (BS) {
-#pragma unroll
-      for (int i = 0; i < HALF; ++i) {
-        const long long ro = rowOut[(i0 + i) * RSTEP + tid / CPR];
-        yv[i] = ro >= 0 ? *(const uint4*)(a.by + (ro + col_off) * ES) : make_uint4(0u, 0u, 0u, 0u);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < HALF; ++i) {
-      const int row = (i0 + i) * RSTEP + tid / CPR;
-      const long long ro = rowOut[row];
-      if (ro >= 0) {
-        const uint4 u = *(const uint4*)(tile + row * Cfg::PITCH + cc * 16);
-        float f[CH];
-        Chunk<T>::unpack(u, f);
-        if constexpr (BS) {
-          float yy[CH];
-          Chunk<T>::unpack(yv[i], yy);
-#pragma unroll
-          for (int j = 0; j < CH; ++j) {
-            const float m = fmaf(yy[j], bsc[j], bsh[j]) > 0.f ? f[j] : 0.f;
-            s1[j] += m; s2[j] = fmaf(m, yy[j], s2[j]);
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < CH; ++j) { s1[j] += f[j]; s2[j] = fmaf(f[j], f[j], s2[j]); }
-        }
-        *(uint4*)(a.y + (ro + col_off) * ES) = u;
-      }
-    }
-  }
+  store_tile_rows<T, BN, BS, FL_THREADS, FL_BM, Cfg::PITCH>(tile, rowOut, a.y, n0, tid, a.by, a.bscale, a.bshift, s1, s2);
   if (GEO == 0 && a.stats && a.carry) {            // (row tiles never carry: one slab row per tile)
     if constexpr (Cfg::LDS_CARRY) {
       // same sums in the same order as the register carry: slot j of the thread += this tile's sum
@@ -489,39 +421,13 @@ __global__ __launch_bounds__(FL_THREADS, 2) void conv3x3_flat_kernel(FlatArgs a)
       for (int j = 0; j < CH; ++j) { cs1[j] += s1[j]; cs2[j] += s2[j]; }
     }
   } else if (a.stats) {
-#pragma unroll
-    for (int j = 0; j < CH; ++j) {
-#pragma unroll
-      for (int o = CPR; o < 64; o <<= 1) { s1[j] += __shfl_xor(s1[j], o, 64); s2[j] += __shfl_xor(s2[j], o, 64); }
-    }
-#pragma unroll
-    for (int j = 0; j < CH; ++j) { LDS_PIN(s1[j]); LDS_PIN(s2[j]); }
-    if (lane < CPR) {
-#pragma unroll
-      for (int j = 0; j < CH; ++j) {
-        sstat[(wave * BN + lane * CH + j) * 2 + 0] = s1[j];
-        sstat[(wave * BN + lane * CH + j) * 2 + 1] = s2[j];
-      }
-    }
-    LDS_DRAIN();
-#pragma unroll
-    for (int j = 0; j < CH; ++j) { LDS_KEEP(s1[j]); LDS_KEEP(s2[j]); }
-    __syncthreads();
-    if (tid < BN) {
-      float v1 = 0.f, v2 = 0.f;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) { v1 += sstat[(w * BN + tid) * 2 + 0]; v2 += sstat[(w * BN + tid) * 2 + 1]; }
-      a.stats[((long long)mtile * 2 + 0) * a.N + n0 + tid] = v1;
-      a.stats[((long long)mtile * 2 + 1) * a.N + n0 + tid] = v2;
-    }
+    fold_tile_stats<BN, CH, CPR, 8>(s1, s2, sstat, a.stats, mtile, a.N, n0, tid, lane, wave);
   }
   FL_STAMP(5);          // epilogue: transpose through LDS, stores, statistics
   __syncthreads();          // the next tile's LDS-DMA rewrites the ring the epilogue tile aliases
   FL_STAMP(6);          // the other waves' epilogues
   }
   if (GEO == 0 && a.stats && a.carry) {
-    constexpr int CPR = BN * ES / 16;
-    constexpr int CH = CHc;
     if constexpr (Cfg::LDS_CARRY) {
 #pragma unroll
       for (int q = 0; q < CH / 4; ++q) {
@@ -530,26 +436,7 @@ __global__ __launch_bounds__(FL_THREADS, 2) void conv3x3_flat_kernel(FlatArgs a)
         cs2[4 * q] = c2v.x; cs2[4 * q + 1] = c2v.y; cs2[4 * q + 2] = c2v.z; cs2[4 * q + 3] = c2v.w;
       }
     }
-#pragma unroll
-    for (int j = 0; j < CH; ++j) {
-#pragma unroll
-      for (int o = CPR; o < 64; o <<= 1) { cs1[j] += __shfl_xor(cs1[j], o, 64); cs2[j] += __shfl_xor(cs2[j], o, 64); }
-    }
-    if (lane < CPR) {
-#pragma unroll
-      for (int j = 0; j < CH; ++j) {
-        sstat[(wave * BN + lane * CH + j) * 2 + 0] = cs1[j];
-        sstat[(wave * BN + lane * CH + j) * 2 + 1] = cs2[j];
-      }
-    }
-    __syncthreads();
-    if (tid < BN) {
-      float v1 = 0.f, v2 = 0.f;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) { v1 += sstat[(w * BN + tid) * 2 + 0]; v2 += sstat[(w * BN + tid) * 2 + 1]; }
-      a.stats[((long long)blockIdx.x * 2 + 0) * a.N + tid] = v1;       // one N tile: n0 = 0
-      a.stats[((long long)blockIdx.x * 2 + 1) * a.N + tid] = v2;
-    }
+    fold_tile_stats<BN, CH, CPR, 8>(cs1, cs2, sstat, a.stats, blockIdx.x, a.N, 0, tid, lane, wave);      // one N tile: n0 = 0
   }
 #ifdef INSAR_STAMPS
   if (tid == 0) {

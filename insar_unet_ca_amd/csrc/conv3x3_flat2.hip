@@ -22,7 +22,7 @@
 //
 // Results: the K loop adds the same products in channel order 32 by 32 instead of 64 by 64 per tap — equal to the 8-wave
 // kernel up to fp32 summation order (tests/test_parity_gpu.py: both against the float64 oracle; bit-reproducible run to run).
-#include "common.h"
+#include "conv_epilogue.h"
 #include "flat_args.h"
 #include <type_traits>
 
@@ -93,6 +93,7 @@ template <int BN, bool BS, int GEO>
 __global__ __launch_bounds__(F2_THREADS, F2_WGS(BN)) void conv3x3_flat2_kernel(FlatArgs a) {
   using Cfg = Flat2Cfg<BN, GEO>;
   constexpr int CH = 8, NT = 4;
+  constexpr int CPR = BN * 2 / 16;                        // 16-byte chunks per row of the epilogue tile
   constexpr int WGM = BN == 128 ? 2 : 4;                  // waves along the pixel dimension
   constexpr int WROWS = F2_BM / WGM, MT = WROWS / 16;     // 128 x 64 (8 x 4 MFMA tiles) / 64 x 64 (4 x 4) per wave
   constexpr int AD = Cfg::AD, BD = Cfg::BD;
@@ -149,12 +150,7 @@ __global__ __launch_bounds__(F2_THREADS, F2_WGS(BN)) void conv3x3_flat2_kernel(F
 #endif
   for (int vb = blockIdx.x; vb < a.total_tiles; vb += gridDim.x) {
     F2_STAMP(7);
-    int t;
-    {
-      const int nwg = a.total_tiles, bid = vb;
-      const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-      t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int t = xcd_tile(vb, a.total_tiles);
     const int mtile = t / a.num_ntiles, ntile = t - mtile * a.num_ntiles;
     const int n0 = ntile * BN;
     const int q0 = mtile * F2_STEP - 1;                                 // flat: tile row r <-> padded pixel q0 + r (P < 2^31: host)
@@ -293,121 +289,24 @@ __global__ __launch_bounds__(F2_THREADS, F2_WGS(BN)) void conv3x3_flat2_kernel(F
     __syncthreads();
     F2_STAMP(4);          // K loop
 
-    // ---- epilogue (as conv3x3_flat.hip): registers -> LDS tile -> 16-byte NHWC stores + BN partial sums ------
+    // ---- epilogue (conv_epilogue.h): registers -> LDS tile -> 16-byte NHWC stores + BN partial sums ------
     char* tile = smem;
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-        const int row = wm * WROWS + mt * 16 + r16;
-        const int col = wn * 64 + nt * 16 + kq * 4;
-        uint2 v;
-        v.x = pack2_bf16(acc[nt][mt][0], acc[nt][mt][1]);
-        v.y = pack2_bf16(acc[nt][mt][2], acc[nt][mt][3]);
-        *(uint2*)(tile + row * Cfg::PITCH + col * 2) = v;
-      }
+    acc_to_tile<2, Cfg::PITCH>(tile, acc, wm * WROWS, wn * 64, r16, kq);
     __syncthreads();
 
-    constexpr int CPR = BN * 2 / 16;
-    constexpr int ITER = F2_BM * CPR / F2_THREADS;
-    constexpr int RSTEP = F2_THREADS / CPR;
-    const int cc = tid % CPR;
-    const long long col_off = n0 + cc * CH;
     float s1[CH], s2[CH];
-#pragma unroll
-    for (int j = 0; j < CH; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
-    float bsc[BS ? CH : 1], bsh[BS ? CH : 1];
-    if constexpr (BS) {
-#pragma unroll
-      for (int j = 0; j < CH; ++j) { bsc[j] = a.bscale[col_off + j]; bsh[j] = a.bshift[col_off + j]; }
-    }
-    constexpr int HALF = ITER / 2;
-#pragma unroll
-    for (int i0 = 0; i0 < ITER; i0 += HALF) {
-      uint4 yv[BS ? HALF : 1];
-      if constexpr (BS) {
-#pragma unroll
-        for (int i = 0; i < HALF; ++i) {
-          const long long ro = rowOut[(i0 + i) * RSTEP + tid / CPR];
-          yv[i] = ro >= 0 ? *(const uint4*)(a.by + (ro + col_off) * 2) : make_uint4(0u, 0u, 0u, 0u);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < HALF; ++i) {
-        const int row = (i0 + i) * RSTEP + tid / CPR;
-        const long long ro = rowOut[row];
-        if (ro >= 0) {
-          const uint4 u = *(const uint4*)(tile + row * Cfg::PITCH + cc * 16);
-          float f[CH];
-          Chunk<bf16_t>::unpack(u, f);
-          if constexpr (BS) {
-            float yy[CH];
-            Chunk<bf16_t>::unpack(yv[i], yy);
-#pragma unroll
-            for (int j = 0; j < CH; ++j) {
-              const float m = fmaf(yy[j], bsc[j], bsh[j]) > 0.f ? f[j] : 0.f;
-              s1[j] += m; s2[j] = fmaf(m, yy[j], s2[j]);
-            }
-          } else {
-#pragma unroll
-            for (int j = 0; j < CH; ++j) { s1[j] += f[j]; s2[j] = fmaf(f[j], f[j], s2[j]); }
-          }
-          *(uint4*)(a.y + (ro + col_off) * 2) = u;
-        }
-      }
-    }
+    store_tile_rows<bf16_t, BN, BS, F2_THREADS, F2_BM, Cfg::PITCH>(tile, rowOut, a.y, n0, tid, a.by, a.bscale, a.bshift, s1, s2);
     if (a.stats && a.carry) {
 #pragma unroll
       for (int j = 0; j < CH; ++j) { cs1[j] += s1[j]; cs2[j] += s2[j]; }
     } else if (a.stats) {
-#pragma unroll
-      for (int j = 0; j < CH; ++j) {
-#pragma unroll
-        for (int o = CPR; o < 64; o <<= 1) { s1[j] += __shfl_xor(s1[j], o, 64); s2[j] += __shfl_xor(s2[j], o, 64); }
-      }
-      if (lane < CPR) {
-#pragma unroll
-        for (int j = 0; j < CH; ++j) {
-          sstat[(wave * BN + lane * CH + j) * 2 + 0] = s1[j];
-          sstat[(wave * BN + lane * CH + j) * 2 + 1] = s2[j];
-        }
-      }
-      __syncthreads();
-      if (tid < BN) {
-        float v1 = 0.f, v2 = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) { v1 += sstat[(w * BN + tid) * 2 + 0]; v2 += sstat[(w * BN + tid) * 2 + 1]; }
-        a.stats[((long long)mtile * 2 + 0) * a.N + n0 + tid] = v1;
-        a.stats[((long long)mtile * 2 + 1) * a.N + n0 + tid] = v2;
-      }
+      fold_tile_stats<BN, CH, CPR, 4>(s1, s2, sstat, a.stats, mtile, a.N, n0, tid, lane, wave);
     }
     F2_STAMP(5);          // epilogue: transpose through LDS, stores, statistics
     __syncthreads();      // the next tile's LDS-DMA rewrites the ring the epilogue tile aliases
     F2_STAMP(6);          // the other waves' epilogues
   }
-  if (a.stats && a.carry) {
-    constexpr int CPR = BN * 2 / 16;
-#pragma unroll
-    for (int j = 0; j < CH; ++j) {
-#pragma unroll
-      for (int o = CPR; o < 64; o <<= 1) { cs1[j] += __shfl_xor(cs1[j], o, 64); cs2[j] += __shfl_xor(cs2[j], o, 64); }
-    }
-    if (lane < CPR) {
-#pragma unroll
-      for (int j = 0; j < CH; ++j) {
-        sstat[(wave * BN + lane * CH + j) * 2 + 0] = cs1[j];
-        sstat[(wave * BN + lane * CH + j) * 2 + 1] = cs2[j];
-      }
-    }
-    __syncthreads();
-    if (tid < BN) {
-      float v1 = 0.f, v2 = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) { v1 += sstat[(w * BN + tid) * 2 + 0]; v2 += sstat[(w * BN + tid) * 2 + 1]; }
-      a.stats[((long long)blockIdx.x * 2 + 0) * a.N + tid] = v1;       // one N tile: n0 = 0
-      a.stats[((long long)blockIdx.x * 2 + 1) * a.N + tid] = v2;
-    }
-  }
+  if (a.stats && a.carry) fold_tile_stats<BN, CH, CPR, 4>(cs1, cs2, sstat, a.stats, blockIdx.x, a.N, 0, tid, lane, wave);      // one N tile: n0 = 0
 #ifdef INSAR_STAMPS
   if (tid == 0) {
 #pragma unroll

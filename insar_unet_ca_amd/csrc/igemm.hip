@@ -19,7 +19,7 @@
 //    BatchNorm needs (:82,85) are taken from the *stored* values on the way out (one slab row per
 //    M tile, no atomics).
 //  * bf16: v_mfma_f32_16x16x32_bf16 (fp32 accumulate); fp32: v_mfma_f32_16x16x4_f32 (exact fp32).
-#include "common.h"
+#include "conv_epilogue.h"
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
@@ -136,14 +136,7 @@ __global__ __launch_bounds__(2 * BM, (BN >= 256 ? 1 : 2)) void igemm_kernel(Igem
   unsigned long long stamp_prev = __builtin_amdgcn_s_memtime();
   const unsigned long long stamp_t0 = stamp_prev, stamp_r0 = __builtin_amdgcn_s_memrealtime();   // [6] / [7]: shader clock vs 100 MHz
 #endif
-  // XCD-aware tile order: blocks that share an XCD (blockIdx % 8) get consecutive tiles, so the
-  // A rows / halo rows shared by neighbouring tiles hit in that XCD's L2 (bijective remap).
-  int t;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int t = xcd_tile(blockIdx.x, gridDim.x);      // XCD-aware tile order (common.h)
   const int mtile = t / a.num_ntiles, ntile = t - mtile * a.num_ntiles;
   const long long m0 = (long long)mtile * BM;
   const int n0 = ntile * BN;
@@ -382,24 +375,9 @@ __global__ __launch_bounds__(2 * BM, (BN >= 256 ? 1 : 2)) void igemm_kernel(Igem
   __syncthreads();
   IG_STAMP(2);          // K loop
 
-  // ---- epilogue: registers -> LDS tile [pixel][channel] -> 16-byte NHWC stores (+stats) ----------
+  // ---- epilogue (conv_epilogue.h): registers -> LDS tile [pixel][channel] -> 16-byte NHWC stores (+stats) ----------
   char* tile = smem;
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      const int row = wm * 64 + mt * 16 + r16;
-      const int col = wn * (BN / 2) + nt * 16 + kq * 4;
-      char* p = tile + row * Cfg::PITCH + col * ES;
-      if constexpr (ES == 2) {
-        uint2 v;
-        v.x = pack2_bf16(acc[nt][mt][0], acc[nt][mt][1]);
-        v.y = pack2_bf16(acc[nt][mt][2], acc[nt][mt][3]);
-        *(uint2*)p = v;
-      } else {
-        *(f32x4_t*)p = acc[nt][mt];
-      }
-    }
+  acc_to_tile<ES, Cfg::PITCH>(tile, acc, wm * 64, wn * (BN / 2), r16, kq);
   __syncthreads();
 
   IG_STAMP(3);          // accumulators -> LDS tile
@@ -441,10 +419,7 @@ __global__ __launch_bounds__(2 * BM, (BN >= 256 ? 1 : 2)) void igemm_kernel(Igem
     if (ro >= 0) {
       float f[CH];
       Chunk<T>::unpack(*(const uint4*)(tile + row * Cfg::PITCH + cc * 16), f);
-      if constexpr (!BS) {
-#pragma unroll
-        for (int j = 0; j < CH; ++j) { s1[j] += f[j]; s2[j] = fmaf(f[j], f[j], s2[j]); }
-      }
+      if constexpr (!BS) sum_step<CH>(f, s1, s2);
 #pragma unroll
       for (int j = 0; j < CH; ++j) f[j] += bias[j];
       if (a.add) {
@@ -467,42 +442,12 @@ __global__ __launch_bounds__(2 * BM, (BN >= 256 ? 1 : 2)) void igemm_kernel(Igem
         float yy[CH], fr[CH];
         Chunk<T>::unpack(yv[i], yy);
         Chunk<T>::unpack(pk, fr);
-#pragma unroll
-        for (int j = 0; j < CH; ++j) {
-          const float m = fmaf(yy[j], bsc[j], bsh[j]) > 0.f ? fr[j] : 0.f;
-          s1[j] += m; s2[j] = fmaf(m, yy[j], s2[j]);
-        }
+        bstat_sum_step<CH>(fr, yy, bsc, bsh, s1, s2);
       }
     }
   }
   IG_STAMP(4);          // stores (+ sums)
-  if (a.stats) {
-#pragma unroll
-    for (int j = 0; j < CH; ++j) {
-#pragma unroll
-      for (int o = CPR; o < 64; o <<= 1) { s1[j] += __shfl_xor(s1[j], o, 64); s2[j] += __shfl_xor(s2[j], o, 64); }
-    }
-#pragma unroll
-    for (int j = 0; j < CH; ++j) { LDS_PIN(s1[j]); LDS_PIN(s2[j]); }
-    if (lane < CPR) {
-#pragma unroll
-      for (int j = 0; j < CH; ++j) {
-        sstat[(wave * BN + lane * CH + j) * 2 + 0] = s1[j];
-        sstat[(wave * BN + lane * CH + j) * 2 + 1] = s2[j];
-      }
-    }
-    LDS_DRAIN();               // see common.h: keep the store's source registers intact until it has drained
-#pragma unroll
-    for (int j = 0; j < CH; ++j) { LDS_KEEP(s1[j]); LDS_KEEP(s2[j]); }
-    __syncthreads();
-    if (tid < BN) {
-      float v1 = 0.f, v2 = 0.f;
-#pragma unroll
-      for (int w = 0; w < NWAVES; ++w) { v1 += sstat[(w * BN + tid) * 2 + 0]; v2 += sstat[(w * BN + tid) * 2 + 1]; }
-      a.stats[((long long)mtile * 2 + 0) * a.N + n0 + tid] = v1;
-      a.stats[((long long)mtile * 2 + 1) * a.N + n0 + tid] = v2;
-    }
-  }
+  if (a.stats) fold_tile_stats<BN, CH, CPR, NWAVES>(s1, s2, sstat, a.stats, mtile, a.N, n0, tid, lane, wave);
 #ifdef INSAR_STAMPS
   IG_STAMP(5);          // statistics fold
   stamp_acc[6] = stamp_prev - stamp_t0; stamp_acc[7] = __builtin_amdgcn_s_memrealtime() - stamp_r0;

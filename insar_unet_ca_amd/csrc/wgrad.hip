@@ -71,12 +71,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 2 : 1)) void wgrad_kernel(Wgrad
   int* soff = (int*)(smem + 2 * Cfg::STAGE);   // [0..11] offx, [12..23] offdy
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int t;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  int t = xcd_tile(blockIdx.x, gridDim.x);
   const int tap = t % a.ntaps; t /= a.ntaps;
   const int ni = t % a.ntc; t /= a.ntc;
   const int mi = t % a.mtc; t /= a.mtc;

@@ -62,12 +62,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 2 : 1)) void wgrad3_kernel(Wgra
   unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long stamp_prev = __builtin_amdgcn_s_memtime();
 #endif
-  int t;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  int t = xcd_tile(blockIdx.x, gridDim.x);
   const int ty = t % 3; t /= 3;
   const int ni = t % a.ntc; t /= a.ntc;
   const int mi = t % a.mtc; t /= a.mtc;

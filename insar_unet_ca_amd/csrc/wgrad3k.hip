@@ -54,12 +54,7 @@ __global__ __launch_bounds__(512) void wgrad3k_kernel(Wgrad3kArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int grp = wave >> 2;                                          // 0: waves 0-3, 1: waves 4-7 (SIMD partners)
-  int t;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  int t = xcd_tile(blockIdx.x, gridDim.x);
   const int ty = t % 3; t /= 3;
   const int ni = t % a.ntc; t /= a.ntc;
   const int mi = t % a.mtc; t /= a.mtc;

@@ -62,12 +62,7 @@ __global__ __launch_bounds__(256, 2) void wgrad3y_kernel(Wgrad3Args a) {
   unsigned long long stamp_prev = __builtin_amdgcn_s_memtime();
   const unsigned long long stamp_t0 = stamp_prev, stamp_r0 = __builtin_amdgcn_s_memrealtime();   // [6] / [7]: shader clock vs 100 MHz
 #endif
-  int t;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  int t = xcd_tile(blockIdx.x, gridDim.x);
   const int ty = t % 3; t /= 3;
   const int ni = t % a.ntc; t /= a.ntc;
   const int mi = t % a.mtc; t /= a.mtc;
