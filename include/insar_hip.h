@@ -739,6 +739,57 @@ int insar_dist_transform(const void* m, int32_t elem_type, int32_t B, int32_t H,
 int insar_dist_boundary_counts(const uint8_t* pred, const uint8_t* gt, const int32_t* d2_pred, const int32_t* d2_gt, int32_t H,
                                int32_t W, int64_t r2, int32_t K, int32_t void_value, int64_t* counts, void* stream);
 
+/* ---- centre lines (build-side addition; the reference has no post-processing): csrc/skeleton.hip ---------------------------
+ * labels int32 [H][W] (row-major, 1 <= H, W <= 32767): a value <= 0 is background, equal positive values form one region.
+ * Thinning: Guo and Hall's two-subiteration parallel thinning (CACM 32(3), 1989) per region. A neighbour of p is SET iff it is
+ * inside the image, still alive and carries p's label. With p2 = N, p3 = NE, p4 = E, p5 = SE, p6 = S, p7 = SW, p8 = W, p9 = NW:
+ *   C = (!p2 & (p3|p4)) + (!p4 & (p5|p6)) + (!p6 & (p7|p8)) + (!p8 & (p9|p2))
+ *   N = min((p9|p2) + (p3|p4) + (p5|p6) + (p7|p8), (p2|p3) + (p4|p5) + (p6|p7) + (p8|p9))
+ *   m = (p6 | p7 | !p9) & p8 in the first sub-iteration, (p2 | p3 | !p5) & p4 in the second
+ *   p is deleted iff it is alive and C == 1 and 2 <= N <= 3 and !m, every pixel decided from the image before the sub-iteration.
+ * One iteration = first then second sub-iteration; max_iterations (1..32768) of them run; an iteration that deletes nothing
+ * leaves a fixed point. Kind of a skeleton pixel on the final image, X = the number of k with p_k unset and p_{k+1} set going
+ * cyclically round p2..p9: X = 0 isolated (1), 1 end (2), 2 line (3), >= 3 junction (4); 0 = not skeleton.
+ *   skeleton: uint8 [H][W], the kinds.
+ *   table:    InsarSkeletonStat [1 + max_regions], 16-byte aligned; record l belongs to label l. Record 0 is the header:
+ *             n = iterations (those that deleted a pixel), n_end = converged (iterations < max_iterations), n_junction = the
+ *             largest label in the map, n_orth = 1 iff a label above max_regions occurs. Pixels of such labels are thinned and
+ *             classified like any other and enter no record; no kernel uses them as an index.
+ *   d2:       nullable; int32 [H][W], the INSAR_DIST_EDGE transform of `labels` (no ignored value). Skeleton pixels with
+ *             d2 == INSAR_DIST_FAR count into n_far and neither into sum_d2 nor max_d2; without d2 the three stay 0.
+ *   scratch:  insar_skeleton_scratch_bytes(...) bytes, 16-byte aligned: ten bit planes of H * ceil(W / 64) 64-bit words (eight
+ *             same-label link planes, the alive map twice), the tiles' change flags and max_iterations iteration flags. Nothing
+ *             in it has to survive between calls or be cleared by the caller.
+ * Call planes, then step for step = 0 .. ceil(max_iterations / 8) - 1, then stats, on one stream with the same H, W,
+ * max_iterations: ONE launch per call, 2 + ceil(max_iterations / 8) in all whatever the map holds, no read-back, no
+ * synchronisation, no work-group waits on another, integers only (bitwise reproducible). Every argument is checked before the
+ * device is touched. */
+typedef struct InsarSkeletonStat {
+  int64_t sum_y, sum_x;            /* over the region's skeleton pixels (y down, x to the right) */
+  int64_t sum_yy, sum_xx, sum_xy;
+  int64_t sum_d2;                  /* over those whose d2 is not FAR */
+  int32_t n, n_end, n_junction;    /* skeleton pixels; of kind end; of kind junction (header: iterations, converged, largest label) */
+  int32_t n_orth;                  /* 4-adjacent pairs of skeleton pixels of the region, each once (header: overflow flag) */
+  int32_t n_diag;                  /* diagonal pairs neither of whose two common 4-neighbours is a skeleton pixel of the region */
+  int32_t n_far;                   /* skeleton pixels whose d2 is FAR */
+  int32_t max_d2;                  /* the largest d2 that is not FAR */
+  int32_t _pad;
+} InsarSkeletonStat;
+/* host only: bytes of scratch for an H x W map and max_iterations, and of a table of max_regions records */
+int insar_skeleton_scratch_bytes(int32_t H, int32_t W, int32_t max_iterations, int32_t max_regions, int64_t* scratch_bytes,
+                                 int64_t* table_bytes);
+/* host only: the launches of one thinning: 2 + ceil(max_iterations / 8), plus the 2 of insar_dist_transform with `widths` */
+int insar_skeleton_launches(int32_t H, int32_t W, int32_t max_iterations, int32_t widths);
+/* 1 launch: the bit planes from the labels; the table and the iteration flags cleared. */
+int insar_skeleton_planes(const int32_t* labels, int32_t H, int32_t W, int32_t max_iterations, int32_t max_regions, void* scratch,
+                          void* table, void* stream);
+/* 1 launch: iterations 8 step .. min(8 step + 8, max_iterations) - 1, one 96 x 384 pixel tile per work-group with a halo of 16
+ * pixels in LDS; the alive map goes from one of its two copies to the other, written whole. */
+int insar_skeleton_step(int32_t H, int32_t W, int32_t max_iterations, int32_t step, void* scratch, void* stream);
+/* 1 launch: the kinds, the records (runs of equal labels folded per wave, then agent-scope integer atomics) and the header. */
+int insar_skeleton_stats(const int32_t* labels, const int32_t* d2 /*nullable*/, int32_t H, int32_t W, int32_t max_iterations,
+                         int32_t max_regions, void* scratch, void* table, uint8_t* skeleton, void* stream);
+
 /* ---- augmentation and test-time augmentation (build-side addition; the reference resizes and normalises, nothing else):
  * csrc/augment.hip ------------------------------------------------------------------------------------------------------
  * A parameter table is a device array int32 [n][4], 16-byte aligned; row s = {int32 op, float gain, float bias, float sigma}

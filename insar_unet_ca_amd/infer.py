@@ -281,11 +281,14 @@ class ScenePredictor:
             self.model.train(was_training)
         return _finalize(acc, wsum, return_prob)
 
-    def detect(self, scene, return_prob: bool = False, outlines: bool = False, **region_kwargs) -> dict:
+    def detect(self, scene, return_prob: bool = False, outlines: bool = False, skeletons: bool = False,
+               max_iterations: int = 32, **region_kwargs) -> dict:
         """`predict(scene)` followed by `label_regions(out["mask"], out["conf"], **region_kwargs)`: the predict outputs
         unchanged, plus "labels", "regions", "count" and the cleaned class map under "mask_clean". With `outlines=True` also
         "outlines" = `outlines.region_outlines(out["labels"])` with the connectivity the regions were labelled with, and
-        out["regions"]["perimeter"], the crack length of each region over all of its rings."""
+        out["regions"]["perimeter"], the crack length of each region over all of its rings. With `skeletons=True` also
+        "skeleton" = the kinds map of `skeletons.thin_regions(out["labels"], max_iterations=max_iterations)`, "skeleton_converged",
+        and out["regions"]["length"], ["mean_width"], ["max_width"], ["orientation"], ["n_end"], ["n_junction"]."""
         out = dict(self.predict(scene, return_prob=return_prob))
         H, W = out["mask"].shape
         max_regions = region_kwargs.get("max_regions", DEFAULT_MAX_REGIONS)
@@ -296,7 +299,23 @@ class ScenePredictor:
         out.update(labels=reg["labels"], regions=reg["regions"], count=reg["count"], mask_clean=reg["mask"])
         if outlines:
             self._trace(out, region_kwargs.get("connectivity", 8))
+        if skeletons:
+            self._thin(out, max_iterations, max_regions)
         return out
+
+    def _thin(self, out: dict, max_iterations: int, max_regions: int) -> None:
+        from .skeletons import SkeletonScratch, thin_regions
+        H, W = out["labels"].shape
+        cache = self.__dict__.setdefault("_skeletons", {})
+        key = (H, W, out["labels"].device, max_iterations, max_regions)
+        if key not in cache and isinstance(max_iterations, int) and 1 <= max_iterations <= 32768:
+            cache[key] = SkeletonScratch(H, W, out["labels"].device, max_iterations, max_regions)
+        sk = thin_regions(out["labels"], max_iterations=max_iterations, max_regions=max_regions, scratch=cache.get(key))
+        out["skeleton"], out["skeleton_converged"] = sk["skeleton"], sk["converged"]
+        # region ids are labels: row id - 1 of the table; a kept region always has a pixel, hence a record
+        rows = np.asarray(out["regions"]["id"], dtype=np.int64) - 1
+        for f in ("length", "mean_width", "max_width", "orientation", "n_end", "n_junction"):
+            out["regions"][f] = sk["table"][f][rows]
 
     def _trace(self, out: dict, connectivity: int) -> None:
         from .outlines import OutlineScratch, perimeters, region_outlines
@@ -351,7 +370,7 @@ def predict_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw
 
 def detect_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw) -> dict:
     """One-shot ScenePredictor(model, ...).detect(scene, return_prob, ...): tile / overlap / batch / num_classes / tta go to
-    the predictor, `outlines` to `detect`, every other keyword to `label_regions`."""
+    the predictor, `outlines`, `skeletons` and `max_iterations` to `detect`, every other keyword to `label_regions`."""
     pred_kw = {k: kw.pop(k) for k in ("tile", "overlap", "batch", "num_classes", "tta") if k in kw}
     return ScenePredictor(model, **pred_kw).detect(scene, return_prob=return_prob, **kw)
 
