@@ -678,6 +678,48 @@ int insar_outline_rings(const int32_t* labels, int32_t H, int32_t W, int32_t n_e
 int insar_outline_write(int32_t H, int32_t W, int32_t n_edges, int32_t corners_only, int32_t max_rings, int32_t max_vertices,
                         int32_t max_edges, void* scratch, void* table, int32_t* vertices, void* stream);
 
+/* ---- polygon rasterisation (build-side addition; the reference reads ready-made masks): csrc/raster.hip ---------------------
+ * The inverse of the region outlines: an edge table becomes a label map `out` [H][W] (row-major; uint8 with INSAR_RASTER_U8,
+ * int32 with INSAR_RASTER_I32; H >= 1, 1 <= W <= 16384, H * W < 2^31) in exact integers, no floating point on the device.
+ *   fixed point: coordinates are int32 in units of 1/256 pixel, X = 256 x, Y = 256 y; (0, 0) is the top-left corner of pixel
+ *              (0, 0), the lattice of the region outlines; the centre of pixel (r, c) is (Y, X) = (256 r + 128, 256 c + 128).
+ *              Every coordinate lies within +-2^24 (the caller's promise: every product below then fits int64; coordinates
+ *              beyond it give an unspecified map, never an access outside the buffers). Vertices outside the scene are legal.
+ *   edges:     int32 [n_edges][5] = (X0, Y0, X1, Y1, value), 4-byte aligned. An edge with Y0 == Y1 is ignored. Its sign is
+ *              w = +1 when Y1 < Y0, else -1: a ring with the region on the right of its travel direction, as the exterior
+ *              rings of the region outlines run, has +1 on its left flank. The caller orients holes the other way.
+ *   crossing:  an edge crosses row r iff min(Y0, Y1) <= 256 r + 128 < max(Y0, Y1) (half-open: a vertex on a centre line counts
+ *              once). With the endpoints ordered so that Y0 < Y1 (both directions of a shared edge then agree), its intercept
+ *              is Xi = X0 + (X1 - X0) (256 r + 128 - Y0) / (Y1 - Y0), and it affects the columns c >= c0,
+ *              c0 = ceil((Xi - 128) / 256) = ceil(((X0 - 128) (Y1 - Y0) + (X1 - X0) (256 r + 128 - Y0)) / (256 (Y1 - Y0))),
+ *              one integer ceiling division, clamped to 0 .. W. The top-left rule: a centre exactly on a left flank is inside,
+ *              on a right flank outside; polygons that share an edge tile the plane with no gap and no double cover.
+ *   pixel:     over the crossings of its row with c0 <= c: cover = sum of w, vsum = sum of w * value (the caller keeps the sum of
+ *              |value| over the edges that cross any one row below 2^31, so no partial sum leaves int32).
+ *              (cover, vsum) == (0, 0): background, `fill`, or base[r][c] when `base` (same element type and shape, never
+ *              written) is given; cover == 1 with vsum representable in the element type and != overlap_value: vsum;
+ *              anything else: overlap_value (overlapping polygons, self-intersections, a hole outside its exterior).
+ *   overlap_pixels: int64 on the device, 8-byte aligned: the number of pixels decided by the last case.
+ *   scratch:   insar_raster_scratch_bytes(...) bytes, 16-byte aligned; nothing in it has to survive between calls or be cleared.
+ *              max_crossings (0 .. 2^30) is the capacity of the record array: at least the number of pairs (edge, row in [0, H))
+ *              that cross, which the caller counts exactly on the host. Records beyond it are dropped, never written.
+ * Rows are filled in bands of insar_raster_band_rows(W) rows, one work-group per band with two int32 LDS planes of W + 1 columns
+ * per row. 5 launches on the caller's stream whatever the table holds (clear, count, scan, emit, fill); no work-group waits on
+ * another, no read-back; integer sums only, so the map is bitwise reproducible although the order of a band's records is not.
+ * Four pixels per store (and per read of `base`) where W % 4 == 0 and the pointer is 4-byte (uint8) or 16-byte (int32) aligned,
+ * guarded scalars otherwise: misalignment is no error. Every argument is checked before the device is touched. */
+enum { INSAR_RASTER_U8 = 0, INSAR_RASTER_I32 = 1 };
+/* host only: the rows of a band at scene width W: a power of two, 1 .. 32, the largest whose planes fit 136 KiB of LDS */
+int insar_raster_band_rows(int32_t W);
+/* host only: the launches of one call: 5 */
+int insar_raster_launches(void);
+/* host only: bytes of scratch for an H x W scene with room for max_crossings records */
+int insar_raster_scratch_bytes(int32_t H, int32_t W, int64_t max_crossings, int64_t* scratch_bytes);
+/* 5 launches. edges may be null when n_edges == 0 (0 .. 2^28); base is nullable; fill and overlap_value lie in 0 .. 255 for uint8. */
+int insar_raster_polygons(const int32_t* edges, int32_t n_edges, int32_t H, int32_t W, int64_t max_crossings, int32_t elem_type,
+                          int32_t fill, int32_t overlap_value, const void* base /*nullable*/, void* out, void* scratch,
+                          int64_t* overlap_pixels, void* stream);
+
 /* ---- overlaps of two label maps (build-side addition; the reference scores pixels only): csrc/overlap.hip ----------------
  * pred, gt int32 [H][W] (row-major, H * W < 2^31): 0 or a region id >= 1, as insar_regions_relabel writes them. voidmap uint8
  * [H][W], nullable: a pixel is dropped iff voidmap is given and voidmap[i] == void_value (0..255). Every remaining pixel with

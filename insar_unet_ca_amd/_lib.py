@@ -21,6 +21,7 @@ AUG_MASK_NONE, AUG_MASK_U8, AUG_MASK_I64 = 0, 1, 2
 DIST_U8, DIST_I32 = 0, 1
 DIST_EQ, DIST_NE, DIST_EDGE = 0, 1, 2
 DIST_FAR = 0x7FFFFFFF
+RASTER_U8, RASTER_I32 = 0, 1
 IGEMM_OOB_ZERO = 1
 IGEMM_PINGPONG = 2
 
@@ -225,6 +226,10 @@ _SIGNATURES = {
     "insar_outline_rank": [_I, _I, _I, _I, _P, _P],
     "insar_outline_rings": [_P, _I, _I, _I, _I, _I, _P, _P, _P],
     "insar_outline_write": [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "insar_raster_band_rows": [_I],
+    "insar_raster_launches": [],
+    "insar_raster_scratch_bytes": [_I, _I, _L, _P],
+    "insar_raster_polygons": [_P, _I, _I, _I, _L, _I, _I, _I, _P, _P, _P, _P, _P],
     "insar_skeleton_scratch_bytes": [_I, _I, _I, _I, _P, _P],
     "insar_skeleton_launches": [_I, _I, _I, _I],
     "insar_skeleton_planes": [_P, _I, _I, _I, _I, _P, _P, _P],
@@ -308,7 +313,7 @@ def load():
 
 _COUNT_ONLY = {"insar_tune_get", "insar_igemm_num_mtiles", "insar_igemm_tile_rows", "insar_igemm_tile_cols", "insar_igemm_tile_cols_dt", "insar_wgrad_tile", "insar_wgrad_tile_pair", "insar_wgrad_conv3_tile", "insar_wgrad_conv3x_tile", "insar_wgrad_conv3y_tile", "insar_wgrad_conv3k_tile", "insar_wgrad_conv3k_slices", "insar_conv3x3_flat_ok", "insar_conv3x3_flat_rows_ok", "insar_conv3x3_flat2_rows_ok", "insar_conv3x3_flat_rows_dil_ok", "insar_conv3x3_flat_num_mtiles", "insar_conv3x3_flat_stat_rows", "insar_conv3x3_c64_ok", "insar_conv3x3_c64_rows", "insar_conv3x3_c64_geometry", "insar_conv3x3_small_wgrad_blocks", "insar_conv3x3_small_wgrad_fused_ok", "insar_conv3x3_small_fwd_rows", "insar_conv1x1_out_bwd_blocks",
                "insar_ce_blocks", "insar_conv7x7s2_fwd_rows", "insar_conv7x7s2_wgrad_blocks", "insar_outline_launches",
-               "insar_skeleton_launches"}
+               "insar_skeleton_launches", "insar_raster_launches", "insar_raster_band_rows"}
 
 
 _TAPE = None      # while a launch tape is being recorded (tape.py): the list every launch is appended to
