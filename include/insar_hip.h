@@ -749,6 +749,45 @@ int insar_overlap_count(const int32_t* pred, const int32_t* gt, const uint8_t* v
 /* 1 launch: the non-empty slots written to `out`, its header filled in. */
 int insar_overlap_compact(const void* table, int64_t max_pairs, void* out, void* stream);
 
+/* ---- statistics of a raster over the regions of a label map (build-side addition; the reference has no post-processing):
+ * csrc/zonal.hip ---------------------------------------------------------------------------------------------------------
+ * labels int32 [H][W] (row-major, H * W < 2^31): a value <= 0 is background, the labels 1..max_regions are measured, a pixel
+ * with a larger label is counted in the header and written nowhere. raster [channels][H][W], 1 <= channels <= 4, float32, uint8
+ * or int32 (INSAR_ZONAL_*). Per pixel of a measured label and per channel:
+ *   integer rasters: q = v. float32: d = (double)v * scale, clamped to +-(2^31 - 1); q = d rounded to nearest, ties to even. A
+ *   product outside the clamp makes the pixel CLIPPED: it takes part with the clamped q. scale is positive and finite.
+ *   A pixel is INVALID if it is not finite or (has_nodata) equals nodata in the raster's own type (float32: v == (float)nodata;
+ *   integers: nodata must be an integer in int32). Invalid pixels are counted and take no other part. NaN nodata is refused.
+ * Record l of channel c is InsarZonalStat number 1 + c * max_regions + (l - 1) of the table; record 0 is the header, whose
+ * sum_q is the number of pixels with a label above max_regions. With bins > 0 (<= 256) the histograms follow the records:
+ * uint32 [channels][max_regions][bins]; a valid pixel with q_lo <= q < q_hi goes to bin floor((q - q_lo) * bins / (q_hi - q_lo))
+ * (int64 arithmetic), q < q_lo adds to `below`, q >= q_hi to `above`; -2^31 <= q_lo < q_hi <= 2^31.
+ * Call clear, then accumulate, on one stream: one launch each whatever the map holds, no allocation, no read-back, no
+ * synchronisation, no work-group waits on another. Integer atomics only (agent scope, relaxed), after folding per thread, per
+ * wave run and, for the label a work-group sees most, per work-group in LDS: every field is independent of the order and the
+ * table is bitwise reproducible. Every argument is checked before the device is touched. */
+enum { INSAR_ZONAL_F32 = 0, INSAR_ZONAL_U8 = 1, INSAR_ZONAL_I32 = 2 };
+typedef struct InsarZonalStat {
+  int64_t sum_q;                     /*  0: sum of q over the valid pixels (header: pixels with a label above max_regions) */
+  uint64_t sumsq_lo;                 /*  8: sum of the low 32 bits of q^2 */
+  uint64_t sumsq_hi;                 /* 16: sum of q^2 >> 32; the square sum is sumsq_lo + (sumsq_hi << 32), exact, up to 93 bits */
+  uint64_t min_key;                  /* 24: (uint32(q) ^ 2^31) << 32 | idx of the first pixel with the smallest q; all ones: none */
+  uint64_t max_key;                  /* 32: (uint32(q) ^ 2^31) << 32 | uint32(~idx) of the first pixel with the largest q; 0: none */
+  int32_t n, n_invalid, n_clipped;   /* 40: valid pixels; invalid ones; valid ones whose product was clamped */
+  uint32_t below, above;             /* 52: valid pixels with q < q_lo, with q >= q_hi (bins > 0) */
+  int32_t _pad;
+} InsarZonalStat;
+/* host only: bytes of the table for 1 <= max_regions <= 2^24, 0 <= bins <= 256, 1 <= channels <= 4 (a multiple of 16, monotone
+ * in every argument) */
+int insar_zonal_scratch_bytes(int32_t max_regions, int32_t bins, int32_t channels, int64_t* table_bytes);
+/* 1 launch: the table zeroed, every min_key all ones. Once before every accumulate. table 16-byte aligned. */
+int insar_zonal_clear(void* table, int32_t max_regions, int32_t bins, int32_t channels, void* stream);
+/* 1 launch. 16-byte loads where H * W % 4 == 0 and the pointers allow it (uint8: 4-byte), guarded scalars otherwise:
+ * misalignment is no error. The raster under background pixels is not read. labels and raster are never written. */
+int insar_zonal_accumulate(const int32_t* labels, const void* raster, int32_t elem_type, int32_t channels, int32_t H, int32_t W,
+                           double scale, int32_t has_nodata, double nodata, int32_t bins, int64_t q_lo, int64_t q_hi,
+                           int32_t max_regions, void* table, void* stream);
+
 /* ---- distance transform (build-side addition; the reference has no post-processing): csrc/distance.hip --------------------
  * The exact squared Euclidean distance from every pixel of a map m [B][H][W] (row-major; uint8 with INSAR_DIST_U8, int32 with
  * INSAR_DIST_I32; B, H, W >= 1, H, W <= 32767, B * H * W < 2^31, no tile-multiple requirement) to the nearest SITE of the same

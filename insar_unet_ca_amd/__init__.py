@@ -18,6 +18,7 @@ from .distance import DistanceScratch, boundary_counts, boundary_iou, distance_t
 from .crops import CropIndex, SceneCrops, draw_crops, gather_crops  # noqa: F401
 from .outlines import OutlineScratch, region_outlines, to_geojson, to_polygons  # noqa: F401
 from .skeletons import SkeletonScratch, skeleton_table, thin_regions  # noqa: F401
+from .zonal import ZonalScratch, percentile, region_stats  # noqa: F401
 from .rasterise import PolygonTable, RasterScratch, from_geojson, labels_from_geojson, pack_polygons, rasterise_polygons  # noqa: F401
 
 __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "ChannelAttentionModule", "MaxPool2d", "CrossEntropyLoss", "DiceLoss", "DiceCELoss", "Adam", "GraphedTrainStep",
@@ -32,4 +33,5 @@ __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "Cha
            "CropIndex", "SceneCrops", "draw_crops", "gather_crops",
            "OutlineScratch", "region_outlines", "to_polygons", "to_geojson",
            "SkeletonScratch", "thin_regions", "skeleton_table",
-           "PolygonTable", "RasterScratch", "pack_polygons", "from_geojson", "rasterise_polygons", "labels_from_geojson"]
+           "PolygonTable", "RasterScratch", "pack_polygons", "from_geojson", "rasterise_polygons", "labels_from_geojson",
+           "ZonalScratch", "region_stats", "percentile"]

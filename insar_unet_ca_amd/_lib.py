@@ -22,6 +22,7 @@ DIST_U8, DIST_I32 = 0, 1
 DIST_EQ, DIST_NE, DIST_EDGE = 0, 1, 2
 DIST_FAR = 0x7FFFFFFF
 RASTER_U8, RASTER_I32 = 0, 1
+ZONAL_F32, ZONAL_U8, ZONAL_I32 = 0, 1, 2
 IGEMM_OOB_ZERO = 1
 IGEMM_PINGPONG = 2
 
@@ -239,6 +240,9 @@ _SIGNATURES = {
     "insar_overlap_clear": [_P, _P, _L, _P],
     "insar_overlap_count": [_P, _P, _P, _I, _I, _I, _P, _L, _P],
     "insar_overlap_compact": [_P, _L, _P, _P],
+    "insar_zonal_scratch_bytes": [_I, _I, _I, _P],
+    "insar_zonal_clear": [_P, _I, _I, _I, _P],
+    "insar_zonal_accumulate": [_P, _P, _I, _I, _I, _I, C.c_double, _I, C.c_double, _I, _L, _L, _I, _P, _P],
     "insar_dist_scratch_bytes": [_I, _I, _I, _P],
     "insar_dist_transform": [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "insar_dist_boundary_counts": [_P, _P, _P, _P, _I, _I, _L, _I, _I, _P, _P],

@@ -230,6 +230,7 @@ class ScenePredictor:
         self._tta.clear()
         self._overlaps.clear()
         self._distance.clear()
+        self.__dict__.pop("_zonal", None)
 
     def _tta_buffers(self, device: torch.device):
         if device not in self._tta:
@@ -282,13 +283,19 @@ class ScenePredictor:
         return _finalize(acc, wsum, return_prob)
 
     def detect(self, scene, return_prob: bool = False, outlines: bool = False, skeletons: bool = False,
-               max_iterations: int = 32, **region_kwargs) -> dict:
+               max_iterations: int = 32, measure: Optional[dict] = None, **region_kwargs) -> dict:
         """`predict(scene)` followed by `label_regions(out["mask"], out["conf"], **region_kwargs)`: the predict outputs
         unchanged, plus "labels", "regions", "count" and the cleaned class map under "mask_clean". With `outlines=True` also
         "outlines" = `outlines.region_outlines(out["labels"])` with the connectivity the regions were labelled with, and
         out["regions"]["perimeter"], the crack length of each region over all of its rings. With `skeletons=True` also
         "skeleton" = the kinds map of `skeletons.thin_regions(out["labels"], max_iterations=max_iterations)`, "skeleton_converged",
-        and out["regions"]["length"], ["mean_width"], ["max_width"], ["orientation"], ["n_end"], ["n_junction"]."""
+        and out["regions"]["length"], ["mean_width"], ["max_width"], ["orientation"], ["n_end"], ["n_junction"]. With `measure` =
+        {name: raster} or {name: (raster, kwargs)} also "stats"[name] = `zonal.region_stats(out["labels"], raster,
+        count=out["count"], max_regions=..., **kwargs)`, rows aligned with out["regions"]["id"]: a raster is [H, W] or
+        [C, H, W], float32, uint8 or int32, numpy or tensor (a host raster is copied once); the string "input" stands for the
+        scene that was predicted (a uint8 scene is measured as its byte values)."""
+        if measure is not None and not isinstance(measure, dict):
+            raise InsarError(f"measure: a dict of name -> raster or (raster, kwargs), got {type(measure).__name__}")
         out = dict(self.predict(scene, return_prob=return_prob))
         H, W = out["mask"].shape
         max_regions = region_kwargs.get("max_regions", DEFAULT_MAX_REGIONS)
@@ -301,7 +308,33 @@ class ScenePredictor:
             self._trace(out, region_kwargs.get("connectivity", 8))
         if skeletons:
             self._thin(out, max_iterations, max_regions)
+        if measure is not None:
+            self._measure(out, scene, measure, max_regions)
         return out
+
+    def _measure(self, out: dict, scene, measure: dict, max_regions: int) -> None:
+        from .zonal import ZonalScratch, region_stats
+        dev = out["labels"].device
+        cache = self.__dict__.setdefault("_zonal", {})
+        out["stats"] = {}
+        for name, spec in measure.items():
+            raster, kw = spec if isinstance(spec, tuple) else (spec, {})
+            if isinstance(raster, str):
+                if raster != "input":
+                    raise InsarError(f"measure[{name!r}]: the only raster named by a string is \"input\", got {raster!r}")
+                raster = scene
+            if isinstance(raster, np.ndarray):
+                raster = torch.from_numpy(np.ascontiguousarray(raster))
+            if not isinstance(raster, torch.Tensor):
+                raise InsarError(f"measure[{name!r}]: numpy array or torch tensor, got {type(raster).__name__}")
+            raster = raster.detach().to(dev).contiguous()
+            bins, channels = kw.get("bins", 0), raster.shape[0] if raster.dim() == 3 else 1
+            key = (dev, max_regions, bins, channels)
+            if key not in cache and isinstance(bins, int) and 0 <= bins <= 256 and 1 <= channels <= 4 \
+                    and isinstance(max_regions, int) and max_regions >= 1:
+                cache[key] = ZonalScratch(dev, max_regions, bins, channels)
+            out["stats"][name] = region_stats(out["labels"], raster, count=out["count"], max_regions=max_regions,
+                                              scratch=cache.get(key), **kw)
 
     def _thin(self, out: dict, max_iterations: int, max_regions: int) -> None:
         from .skeletons import SkeletonScratch, thin_regions
@@ -328,14 +361,15 @@ class ScenePredictor:
         out["regions"]["perimeter"] = perimeters(out["outlines"]["rings"], out["regions"]["id"])
 
     def evaluate(self, scene, gt_mask, *, iou_threshold: float = 0.5, gt_min_area: int = 1, max_pairs: int = DEFAULT_MAX_PAIRS,
-                 boundary_distance: Optional[int] = None, **region_kwargs) -> dict:
+                 boundary_distance: Optional[int] = None, measure: Optional[dict] = None, **region_kwargs) -> dict:
         """`detect(scene, **region_kwargs)`, then `label_regions` of the ground-truth class map (`gt_mask` uint8 [H, W], numpy
         or tensor, copied to the device once; 255 = ignore, labelled as background) with the same connectivity and
         `min_area=gt_min_area`, then `score.match_regions` with `void=gt_mask, void_value=255`: the detect outputs unchanged,
         plus "score" (the match result), "gt_labels", "gt_regions" and "gt_count". With `boundary_distance` = d (an integer
         >= 0) the score gains "boundary" = {"distance", "counts", "iou", "mean_iou"}: `distance.boundary_counts` of
-        "mask_clean" against `gt_mask` (void 255) at d pixels, and `boundary_iou` of them; with None nothing of it runs."""
-        out = self.detect(scene, **region_kwargs)
+        "mask_clean" against `gt_mask` (void 255) at d pixels, and `boundary_iou` of them; with None nothing of it runs.
+        `measure` goes to `detect`."""
+        out = self.detect(scene, measure=measure, **region_kwargs)
         dev = out["mask"].device
         H, W = out["mask"].shape
         gt = torch.from_numpy(np.ascontiguousarray(gt_mask)) if isinstance(gt_mask, np.ndarray) else gt_mask
@@ -370,7 +404,7 @@ def predict_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw
 
 def detect_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw) -> dict:
     """One-shot ScenePredictor(model, ...).detect(scene, return_prob, ...): tile / overlap / batch / num_classes / tta go to
-    the predictor, `outlines`, `skeletons` and `max_iterations` to `detect`, every other keyword to `label_regions`."""
+    the predictor, `outlines`, `skeletons`, `max_iterations` and `measure` to `detect`, every other keyword to `label_regions`."""
     pred_kw = {k: kw.pop(k) for k in ("tile", "overlap", "batch", "num_classes", "tta") if k in kw}
     return ScenePredictor(model, **pred_kw).detect(scene, return_prob=return_prob, **kw)
 
