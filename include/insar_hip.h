@@ -678,6 +678,75 @@ int insar_outline_rings(const int32_t* labels, int32_t H, int32_t W, int32_t n_e
 int insar_outline_write(int32_t H, int32_t W, int32_t n_edges, int32_t corners_only, int32_t max_rings, int32_t max_vertices,
                         int32_t max_edges, void* scratch, void* table, int32_t* vertices, void* stream);
 
+/* ---- outline simplification (build-side addition; the reference has no post-processing): csrc/simplify.hip -------------------
+ * Douglas-Peucker over the rings of the region outlines, in exact integers, with the common border of two regions simplified
+ * to the same vertices from both sides. A POSITION is an index into the input vertex array; the kept set is a set of positions.
+ *   input:     vertices int32 [n_vertices][2] as (y, x), ring after ring, 0 <= y, x <= 16384; `rings`: InsarRing [1 + n_rings]
+ *              on the device (record 0 is a header and is not read; of a ring only start and count are read, the other fields
+ *              are copied), the rings contiguous and in order: start[0] = 0, start[r + 1] = start[r] + count[r], the counts
+ *              adding up to n_vertices; optionally the label map int32 [H][W], H, W <= 16384, the rings were traced from.
+ *              Vertex (y, x) is the top-left corner of pixel (y, x); its four pixels are p00 = (y-1, x-1), p01 = (y-1, x),
+ *              p10 = (y, x-1), p11 = (y, x), a pixel outside the map counting as 0.
+ *   anchors:   only with `labels`: a position whose four pixels hold three or more distinct values, or form a two-label saddle
+ *              (p00 == p11, p01 == p10, p00 != p01, both non-zero). Anchors are always kept and split a ring into arcs along
+ *              which the pair (own label, label across) is constant: both rings that border an arc see the same vertices
+ *              between the same end points, in opposite order. This needs every lattice vertex in both rings (a T-junction
+ *              on a straight side is a corner of one ring only): with `labels` the caller passes rings traced with
+ *              corners_only = 0 (count == edges). Without `labels` there are no anchors and every ring stands alone.
+ *   seeds:     a ring with no anchor position, or exactly one, is a closed arc. Seed 1 is the anchor's coordinates, else the
+ *              lexicographically smallest (y, x) of the ring; seed 2 is the coordinates with the largest squared distance from
+ *              seed 1, ties to the smallest (y, x). EVERY position of the ring that carries the coordinates of a seed is kept (a
+ *              ring may pass a saddle twice). Neither seed depends on the ring's direction or start vertex.
+ *   round:     a segment (a, b) is a pair of cyclically consecutive kept positions of a ring. Among the positions strictly
+ *              between them the winner has the largest cross^2, cross = (b - a) x (p - a) as an integer, ties to the smallest
+ *              (y, x) - never to the smallest index, so both directions agree; every position of the segment that equals the
+ *              winner in both is a winner. Winners are kept iff 256 cross^2 > eps2q |b - a|^2, with eps2q = q^2 and q the
+ *              tolerance in 1/16 pixel (0 <= q <= 16384), compared exactly: for integers this is cross^2 > floor(eps2q
+ *              |b - a|^2 / 256), and cross^2 < 2^60, eps2q |b - a|^2 < 2^58 fit 64 bits. Where a and b carry the same
+ *              coordinates (an arc that returns to its anchor) the distance from that point stands for the distance from the
+ *              line: |p - a|^2 takes the place of cross^2 and 1 that of |b - a|^2. Round r is recursion level r of the
+ *              sequential algorithm; all segments of all rings take part in every round. With eps2q = 0 exactly the vertices
+ *              off their chord survive: collinear vertices are dropped.
+ *   rounds:    rounds 0 .. max_rounds - 1 keep their winners (1 <= max_rounds <= 4095); round max_rounds is a probe that only
+ *              counts them. A round whose predecessor kept nothing returns at once, so later rounds are no-ops. `rounds` is
+ *              the number of rounds that kept a vertex; `converged` says that the probe found nothing to keep (or was not
+ *              needed): otherwise the result is the sequential result truncated at depth max_rounds.
+ *   output:    out_vertices int32 [n_vertices][2], out_kept int32 [n_vertices]: the kept vertices and their positions, in
+ *              input order, compacted (the first `count` of the header are written). table: InsarRing [1 + n_rings], 16-byte
+ *              aligned. Record 0: label = n_rings, count = kept vertices, edges = n_vertices, leader = rounds, start =
+ *              converged. Record 1 + r: label, leader and edges of the input ring; start and count in the compacted array;
+ *              area2 the exact shoelace sum and y0 .. x1 the half-open box of the kept vertices; _pad = 1 where the ring
+ *              collapsed (fewer than 3 kept vertices, or area2 == 0), else 0.
+ *   scratch:   insar_simplify_scratch_bytes(...) bytes, 16-byte aligned; setup clears what it needs. Its first 4096 int32
+ *              are the per-round counters of kept vertices (slot max_rounds: the probe): a host that reads the counter of the
+ *              last round it launched and finds 0 may stop launching rounds.
+ * Guaranteed: every dropped vertex lies within the tolerance of the chord of the segment it ended in; the kept set of a larger
+ * tolerance is a subset of that of a smaller one when both converged; a shared arc comes out identical from both sides. NOT
+ * guaranteed: that two different arcs never cross at a large tolerance (Douglas-Peucker does not, and nothing is added).
+ * Call setup, rounds (once, or in batches of consecutive rounds), finish in this order on one stream with the same counts and
+ * capacities. 4 + 4 per round + 6 launches; no work-group waits on another, integer atomics only, nothing depends on launch
+ * geometry. Every argument is checked before the device is touched (null pointers, counts against capacities, alignment,
+ * H, W, eps2q, the round numbers); the ring table itself lives on the device and is the caller's promise, and no kernel
+ * leaves its buffers whatever the table holds. */
+/* host only: bytes of scratch and of the output table for these capacities (1 <= max_vertices <= 2^28, 1 <= max_rings <= 2^26) */
+int insar_simplify_scratch_bytes(int32_t max_vertices, int32_t max_rings, int64_t* scratch_bytes, int64_t* table_bytes);
+/* host only: the launches of setup, `rounds` rounds (the probe counts as one) and finish: 10 + 4 rounds */
+int insar_simplify_launches(int32_t rounds);
+/* 4 launches (clear; ring of every vertex, anchors, smallest key per ring; farthest vertex per ring; seeds kept). labels is
+ * nullable; H and W are checked only with labels. */
+int insar_simplify_setup(const int32_t* vertices, int32_t n_vertices, const void* rings, int32_t n_rings,
+                         const int32_t* labels /*nullable*/, int32_t H, int32_t W, int32_t max_vertices, int32_t max_rings,
+                         void* scratch, void* stream);
+/* 4 launches per round (carries of the kept positions over the blocks; cross^2 and the segment maximum; ties; winners kept) for
+ * the rounds first_round .. first_round + n_rounds - 1, all within 0 .. max_rounds; round max_rounds is the probe. */
+int insar_simplify_rounds(const int32_t* vertices, int32_t n_vertices, const void* rings, int32_t n_rings, int64_t eps2q,
+                          int32_t first_round, int32_t n_rounds, int32_t max_rounds, int32_t max_vertices, int32_t max_rings,
+                          void* scratch, void* stream);
+/* 6 launches (kept per block; one-work-group scan and the header; scatter; ring records; area2 and boxes; collapsed flags) */
+int insar_simplify_finish(const int32_t* vertices, int32_t n_vertices, const void* rings, int32_t n_rings, int32_t max_rounds,
+                          int32_t max_vertices, int32_t max_rings, void* scratch, void* table, int32_t* out_vertices,
+                          int32_t* out_kept, void* stream);
+
 /* ---- polygon rasterisation (build-side addition; the reference reads ready-made masks): csrc/raster.hip ---------------------
  * The inverse of the region outlines: an edge table becomes a label map `out` [H][W] (row-major; uint8 with INSAR_RASTER_U8,
  * int32 with INSAR_RASTER_I32; H >= 1, 1 <= W <= 16384, H * W < 2^31) in exact integers, no floating point on the device.

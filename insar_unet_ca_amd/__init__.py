@@ -17,6 +17,7 @@ from .augment import Augment  # noqa: F401
 from .distance import DistanceScratch, boundary_counts, boundary_iou, distance_transform, expand_labels, void_band  # noqa: F401
 from .crops import CropIndex, SceneCrops, draw_crops, gather_crops  # noqa: F401
 from .outlines import OutlineScratch, region_outlines, to_geojson, to_polygons  # noqa: F401
+from .simplify import SimplifyScratch, simplify_outlines  # noqa: F401
 from .skeletons import SkeletonScratch, skeleton_table, thin_regions  # noqa: F401
 from .zonal import ZonalScratch, percentile, region_stats  # noqa: F401
 from .rasterise import PolygonTable, RasterScratch, from_geojson, labels_from_geojson, pack_polygons, rasterise_polygons  # noqa: F401
@@ -31,7 +32,7 @@ __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "Cha
            "region_overlaps", "match_regions", "match_from_overlaps", "DetectionScore", "evaluate_scene",
            "DistanceScratch", "distance_transform", "void_band", "expand_labels", "boundary_counts", "boundary_iou",
            "CropIndex", "SceneCrops", "draw_crops", "gather_crops",
-           "OutlineScratch", "region_outlines", "to_polygons", "to_geojson",
+           "OutlineScratch", "region_outlines", "to_polygons", "to_geojson", "SimplifyScratch", "simplify_outlines",
            "SkeletonScratch", "thin_regions", "skeleton_table",
            "PolygonTable", "RasterScratch", "pack_polygons", "from_geojson", "rasterise_polygons", "labels_from_geojson",
            "ZonalScratch", "region_stats", "percentile"]

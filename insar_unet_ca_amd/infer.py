@@ -283,11 +283,14 @@ class ScenePredictor:
         return _finalize(acc, wsum, return_prob)
 
     def detect(self, scene, return_prob: bool = False, outlines: bool = False, skeletons: bool = False,
-               max_iterations: int = 32, measure: Optional[dict] = None, **region_kwargs) -> dict:
+               max_iterations: int = 32, measure: Optional[dict] = None, simplify: Optional[float] = None, **region_kwargs) -> dict:
         """`predict(scene)` followed by `label_regions(out["mask"], out["conf"], **region_kwargs)`: the predict outputs
         unchanged, plus "labels", "regions", "count" and the cleaned class map under "mask_clean". With `outlines=True` also
         "outlines" = `outlines.region_outlines(out["labels"])` with the connectivity the regions were labelled with, and
-        out["regions"]["perimeter"], the crack length of each region over all of its rings. With `skeletons=True` also
+        out["regions"]["perimeter"], the crack length of each region over all of its rings. With `simplify` = a tolerance in
+        pixels next to `outlines=True`, "outlines" is instead `simplify.simplify_outlines` of the rings traced with
+        corners_only=False, with out["labels"] as the label map, so touching regions share their border vertex for vertex; the
+        untouched trace is not kept, and the perimeter, which comes from `edges`, is the same. With `skeletons=True` also
         "skeleton" = the kinds map of `skeletons.thin_regions(out["labels"], max_iterations=max_iterations)`, "skeleton_converged",
         and out["regions"]["length"], ["mean_width"], ["max_width"], ["orientation"], ["n_end"], ["n_junction"]. With `measure` =
         {name: raster} or {name: (raster, kwargs)} also "stats"[name] = `zonal.region_stats(out["labels"], raster,
@@ -304,7 +307,11 @@ class ScenePredictor:
             self._regions[key] = RegionScratch(H, W, out["mask"].device, max_regions)
         reg = label_regions(out["mask"], out["conf"], scratch=self._regions.get(key), **region_kwargs)
         out.update(labels=reg["labels"], regions=reg["regions"], count=reg["count"], mask_clean=reg["mask"])
-        if outlines:
+        if simplify is not None and not outlines:
+            raise InsarError("detect: simplify needs outlines=True")
+        if outlines and simplify is not None:
+            self._trace_simplified(out, region_kwargs.get("connectivity", 8), simplify)
+        elif outlines:
             self._trace(out, region_kwargs.get("connectivity", 8))
         if skeletons:
             self._thin(out, max_iterations, max_regions)
@@ -360,6 +367,18 @@ class ScenePredictor:
         out["outlines"] = region_outlines(out["labels"], connectivity=connectivity, scratch=cache[key])
         out["regions"]["perimeter"] = perimeters(out["outlines"]["rings"], out["regions"]["id"])
 
+    def _trace_simplified(self, out: dict, connectivity: int, tolerance: float) -> None:
+        from .outlines import OutlineScratch, perimeters, region_outlines
+        from .simplify import simplify_outlines
+        H, W = out["labels"].shape
+        cache = self.__dict__.setdefault("_outlines", {})
+        key = (H, W, out["labels"].device)
+        if key not in cache:
+            cache[key] = OutlineScratch(H, W, out["labels"].device)
+        raw = region_outlines(out["labels"], connectivity=connectivity, corners_only=False, scratch=cache[key])
+        out["outlines"] = simplify_outlines(raw, out["labels"], tolerance=tolerance)
+        out["regions"]["perimeter"] = perimeters(out["outlines"]["rings"], out["regions"]["id"])
+
     def evaluate(self, scene, gt_mask, *, iou_threshold: float = 0.5, gt_min_area: int = 1, max_pairs: int = DEFAULT_MAX_PAIRS,
                  boundary_distance: Optional[int] = None, measure: Optional[dict] = None, **region_kwargs) -> dict:
         """`detect(scene, **region_kwargs)`, then `label_regions` of the ground-truth class map (`gt_mask` uint8 [H, W], numpy
@@ -404,7 +423,8 @@ def predict_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw
 
 def detect_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw) -> dict:
     """One-shot ScenePredictor(model, ...).detect(scene, return_prob, ...): tile / overlap / batch / num_classes / tta go to
-    the predictor, `outlines`, `skeletons`, `max_iterations` and `measure` to `detect`, every other keyword to `label_regions`."""
+    the predictor, `outlines`, `simplify`, `skeletons`, `max_iterations` and `measure` to `detect`, every other keyword to
+    `label_regions`."""
     pred_kw = {k: kw.pop(k) for k in ("tile", "overlap", "batch", "num_classes", "tta") if k in kw}
     return ScenePredictor(model, **pred_kw).detect(scene, return_prob=return_prob, **kw)
 

@@ -184,26 +184,33 @@ def _apply(ring_yx: np.ndarray, transform) -> np.ndarray:
     return xy1 @ A.T
 
 
-def to_polygons(outlines: dict, *, transform=None) -> List[dict]:
+def to_polygons(outlines: dict, *, transform=None, drop_collapsed: bool = True) -> List[dict]:
     """One entry per label, in ascending label order: {"label", "polygons": [{"exterior": ndarray [n, 2], "holes": [ndarray,
     ...]}, ...]}, polygons in ring order. Every hole goes to the exterior ring of its label that contains it: the only one
     where there is one, else the smallest (by |area2|) exterior that holds, by an even-odd crossing test, the centre of the
     pixel below-right of the hole's top-left-most vertex, which lies inside the hole. Rings are closed by repeating the first
     vertex. Without `transform` the vertices are the integer lattice (y, x); with a 2 x 3 affine they are float64 world
-    coordinates A @ (x, y, 1)."""
+    coordinates A @ (x, y, 1). A dict with a `collapsed` ring field (`simplify_outlines` writes one) tells exteriors from holes
+    by its `hole` field, since a simplified ring may have lost its area, and with `drop_collapsed` leaves collapsed rings out: a
+    collapsed exterior takes its holes with it, and a label left without a polygon has no entry. A dict without that field is
+    treated exactly as before, whatever `drop_collapsed` says."""
     rings = outlines["rings"]
     v = outlines["vertices"]
     v = v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
     by_label: Dict[int, dict] = {}
     n = len(rings["label"])
     raw = [v[int(rings["start"][i]):int(rings["start"][i]) + int(rings["count"][i])] for i in range(n)]
+    simplified = "collapsed" in rings
+    is_ext = ~np.asarray(rings["hole"], dtype=bool) if simplified else np.asarray(rings["area2"]) > 0
+    is_hole = np.asarray(rings["hole"], dtype=bool) if simplified else np.asarray(rings["area2"]) < 0
+    gone = np.asarray(rings["collapsed"], dtype=bool) if simplified and drop_collapsed else np.zeros(n, dtype=bool)
     for i in range(n):
-        if rings["area2"][i] > 0:
+        if is_ext[i]:
             e = by_label.setdefault(int(rings["label"][i]), {"label": int(rings["label"][i]), "polygons": [], "_ext": []})
             e["polygons"].append({"exterior": _apply(raw[i], transform), "holes": []})
             e["_ext"].append(i)
     for i in range(n):
-        if rings["area2"][i] >= 0:
+        if not is_hole[i] or gone[i]:
             continue
         lab = int(rings["label"][i])
         if lab not in by_label:
@@ -213,25 +220,30 @@ def to_polygons(outlines: dict, *, transform=None) -> List[dict]:
         if len(ext) > 1:
             top = raw[i][np.lexsort((raw[i][:, 1], raw[i][:, 0]))[0]]
             py, px = top[0] + 0.5, top[1] + 0.5
-            holding = [j for j, r in enumerate(ext) if _inside(raw[r], py, px)]
+            holding = [j for j, r in enumerate(ext) if not gone[r] and _inside(raw[r], py, px)]
             if not holding:
+                if any(gone[r] for r in ext):                                 # its exterior collapsed: the hole goes with it
+                    continue
                 raise InsarError(f"to_polygons: no exterior ring of label {lab} contains hole ring {i}")
             pick = min(holding, key=lambda j: abs(int(rings["area2"][ext[j]])))
         by_label[lab]["polygons"][pick]["holes"].append(_apply(raw[i], transform))
     out = []
     for lab in sorted(by_label):
         e = by_label[lab]
+        e["polygons"] = [p for p, r in zip(e["polygons"], e["_ext"]) if not gone[r]]
         del e["_ext"]
-        out.append(e)
+        if e["polygons"]:
+            out.append(e)
     return out
 
 
-def to_geojson(outlines: dict, *, transform=None, properties=None) -> dict:
+def to_geojson(outlines: dict, *, transform=None, properties=None, drop_collapsed: bool = True) -> dict:
     """A GeoJSON FeatureCollection: one Polygon / MultiPolygon feature per label, coordinates as [x, y] lists (lattice x, y
     without `transform`, world coordinates with it), rings closed. `properties`: a dict label -> dict merged into the
-    feature's properties next to "label", or a callable label -> dict. json-serialisable types only."""
+    feature's properties next to "label", or a callable label -> dict. json-serialisable types only. `drop_collapsed` goes to
+    `to_polygons`."""
     feats = []
-    for e in to_polygons(outlines, transform=transform):
+    for e in to_polygons(outlines, transform=transform, drop_collapsed=drop_collapsed):
         polys = []
         for p in e["polygons"]:
             rings = [p["exterior"]] + p["holes"]
