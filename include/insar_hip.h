@@ -88,7 +88,8 @@ int insar_weight_prep_pair_batch(const int64_t* jobs, int32_t njobs, int64_t tot
  *         ConvTranspose2d dgrad (stride 2, taps {0,1}^2): out pixel (ho,wo), channel n.
  * mode 1: ConvTranspose2d(k=2,s=2) forward (:112,115,118,121): N = 4*Cout, n=(a*2+b)*Cout+co
  *         is scattered to out pixel (2ho+a, 2wo+b), channel co.
- * stats (nullable): per-M-tile partial column sums of the stored output,
+ * stats (nullable): per-M-tile partial column sums of the GEMM result as rounded to the output type, BEFORE bias / add
+ *         (the raw, bias-free conv output insar_bn_finalize expects; without bias / add that is the stored output),
  *         float[insar_igemm_num_mtiles(M, N)][2][N] (sum, sum of squares) for BatchNorm (:82,85). */
 /* BatchNorm-backward sums taken in the epilogue of the GEMM that PRODUCES a unit's incoming gradient ("bstat"), instead of
  * a pass of its own over (dout, y) (insar_bnrelu_bwd_reduce; :82-83,85-86 inside loss.backward(), :345): with g = the
