@@ -1038,6 +1038,21 @@ extern "C" int insar_conv1x1_out_bwd_blocks(int32_t B, int32_t H) {
   return (int)(r > 1024 ? 1024 : r);
 }
 
+// conv1x1_out_bwd_kernel keeps the weights and one partial row per wave in LDS: (K*C + 4*(K*C + K)) floats. At bf16 with
+// C = 512 (cpp = 64, the widest narrow-path input) and K = 7 or 8 that is 71 792 / 82 048 bytes, past the 64 KB a kernel
+// may ask for without hipFuncAttributeMaxDynamicSharedMemorySize (the FCN head in bf16 with 7 or 8 classes). fp32 stops
+// at C = 256: 41 088 bytes. One "attribute set" mask per instantiation (see insar_set_lds_once in common.h).
+#define DR_OUT_BWD_MAX_LDS ((DR_MAXK * 512 + 4 * (DR_MAXK * 512 + DR_MAXK)) * (int)sizeof(float))
+template <typename T, bool FROMY>
+static int out_bwd_allow_lds(size_t lds, const char* who) {
+  if (lds <= 64 * 1024) return INSAR_OK;
+  if (lds > (size_t)DR_OUT_BWD_MAX_LDS) INSAR_FAIL(INSAR_E_SHAPE, "%s: %zu bytes of LDS", who, lds);
+  static std::atomic<uint64_t> attr_mask{0};       // per-device, see common.h
+  hipError_t e = insar_set_lds_once(attr_mask, (const void*)conv1x1_out_bwd_kernel<T, FROMY>, DR_OUT_BWD_MAX_LDS);
+  if (e != hipSuccess) INSAR_FAIL(-(int)e, "%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
+  return INSAR_OK;
+}
+
 extern "C" int insar_conv1x1_out_bwd(const InsarAct* x, const float* w, const float* dlogits, int32_t K,
                                      const InsarAct* dx, float* part, void* stream) {
   int rc;
@@ -1062,6 +1077,7 @@ extern "C" int insar_conv1x1_out_bwd(const InsarAct* x, const float* w, const fl
   if (x->B != dx->B || x->H != dx->H || x->W != dx->W || x->c_len != dx->c_len || x->dtype != dx->dtype)
     INSAR_FAIL(INSAR_E_SHAPE, "insar_conv1x1_out_bwd: x/dx mismatch");
   size_t lds = (size_t)(K * x->c_len + 4 * (K * x->c_len + K)) * sizeof(float);
+  if (x->dtype == INSAR_BF16 && (rc = out_bwd_allow_lds<bf16_t, false>(lds, "insar_conv1x1_out_bwd"))) return rc;
   int grid = insar_conv1x1_out_bwd_blocks(x->B, x->H);
   hipStream_t s = (hipStream_t)stream;
   if (x->dtype == INSAR_BF16) hipLaunchKernelGGL(conv1x1_out_bwd_kernel<bf16_t>, dim3(grid), dim3(DR_THREADS), lds, s, make_view(*x), w, dlogits, K, make_view(*dx), part);
@@ -1078,6 +1094,7 @@ extern "C" int insar_conv1x1_out_wgrad(const InsarAct* x, const float* w, const 
   if ((rc = check_out(x, K, "insar_conv1x1_out_wgrad"))) return rc;
   if (!w || !dlogits || !part) INSAR_FAIL(INSAR_E_ARG, "insar_conv1x1_out_wgrad: null pointer");
   size_t lds = (size_t)(K * x->c_len + 4 * (K * x->c_len + K)) * sizeof(float);
+  if (x->dtype == INSAR_BF16 && (rc = out_bwd_allow_lds<bf16_t, false>(lds, "insar_conv1x1_out_wgrad"))) return rc;
   int grid = insar_conv1x1_out_bwd_blocks(x->B, x->H);
   hipStream_t s = (hipStream_t)stream;
   ActView none = make_view(*x); none.base = nullptr;
@@ -1095,6 +1112,7 @@ extern "C" int insar_conv1x1_out_wgrad_y(const InsarAct* y, const float* scale, 
   if ((rc = check_out(y, K, "insar_conv1x1_out_wgrad_y"))) return rc;
   if (!w || !dlogits || !part || !scale || !shift) INSAR_FAIL(INSAR_E_ARG, "insar_conv1x1_out_wgrad_y: null pointer");
   size_t lds = (size_t)(K * y->c_len + 4 * (K * y->c_len + K)) * sizeof(float);
+  if (y->dtype == INSAR_BF16 && (rc = out_bwd_allow_lds<bf16_t, true>(lds, "insar_conv1x1_out_wgrad_y"))) return rc;
   int grid = insar_conv1x1_out_bwd_blocks(y->B, y->H);
   hipStream_t s = (hipStream_t)stream;
   ActView none = make_view(*y); none.base = nullptr;
