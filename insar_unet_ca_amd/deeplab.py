@@ -221,7 +221,7 @@ def _live(n_out: int, n_in: int, stride: int, off: int) -> bool:
     return lo <= hi
 
 
-class ConvUnit:
+class ConvUnit(engine.BNUnit):
     """Conv2d(k in {1,3}, stride, dilation, bias=False) -> BatchNorm2d [-> + res] [-> ReLU]: the unit every layer of
     the backbone / ASPP / head is made of. Raw conv output `y`, activation `out` (any channel slice)."""
 
@@ -253,53 +253,24 @@ class ConvUnit:
             raise _lib.InsarError(f"{name}: output slice does not match the convolution")
         # 3x3 / stride-1 convs with all nine taps, dense or dilated by <= 4 at 32 x 32 (layer1-4 and the head): the flat kernel's
         # row tiles (engine.FLAT_ROWS; conv3x3_flat.hip GEO = 1 / 2) wherever the per-tap kernel would not run 256 x 256 tiles
-        self.rows_fwd = self._rows_flags(self.cout)
-        self.rows_bwd = self._rows_flags(self.cin)
-        self.stat_rows = (call("insar_conv3x3_flat_stat_rows", x.ref, self.cout, self.rows_fwd) if self.rows_fwd
-                          else call("insar_igemm_num_mtiles", self.M, self.cout))
-        self.stats = ctx.f32(self.stat_rows, 2, self.cout)
-        self.stat_rps = 0 if self.stat_rows <= engine.STAT_PREFOLD_ROWS else max(64, -(-self.stat_rows // 64))
-        self.fold_rows = self.stat_rows if not self.stat_rps else -(-self.stat_rows // self.stat_rps)
-        self.sums = ctx.f32(self.fold_rows, 2, self.cout) if self.stat_rps else self.stats
-        self.scale, self.shift, self.mean, self.invstd = (ctx.f32(self.cout) for _ in range(4))
-        self.k1, self.k2 = ctx.f32(self.cout), ctx.f32(self.cout)
-        self.red_rpp = _rows_per_part(B, self.Ho)
-        self.red_rows = -(-self.Ho // self.red_rpp)
-        self.red_part = ctx.f32(B * self.red_rows, 2, self.cout)
-        self.bwd_ws = ctx.f32(B * (3 * self.cout + 1))
+        self.fwd, self.bwd = self._route(self.cout), self._route(self.cin)
+        self._bn_buffers(self.fwd.stat_rows(x, self.y), B, self.Ho, 1)
         self.dy: Optional[Act] = None
         self.w = GemmWeight(ctx, conv.weight, "conv3")
         self._class_w = {}
         self._tmp_grad = None
-        self._ticket = None                       # last-arriver counter of the single-launch coefficient stages
-        # BatchNorm-backward sums written by the epilogue of the GEMM that produces this unit's incoming gradient
-        # (engine.ConvBN.bstat_slab, InsarBstat)
-        self.bred, self.bred_rows, self.bred_ready = None, 0, False
-        self.bred_plain, self._mask_off = False, None
-
-    def bstat_slab(self, rows_total: int, per_image: bool, plain: bool = False):
-        """(slab, (y, scale, shift)) for a GEMM that writes this unit's incoming gradient and takes its BatchNorm-backward
-        sums in its epilogue. plain: sums without the unit's own ReLU mask (a residual block's last unit, whose gradient
-        arrives already gated by the block's ReLU: scale 0 / shift 1 make the mask all-ones)."""
-        B = self.x.B
-        if (not self.relu and not plain) or (per_image and rows_total % B):
-            return None
-        rows = -(-rows_total // B)
-        if self.bred is None or self.bred_rows != rows:
-            self.bred, self.bred_rows = self.ctx.f32(B * rows, 2, self.cout), rows
-        self.bred_plain = plain
-        if plain:
-            if self._mask_off is None:
-                self._mask_off = (torch.zeros(self.cout, device=self.ctx.device), torch.ones(self.cout, device=self.ctx.device))
-            return self.bred, (self.y, self._mask_off[0], self._mask_off[1])
-        return self.bred, (self.y, self.scale, self.shift)
 
     def params(self):
         return [self.conv.weight, self.bn.weight, self.bn.bias]
 
-    def _wptr(self, which: str) -> int:
+    def _w(self, which: str):
+        """The GEMM-layout weight of a direction; where only the centre tap is live, the address of that tap's slab."""
         w = self.w.fwd() if which == "fwd" else self.w.dgrad()
-        return w.data_ptr() + self.tap_ids[0] * self.cout * self.cin * self.ctx.esize
+        return w.data_ptr() + 4 * self.cout * self.cin * self.ctx.esize if self.centre_only else w
+
+    def _route(self, N: int) -> engine.Route:
+        geo = self._rows_flags(N)
+        return engine.Route("rows", geo) if geo else engine.Route("igemm")
 
     def _rows_flags(self, N: int) -> int:
         """flip bits of the flat kernel's row tiles for this unit's convolution to N output columns (forward: cout, input
@@ -323,16 +294,8 @@ class ConvUnit:
         if training and self.M <= 1:
             raise ValueError("Expected more than 1 value per channel when training, got input size "
                              f"torch.Size([{self.x.B}, {self.cout}, {self.Ho}, {self.Wo}])")
-        if self.rows_fwd:
-            engine._conv3x3_flat(self.x, self.y, self.w.fwd(), 0, self.stats if training else None, geo=self.rows_fwd)
-        else:
-            _igemm(self.x, self.y, self._wptr("fwd"), self.cout, self.Ho, self.Wo, self.s, self.taps, 0,
-                   stats=self.stats if training else None, oob=self.oob)
-        if training and self.stat_rps:
-            call("insar_colsum_partial", ptr(self.stats), ptr(self.sums), self.stat_rows, 2 * self.cout, self.stat_rps, s)
-        d = bn_finalize_desc(self.bn, ptr(self.sums), self.fold_rows, self.M, self.cout, training, 0,
-                             ptr(self.scale), ptr(self.shift), ptr(self.mean), ptr(self.invstd))
-        call("insar_bn_finalize", C.byref(d), s)
+        self.fwd.launch(self.x, self.y, self._w("fwd"), 0, self.stats if training else None, stride=self.s, taps=self.taps, oob=self.oob)
+        self._bn_finalize(training)
         if not apply:
             return
         if self.res is not None:
@@ -356,23 +319,12 @@ class ConvUnit:
         B = self.x.B
         if self.dy is None:
             self.dy = Act.alloc(B, self.Ho, self.Wo, self.cout, ctx.dtype, ctx.device)
-        fused = self.bred_ready and (relu != self.bred_plain)      # the slab's sums were taken with / without this unit's ReLU mask
-        self.bred_ready = False
+        red, red_rows, fused = self._take_sums(relu)
         if not fused:
             call("insar_bnrelu_bwd_reduce", dout.ref, self.y.ref, ptr(self.scale), ptr(self.shift), ptr(self.red_part), int(relu),
                  self.red_rpp, s)
-        red, red_rows = (self.bred, self.bred_rows) if fused else (self.red_part, self.red_rows)
         d = bn_bwd_desc(B, self.Ho, self.Wo, self.cout, self.bn, sink, self.mean, self.invstd, self.k1, self.k2)
-        if engine.COEF_SIMPLE:      # no SE gate: one channel-parallel launch over all slab rows
-            call("insar_bn_bwd_coef", C.byref(d), ptr(red), red_rows * B, ptr(self.scale), 0, int(training), s)
-        elif engine.COEF_FUSE:      # both coefficient stages in one launch (stage 2 by the last-arriving work-group)
-            if self._ticket is None:
-                self._ticket = torch.zeros(1, dtype=torch.int32, device=ctx.device)
-            call("insar_bnse_bwd_coef_fused", C.byref(d), ptr(red), red_rows, ptr(self.scale), ptr(self.shift),
-                 ptr(self.bwd_ws), 0, int(training), ptr(self._ticket), s)
-        else:
-            call("insar_bnse_bwd_coef", C.byref(d), ptr(red), red_rows, ptr(self.scale), ptr(self.shift),
-                 ptr(self.bwd_ws), 0, int(training), s)
+        self._coef((C.byref(d), ptr(red), red_rows, ptr(self.scale), ptr(self.shift), ptr(self.bwd_ws), 0, int(training)), s, None)
         call("insar_bnrelu_bwd_apply", dout.ref, self.y.ref, ptr(self.scale), ptr(self.shift), ptr(self.mean), ptr(self.invstd),
              0, 0, ptr(self.k1), ptr(self.k2), self.dy.ref, int(relu), s)
         with ctx.side_stream():
@@ -382,7 +334,7 @@ class ConvUnit:
 
     def can_gate(self) -> bool:
         """The input-gradient GEMM of this unit can apply a ReLU mask to what it stores (stride 1, per-tap GEMM)."""
-        return self.s == 1 and not self.rows_bwd
+        return self.s == 1 and self.bwd.kind == "igemm"
 
     def _input_grad(self, dx: Act, add: Optional[Act], bstat_for: Optional["ConvUnit"] = None, gate: Optional[Act] = None,
                     plain_for: Optional["ConvUnit"] = None) -> None:
@@ -390,27 +342,13 @@ class ConvUnit:
         if gate is not None and not self.can_gate():
             raise _lib.InsarError(f"{self.name}: no gated input gradient on this path")
         if self.s == 1:
-            taps = [(-dy, -dx_) for dy, dx_ in self.taps]
-            slab = None
-            if self.rows_bwd and add is None:
-                # (the dilated 128-column instantiation with the sums in its epilogue spills: 130 us against 68 + a 20 us reduce pass)
-                heavy = (self.rows_bwd >> 8) and not (self.rows_bwd & 16)
-                if bstat_for is not None and engine.BSTAT_FUSE and not heavy and engine._same_layout(dx, bstat_for.y):
-                    slab = bstat_for.bstat_slab(call("insar_conv3x3_flat_stat_rows", self.dy.ref, self.cin, self.rows_bwd), False)
-                engine._conv3x3_flat(self.dy, dx, self.w.dgrad(), 1, slab[0] if slab else None, bstat=slab[1] if slab else None,
-                                     geo=self.rows_bwd)
-                if slab:
-                    bstat_for.bred_ready = True
-                return
-            if add is None and gate is None and bstat_for is not None:
-                slab = engine._igemm_bstat_slab(bstat_for, False, self.x.B * H * W, self.cin, H * W, dx)
-            elif gate is not None and plain_for is not None and engine.BSTAT_FUSE and GATE_STATS and engine._same_layout(dx, plain_for.y):
-                slab = plain_for.bstat_slab(call("insar_igemm_num_mtiles", self.x.B * H * W, self.cin), False, plain=True)
-                bstat_for = plain_for
-            _igemm(self.dy, dx, self._wptr("dgrad"), self.cin, H, W, 1, taps, 0, oob=self.oob, add=add,
-                   stats=slab[0] if slab else None, bstat=slab[1] if slab else None, gate=gate)
-            if slab:
-                bstat_for.bred_ready = True
+            # row tiles add nothing to what they store: with `add` the per-tap GEMM. Only a launch that stores dx complete and
+            # as it is hands out sums: bstat_for's, or under a gate plain_for's (taken without a mask of that unit's own)
+            route = self.bwd if add is None else engine.Route("igemm")
+            consumer = bstat_for if (add is None and gate is None) else None
+            plain = gate is not None and plain_for is not None and GATE_STATS
+            engine._dgrad(route, self.dy, dx, lambda: self._w("dgrad"), plain_for if plain else consumer, plain=plain,
+                          taps=[(-dy, -dx_) for dy, dx_ in self.taps], oob=self.oob, add=add, gate=gate)
             return
         # stride 2: the input gradient of a strided convolution, one launch per parity class of the input pixel
         wd = self.w.dgrad()                                     # [T][Ci][Co]

@@ -678,7 +678,167 @@ def bn_bwd_desc(B: int, H: int, W: int, C: int, bn, sink: "GradSink", mean, invs
     return d
 
 
-class ConvBN:
+class Route:
+    """The kernel a unit's convolution runs on in one direction: the direct first-layer kernel ("small"), the 64 -> 64
+    register-weight kernel ("c64"), the flat kernel ("flat"), its row tiles ("rows", with their `geo` flip bits) or the per-tap
+    implicit GEMM ("igemm"). Chosen once per unit and direction; it says how many statistics rows its launch writes, launches,
+    and says whether the launch can take a consumer's BatchNorm-backward sums in its epilogue."""
+
+    def __init__(self, kind: str, geo: int = 0):
+        self.kind, self.geo = kind, geo
+
+    def per_image(self) -> "Route":
+        """The route whose statistics rows never mix images (persistent work-groups carry their sums across images)."""
+        return Route("rows", self.geo & ~4) if self.kind == "rows" else self
+
+    def stat_rows(self, x: Act, y: Act, flip: int = 0) -> int:
+        """Rows of the statistics slab the launch x -> y writes."""
+        if self.kind == "small":
+            return call("insar_conv3x3_small_fwd_rows", x.ref, y.ref)
+        if self.kind == "c64":
+            return call("insar_conv3x3_c64_rows", x.ref)
+        if self.kind in ("flat", "rows"):
+            return call("insar_conv3x3_flat_stat_rows", x.ref, y.c_len, self.geo or _flat_flags(flip, x))
+        return call("insar_igemm_num_mtiles", y.B * y.H * y.W, y.c_len)
+
+    def launch(self, x: Act, y: Act, w, flip: int, stats: Optional[torch.Tensor], bstat=None, stride: int = 1, taps=None,
+               oob: bool = False, add: Optional[Act] = None, gate: Optional[Act] = None) -> None:
+        """w: the fp32 master ("small") or the GEMM-layout copy of the direction. stride ... gate: the per-tap GEMM's own."""
+        if self.kind == "small":
+            call("insar_conv3x3_small_fwd", x.ref, ptr(w), y.ref, ptr(stats), _lib.stream_ptr())
+        elif self.kind == "c64":
+            _conv3x3_c64(x, y, w, flip, stats, bstat=bstat)
+        elif self.kind in ("flat", "rows"):
+            _conv3x3_flat(x, y, w, flip, stats, bstat=bstat, geo=self.geo)
+        else:
+            _igemm(x, y, w, y.c_len, y.H, y.W, stride, taps or (_TAPS3_DGRAD if flip else _TAPS3), 0, stats=stats, oob=oob,
+                   add=add, bstat=bstat, gate=gate)
+
+    def sums_slab(self, consumer: Optional["BNUnit"], se: bool, x: Act, y: Act, plain: bool = False):
+        """(slab, (y, scale, shift)) if the input-gradient launch x -> y, y being ALL of `consumer`'s incoming gradient, can
+        take that unit's BatchNorm-backward sums in its epilogue (InsarBstat), else None. se: the consumer has an SE gate, whose
+        coefficient stage needs the sums per image: only row tiles (whole rows of ONE image) and GEMM tiles that stay inside an
+        image give that. plain: sums without the consumer's ReLU mask, over the whole batch (BNUnit.bstat_slab)."""
+        if consumer is None or not BSTAT_FUSE or not _same_layout(y, consumer.y):
+            return None
+        if (self.kind in ("c64", "flat") and se) or (self.kind == "c64" and not BSTAT_C64):
+            return None       # their statistics rows mix images
+        if self.kind == "rows" and (self.geo >> 8) and not (self.geo & 16):
+            return None       # the dilated 128-column instantiation with the sums in its epilogue spills: 130 us against 68 + a 20 us reduce pass
+        if self.kind == "igemm" and not plain:
+            bm = call("insar_igemm_tile_rows", y.B * y.H * y.W, y.c_len)
+            if se and (y.H * y.W) % bm:
+                return None
+        return consumer.bstat_slab(self.stat_rows(x, y, 1), se, plain)
+
+
+def _dgrad(route: Route, dy: Act, dx: Act, w, consumer: Optional["BNUnit"] = None, se: bool = False, plain: bool = False,
+           **igemm) -> None:
+    """The input-gradient launch dy -> dx on `route`, and the slab protocol around it: ask the unit that consumes dx for a slab,
+    launch with or without it, tell the unit that its sums are there. w: gives the GEMM-layout weight (a stale copy is re-laid
+    when it is asked for, behind the slab's queries)."""
+    if se:
+        route = route.per_image()
+    slab = route.sums_slab(consumer, se, dy, dx, plain)
+    route.launch(dy, dx, w(), 1, slab[0] if slab else None, bstat=slab[1] if slab else None, **igemm)
+    if slab:
+        consumer.bred_ready = True
+
+
+class BNUnit:
+    """The BatchNorm half of a conv -> BatchNorm [-> ReLU] unit (ConvBN here, deeplab.ConvUnit): its buffers, the forward
+    tail from the convolution's statistics slab to scale / shift, and in backward the slab of sums a producer GEMM fills, the
+    choice between that slab and the unit's own reduce pass, and the coefficient launches. A subclass sets ctx, bn, x, y, cout
+    and M (values per channel) before _bn_buffers."""
+    relu = True
+
+    def _bn_buffers(self, stat_rows: int, B: int, Ho: int, cr: int, k12: bool = False) -> None:
+        """stat_rows: rows the forward convolution writes (Route.stat_rows). cr: SE hidden width the coefficient workspace has
+        room for. k12: k1 / k2 as ONE buffer (SyncBN all-reduces both coefficient vectors at once)."""
+        ctx, cout = self.ctx, self.cout
+        self.stat_rows = stat_rows
+        self.stats = ctx.f32(stat_rows, 2, cout)
+        # BN partial sums: slabs with many rows are folded to <= 64 rows first, bn_finalize folds the rest
+        self.stat_rps = 0 if stat_rows <= STAT_PREFOLD_ROWS else max(64, -(-stat_rows // 64))
+        self.fold_rows = stat_rows if not self.stat_rps else -(-stat_rows // self.stat_rps)
+        self.sums = ctx.f32(self.fold_rows, 2, cout) if self.stat_rps else self.stats
+        self.scale, self.shift, self.mean, self.invstd = (ctx.f32(cout) for _ in range(4))
+        if k12:
+            self.k12 = ctx.f32(2, cout)
+            self.k1, self.k2 = self.k12[0], self.k12[1]
+        else:
+            self.k1, self.k2 = ctx.f32(cout), ctx.f32(cout)
+        self._ticket = None                               # last-arriver counter of the single-launch coefficient stages
+        self.sync_sums = None                             # [2][C] batch sums of this replica (SyncBN only)
+        self.sync = None
+        self.red_rpp = _rows_per_part(B, Ho)
+        self.red_rows = -(-Ho // self.red_rpp)
+        self.red_part = ctx.f32(B * self.red_rows, 2, cout)
+        self.bwd_ws = ctx.f32(B * (3 * cout + cr))
+        # BatchNorm-backward sums written by the epilogue of the GEMM that produces this unit's incoming gradient
+        # (InsarBstat): slab [B * bred_rows][2][C]; bred_ready is set by that GEMM's launch (_dgrad) and consumed by backward
+        self.bred, self.bred_rows, self.bred_ready = None, 0, False
+        self.bred_plain, self._mask_off = False, None
+
+    def bstat_slab(self, rows_total: int, per_image: bool, plain: bool = False):
+        """(slab, (y, scale, shift)) for a producer GEMM whose statistics slab has `rows_total` rows, or None if this unit
+        cannot take its backward sums from it. per_image: the rows are whole-image groups in image order (an SE unit's
+        coefficient stage folds them per image); else any partition will do and the slab is padded with zero rows to a
+        multiple of B (the coefficient stage sums B equal groups). plain: sums without the unit's own ReLU mask (a residual
+        block's last unit, whose gradient arrives already gated by the block's ReLU: scale 0 / shift 1 make the mask all-ones)."""
+        B = self.x.B
+        if (not self.relu and not plain) or (per_image and rows_total % B):
+            return None
+        rows = -(-rows_total // B)
+        if self.bred is None or self.bred_rows != rows:
+            self.bred, self.bred_rows = self.ctx.f32(B * rows, 2, self.cout), rows
+        self.bred_plain = plain
+        if plain:
+            if self._mask_off is None:
+                self._mask_off = (torch.zeros(self.cout, device=self.ctx.device), torch.ones(self.cout, device=self.ctx.device))
+            return self.bred, (self.y, self._mask_off[0], self._mask_off[1])
+        return self.bred, (self.y, self.scale, self.shift)
+
+    def _bn_finalize(self, training: bool, conv_bias: int = 0) -> None:
+        """From the statistics slab the convolution wrote to scale / shift / mean / invstd (and the running statistics)."""
+        s = _lib.stream_ptr()
+        if training and self.stat_rps:
+            call("insar_colsum_partial", ptr(self.stats), ptr(self.sums), self.stat_rows, 2 * self.cout, self.stat_rps, s)
+        part, rows, count = ptr(self.sums), self.fold_rows, self.M
+        if self.sync:
+            import torch.distributed as dist
+            pg, world = self.sync
+            if self.sync_sums is None:
+                self.sync_sums = self.ctx.f32(2 * self.cout)
+            self.ctx.colsum(self.sums, self.sync_sums, 1, self.fold_rows, 2 * self.cout)
+            dist.all_reduce(self.sync_sums, op=dist.ReduceOp.SUM, group=pg)
+            part, rows, count = ptr(self.sync_sums), 1, self.M * world
+        d = bn_finalize_desc(self.bn, part, rows, count, self.cout, training, conv_bias,
+                             ptr(self.scale), ptr(self.shift), ptr(self.mean), ptr(self.invstd))
+        call("insar_bn_finalize", C.byref(d), s)
+
+    def _take_sums(self, relu: bool = True, usable: bool = True):
+        """(slab, rows per image, fused) of the backward sums: the slab a producer GEMM filled (fused: no reduce pass is due)
+        if it did, the caller can use it and it was taken with / without the ReLU mask as this backward wants it; else red_part."""
+        fused = self.bred_ready and usable and relu != self.bred_plain
+        self.bred_ready = False
+        return (self.bred, self.bred_rows, True) if fused else (self.red_part, self.red_rows, False)
+
+    def _coef(self, coef_args, s, se) -> None:
+        """The backward coefficients. A unit without an SE gate: one channel-parallel launch over all slab rows
+        (insar_bn_bwd_coef; COEF_SIMPLE=0: the per-image stage + batch fold in one launch, stage 2 by the work-group that
+        finishes stage 1 last). With a gate: two launches (stage 2 carries the SE weight gradients)."""
+        if COEF_SIMPLE and se is None:       # no SE gate: the coefficients are linear in the slab rows — one channel-parallel launch
+            call("insar_bn_bwd_coef", coef_args[0], coef_args[1], coef_args[2] * self.x.B, coef_args[3], coef_args[6], coef_args[7], s)
+        elif COEF_FUSE and se is None:
+            if self._ticket is None:
+                self._ticket = torch.zeros(1, dtype=torch.int32, device=self.ctx.device)
+            call("insar_bnse_bwd_coef_fused", *coef_args, ptr(self._ticket), s)
+        else:
+            call("insar_bnse_bwd_coef", *coef_args, s)
+
+
+class ConvBN(BNUnit):
     """conv3x3 (bias) -> BatchNorm2d -> ReLU, the unit DoubleConv is made of (:81-86)."""
 
     def __init__(self, ctx: Ctx, conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d, x: Act, name: str):
@@ -695,70 +855,31 @@ class ConvBN:
             raise _lib.InsarError(f"{name}: out_channels={self.cout} must be a multiple of 64 on the HIP path")
         self.M = B * H * W
         self.y = Act.alloc(B, H, W, self.cout, ctx.dtype, ctx.device)           # raw conv output (no bias)
-        # large grids: flat-padded kernel (A rows shared by the three dx taps); else the per-tap implicit GEMM
-        # 64 -> 64 channels in bf16: persistent register-weight kernel (forward and input gradient)
         c64_mode = os.environ.get("INSAR_C64", "1")           # diagnostic: 0 = off, fwd / bwd = that direction only
-        self.c64 = (not self.small) and bool(call("insar_conv3x3_c64_ok", x.ref, self.cout)) and c64_mode != "0"
-        self.c64_fwd, self.c64_bwd = self.c64 and c64_mode != "bwd", self.c64 and c64_mode != "fwd"
-        self.flat_fwd = (not self.small) and not self.c64 and bool(call("insar_conv3x3_flat_ok", x.ref, self.cout))
-        self.flat_bwd = (not self.small) and not self.c64 and bool(call("insar_conv3x3_flat_ok", x.ref, self.cin))
-        # the rest: per-tap implicit GEMM, or (bf16, where that kernel would not run its 256 x 256 tiles) the flat kernel's row tiles
-        plain = not (self.small or self.c64)
-        self.rows_fwd = _rows_flags(x, self.cout) if (plain and not self.flat_fwd) else 0
-        self.rows_bwd = _rows_flags(x, self.cin, self.cout, flip=1) if (plain and not self.flat_bwd) else 0
-        if self.small:
-            self.stat_rows = call("insar_conv3x3_small_fwd_rows", x.ref, self.y.ref)
-        elif self.rows_fwd:
-            self.stat_rows = call("insar_conv3x3_flat_stat_rows", x.ref, self.cout, self.rows_fwd)
-        elif self.c64_fwd:
-            self.stat_rows = call("insar_conv3x3_c64_rows", x.ref)
-        elif self.c64:
-            self.stat_rows = call("insar_igemm_num_mtiles", self.M, self.cout)
-        elif self.flat_fwd:
-            self.stat_rows = call("insar_conv3x3_flat_stat_rows", x.ref, self.cout, _flat_flags(0, x))
-        else:
-            self.stat_rows = call("insar_igemm_num_mtiles", self.M, self.cout)
-        self.stats = ctx.f32(self.stat_rows, 2, self.cout)
-        # BN partial sums: slabs with many rows are folded to <= 64 rows first, bn_finalize folds the rest
-        self.stat_rps = 0 if self.stat_rows <= STAT_PREFOLD_ROWS else max(64, -(-self.stat_rows // 64))
-        self.fold_rows = self.stat_rows if not self.stat_rps else -(-self.stat_rows // self.stat_rps)
-        self.sums = ctx.f32(self.fold_rows, 2, self.cout) if self.stat_rps else self.stats
-        self.scale, self.shift = ctx.f32(self.cout), ctx.f32(self.cout)
-        self.mean, self.invstd = ctx.f32(self.cout), ctx.f32(self.cout)
-        self.k12 = ctx.f32(2, self.cout)                  # one buffer: SyncBN all-reduces both coefficient vectors at once
-        self.k1, self.k2 = self.k12[0], self.k12[1]
-        self._ticket = None                               # last-arriver counter of the single-launch coefficient stages
-        self.sync_sums = None                             # [2][C] batch sums of this replica (SyncBN only)
-        self.sync = None
-        self.red_rpp = _rows_per_part(B, H)
-        self.red_rows = -(-H // self.red_rpp)
-        self.red_part = ctx.f32(B * self.red_rows, 2, self.cout)
-        self.bwd_ws = ctx.f32(B * (3 * self.cout + max(self.cout // 16, 1)))
+        c64 = (not self.small) and bool(call("insar_conv3x3_c64_ok", x.ref, self.cout)) and c64_mode != "0"
+        self.fwd = Route("small") if self.small else self._route(self.cout, None, 0, c64, c64_mode != "bwd")
+        self.bwd = None if self.small else self._route(self.cin, self.cout, 1, c64, c64_mode != "fwd")
+        self._bn_buffers(self.fwd.stat_rows(x, self.y), B, H, max(self.cout // 16, 1), k12=True)
         self.dy = None            # gradient wrt the raw conv output (allocated on first backward)
         self.w = None if self.small else GemmWeight(ctx, conv.weight, "conv3")
-        # BatchNorm-backward sums written by the epilogue of the GEMM that produces this unit's incoming gradient
-        # (InsarBstat): slab [B * bred_rows][2][C]; bred_ready is set by that GEMM's launch and consumed by backward()
-        self.bred, self.bred_rows, self.bred_ready = None, 0, False
 
-    def bstat_slab(self, rows_total: int, per_image: bool):
-        """(slab, (y, scale, shift)) for a producer GEMM whose statistics slab has `rows_total` rows, or None if this unit
-        cannot take its backward sums from it. per_image: the rows are whole-image groups in image order (an SE unit's
-        coefficient stage folds them per image); else any partition will do and the slab is padded with zero rows to a
-        multiple of B (the coefficient stage sums B equal groups)."""
-        B = self.x.B
-        if per_image and rows_total % B:
-            return None
-        rows = -(-rows_total // B)
-        if self.bred is None or self.bred_rows != rows:
-            self.bred, self.bred_rows = self.ctx.f32(B * rows, 2, self.cout), rows
-        return self.bred, (self.y, self.scale, self.shift)
+    def _route(self, N: int, K: Optional[int], flip: int, c64: bool, c64_on: bool) -> Route:
+        """The route of the 3x3 convolution of x's grid to N channels (forward: cout; input gradient: cin, K = cout, flipped).
+        64 -> 64 channels in bf16: the persistent register-weight kernel, or with INSAR_C64 naming the other direction the
+        per-tap GEMM; large grids: the flat-padded kernel (A rows shared by the three dx taps); the rest: the per-tap implicit
+        GEMM, or (bf16, where that kernel would not run its 256 x 256 tiles) the flat kernel's row tiles."""
+        if c64:
+            return Route("c64" if c64_on else "igemm")
+        if call("insar_conv3x3_flat_ok", self.x.ref, N):
+            return Route("flat")
+        geo = _rows_flags(self.x, N, K, flip)
+        return Route("rows", geo) if geo else Route("igemm")
 
     # ---- forward: y = conv(x); BN statistics; scale/shift ---------------------------------------
     def forward_conv(self, training: bool, sync=None) -> None:
         """sync = (process group, world size): synchronised BatchNorm — the batch statistics are those of the GLOBAL batch
         (one all-reduce of this layer's [sum, sum of squares] per forward, one of [k1, k2] per backward), which makes
         data-parallel training equal to the reference's single-device batch ('BatchNorm under DP')."""
-        s = _lib.stream_ptr()
         self.sync = sync if training else None
         if training and self.M <= 1 and not sync:
             # nn.BatchNorm2d's own check (torch.nn.functional._verify_batch_size), same exception and text
@@ -766,38 +887,11 @@ class ConvBN:
                              f"torch.Size([{self.x.B}, {self.cout}, {self.x.H}, {self.x.W}])")
         if self.small:
             w = self.conv.weight.detach()
-            call("insar_conv3x3_small_fwd", self.x.ref, ptr(w), self.y.ref, ptr(self.stats) if training else 0, s)
-        elif self.c64_fwd:
-            self.ctx.join_side()          # GEMM-layout weights come from the side stream (UNetPlan.forward)
-            _conv3x3_c64(self.x, self.y, self.w.fwd(), 0, self.stats if training else None)
-        elif self.c64:
-            self.ctx.join_side()
-            _igemm(self.x, self.y, self.w.fwd(), self.cout, self.x.H, self.x.W, 1, _TAPS3, 0,
-                   stats=self.stats if training else None)
-        elif self.flat_fwd:
-            self.ctx.join_side()
-            _conv3x3_flat(self.x, self.y, self.w.fwd(), 0, self.stats if training else None)
-        elif self.rows_fwd:
-            self.ctx.join_side()
-            _conv3x3_flat(self.x, self.y, self.w.fwd(), 0, self.stats if training else None, geo=self.rows_fwd)
         else:
-            self.ctx.join_side()
-            _igemm(self.x, self.y, self.w.fwd(), self.cout, self.x.H, self.x.W, 1, _TAPS3, 0,
-                   stats=self.stats if training else None)
-        if training and self.stat_rps:
-            call("insar_colsum_partial", ptr(self.stats), ptr(self.sums), self.stat_rows, 2 * self.cout, self.stat_rps, s)
-        part, rows, count = ptr(self.sums), self.fold_rows, self.M
-        if self.sync:
-            import torch.distributed as dist
-            pg, world = self.sync
-            if self.sync_sums is None:
-                self.sync_sums = self.ctx.f32(2 * self.cout)
-            self.ctx.colsum(self.sums, self.sync_sums, 1, self.fold_rows, 2 * self.cout)
-            dist.all_reduce(self.sync_sums, op=dist.ReduceOp.SUM, group=pg)
-            part, rows, count = ptr(self.sync_sums), 1, self.M * world
-        d = bn_finalize_desc(self.bn, part, rows, count, self.cout, training, ptr(self.conv.bias) if self.conv.bias is not None else 0,
-                             ptr(self.scale), ptr(self.shift), ptr(self.mean), ptr(self.invstd))
-        call("insar_bn_finalize", C.byref(d), s)
+            self.ctx.join_side()          # GEMM-layout weights come from the side stream (UNetPlan.forward)
+            w = self.w.fwd()
+        self.fwd.launch(self.x, self.y, w, 0, self.stats if training else None)
+        self._bn_finalize(training, ptr(self.conv.bias) if self.conv.bias is not None else 0)
 
     def apply(self, dst: Act, gate: Optional[torch.Tensor], pooled: Optional[Act] = None,
               pool_arg: Optional[torch.Tensor] = None) -> None:
@@ -816,19 +910,6 @@ class ConvBN:
             return
         call("insar_bn_relu_apply", self.y.ref, ptr(self.scale), ptr(self.shift), ptr(gate), dst.ref, 1,
              _lib.stream_ptr())
-
-    def _coef(self, coef_args, s, se) -> None:
-        """The backward coefficients. A unit without an SE gate: one channel-parallel launch over all slab rows
-        (insar_bn_bwd_coef; COEF_SIMPLE=0: the per-image stage + batch fold in one launch, stage 2 by the work-group that
-        finishes stage 1 last). With a gate: two launches (stage 2 carries the SE weight gradients)."""
-        if COEF_SIMPLE and se is None:       # no SE gate: the coefficients are linear in the slab rows — one channel-parallel launch
-            call("insar_bn_bwd_coef", coef_args[0], coef_args[1], coef_args[2] * self.x.B, coef_args[3], coef_args[6], coef_args[7], s)
-        elif COEF_FUSE and se is None:
-            if self._ticket is None:
-                self._ticket = torch.zeros(1, dtype=torch.int32, device=self.ctx.device)
-            call("insar_bnse_bwd_coef_fused", *coef_args, ptr(self._ticket), s)
-        else:
-            call("insar_bnse_bwd_coef", *coef_args, s)
 
     def _sync_k(self) -> None:
         """SyncBN backward: k1 = mean(g*mask), k2 = mean(g*mask*xhat) over the GLOBAL batch = the mean over the replicas of
@@ -858,6 +939,8 @@ class ConvBN:
                       and call("insar_conv3x3_small_wgrad_fused_ok", self.x.ref, dout.ref) == 1)
         if self.dy is None and not fuse_small:
             self.dy = Act.alloc(B, H, W, self.cout, ctx.dtype, ctx.device)
+        # the sums may have come out of the epilogue of the GEMM that wrote dout (bstat_slab)
+        red, red_rows, fused = self._take_sums(usable=outc_grad is None and pool_grad is None)
         if outc_grad is not None:
             # (dlogits, outc weight, K[, gate, wpart]): with wpart the reduce pass also writes the output conv's own
             # parameter-gradient partials, one row per row part (OutConvPlan.backward_fused folds them)
@@ -870,12 +953,8 @@ class ConvBN:
             dpool, parg = pool_grad
             call("insar_bnrelu_bwd_reduce_pool", dout.ref, dpool.ref, ptr(parg), self.y.ref, ptr(self.scale), ptr(self.shift),
                  ptr(self.red_part), 1, self.red_rpp, s)
-        elif self.bred_ready:
-            pass                  # the sums came out of the epilogue of the GEMM that wrote dout (bstat_slab)
-        else:
+        elif not fused:
             call("insar_bnrelu_bwd_reduce", dout.ref, self.y.ref, ptr(self.scale), ptr(self.shift), ptr(self.red_part), 1, self.red_rpp, s)
-        red, red_rows = (self.bred, self.bred_rows) if (self.bred_ready and outc_grad is None and pool_grad is None) else (self.red_part, self.red_rows)
-        self.bred_ready = False
         d = bn_bwd_desc(B, H, W, self.cout, self.bn, sink, self.mean, self.invstd, self.k1, self.k2)
         if se:
             d.Cr, d.use_se = se.cr, 1
@@ -958,39 +1037,7 @@ class ConvBN:
         if dx is not None:
             if self.small:
                 raise _lib.InsarError(f"{self.name}: input gradient of the direct first-layer conv is not provided")
-            if self.c64_bwd:
-                slab = None
-                if bstat_for is not None and BSTAT_FUSE and BSTAT_C64 and not bstat_se and _same_layout(dx, bstat_for.y):
-                    slab = bstat_for.bstat_slab(call("insar_conv3x3_c64_rows", self.dy.ref), False)
-                if slab:
-                    _conv3x3_c64(self.dy, dx, self.w.dgrad(), 1, slab[0], bstat=slab[1])
-                    bstat_for.bred_ready = True
-                else:
-                    _conv3x3_c64(self.dy, dx, self.w.dgrad(), 1, None)
-            elif self.flat_bwd and not self.c64:
-                slab = None
-                if bstat_for is not None and BSTAT_FUSE and not bstat_se and _same_layout(dx, bstat_for.y):
-                    slab = bstat_for.bstat_slab(call("insar_conv3x3_flat_stat_rows", self.dy.ref, self.cin, _flat_flags(1, self.dy)), False)
-                if slab:
-                    _conv3x3_flat(self.dy, dx, self.w.dgrad(), 1, slab[0], bstat=slab[1])
-                    bstat_for.bred_ready = True
-                else:
-                    _conv3x3_flat(self.dy, dx, self.w.dgrad(), 1, None)
-            elif self.rows_bwd:
-                # row tiles are whole image rows of ONE image: the slab rows group per image, as an SE consumer needs
-                slab = None
-                geo = self.rows_bwd & ~4 if bstat_se else self.rows_bwd      # (persistent work-groups' carried sums mix images)
-                if bstat_for is not None and BSTAT_FUSE and _same_layout(dx, bstat_for.y):
-                    slab = bstat_for.bstat_slab(call("insar_conv3x3_flat_stat_rows", self.dy.ref, self.cin, geo), bstat_se)
-                _conv3x3_flat(self.dy, dx, self.w.dgrad(), 1, slab[0] if slab else None, bstat=slab[1] if slab else None, geo=geo)
-                if slab:
-                    bstat_for.bred_ready = True
-            else:
-                slab = _igemm_bstat_slab(bstat_for, bstat_se, self.M, self.cin, H * W, dx)
-                _igemm(self.dy, dx, self.w.dgrad(), self.cin, H, W, 1, _TAPS3_DGRAD, 0,
-                       stats=slab[0] if slab else None, bstat=slab[1] if slab else None)
-                if slab:
-                    bstat_for.bred_ready = True
+            _dgrad(self.bwd, self.dy, dx, self.w.dgrad, bstat_for, bstat_se)
         if WGRAD_LATE:
             weight_grad()
 
@@ -998,18 +1045,6 @@ class ConvBN:
 def _same_layout(a: Act, b: Act) -> bool:
     return (a.buf.shape == b.buf.shape and a.buf.dtype == b.buf.dtype and a.C == b.C and a.c_off == b.c_off
             and a.c_len == b.c_len)
-
-
-def _igemm_bstat_slab(consumer: Optional["ConvBN"], se: bool, M: int, N: int, hw: int, out: Act):
-    """Statistics slab + InsarBstat operands for an insar_igemm launch (mode 0, dense output `out`, M rows, N columns) whose
-    output is `consumer`'s incoming gradient, or None: BSTAT_FUSE off, layouts differ, or — for a unit with an SE gate,
-    whose coefficient stage needs the sums per image — GEMM row tiles that straddle images."""
-    if consumer is None or not BSTAT_FUSE or not _same_layout(out, consumer.y):
-        return None
-    bm = call("insar_igemm_tile_rows", M, N)
-    if se and hw % bm:
-        return None
-    return consumer.bstat_slab(call("insar_igemm_num_mtiles", M, N), se)
 
 
 def _wgrad_conv3(ctx: Ctx, x: Act, dy: Act, grad: torch.Tensor) -> None:
@@ -1307,11 +1342,8 @@ class UpPlan:
             weight_grad()
         if dx is not None:
             unit = consumer.u2 if (consumer is not None and consumer.pool_arg is None) else None
-            slab = _igemm_bstat_slab(unit, consumer is not None and consumer.se is not None, B * h * w, self.cin, h * w, dx)
-            _igemm(dout, dx, self.w.dgrad(), self.cin, h, w, 2, _TAPS2, 0,
-                   stats=slab[0] if slab else None, bstat=slab[1] if slab else None)
-            if slab:
-                unit.bred_ready = True
+            _dgrad(Route("igemm"), dout, dx, self.w.dgrad, unit, consumer is not None and consumer.se is not None,
+                   stride=2, taps=_TAPS2)
         if WGRAD_LATE:
             weight_grad()
 
