@@ -627,6 +627,59 @@ int insar_regions_number(const uint8_t* mask, int32_t H, int32_t W, int64_t min_
 int insar_regions_relabel(const uint8_t* mask, const float* conf /*nullable*/, int32_t H, int32_t W, int32_t max_regions,
                           void* scratch, void* table, int32_t* labels, uint8_t* mask_out, void* stream);
 
+/* ---- splitting touching sites (build-side addition; the reference has no post-processing): csrc/split.hip ------------------
+ * A watershed of a height map inside every label of a label map. labels int32 [H][W] (row-major, H * W < 2^31): a value <= 0 is
+ * background, every other value a region; height int32 [H][W], >= 0 on the foreground (a negative one is counted in the
+ * header and the result is then meaningless). key(p) = (height[p], -index(p)). Every foreground pixel points to the
+ * greatest-key pixel among itself and its 8 neighbours of the same label; the pixels that point to themselves are the roots of
+ * the basins; saddle(a, b) of two basins of one label is the maximum of min(height[p], height[q]) over 8-adjacent p in a, q in
+ * b. Pieces start as the basins and merge in synchronous rounds: every piece u finds the neighbouring piece v with the greatest
+ * (saddle(u, v), key(root v)) and merges into it iff depth(height[root u], saddle) <= threshold and key(root v) > key(root u),
+ * where depth(P, S) = isqrt(256 P) - isqrt(256 S) (sixteenths of a pixel between two squared distances) with `squared`, else
+ * P - S. Pieces are numbered 1..M by ascending smallest row-major pixel index. Integers only: bitwise reproducible.
+ * One call per phase, in this order on one stream; no work-group waits on another. Every argument is checked before the
+ * device is touched.
+ *   scratch: insar_split_scratch_bytes(...) bytes, 16-byte aligned: int32 basin / piece [H*W], up [H*W], next / id [H*W],
+ *            best index / first pixel [H*W], uint64 best word [H*W], block counts, the control words, the saddle table
+ *            (2^k >= 2 max_pairs slots of 16 bytes) and the edge list (max_pairs x 16 bytes). Nothing in it has to survive
+ *            between calls or be cleared by the caller. The control words are int32 [8 + max_rounds] at `ctrl_offset`:
+ *            0 the TRUE number of basin pairs (may exceed max_pairs), 1 non-zero iff the saddle table overflowed, 2 the number
+ *            of negative heights on the foreground, 3 the number of basins, 4 M (after finish), 8 + r the merges that round
+ *            r decided (an upper bound: zero iff the round merged nothing).
+ *   table:   InsarSplitRegion [1 + max_regions], 16-byte aligned. Record 0 is the header: area = M, the TRUE number of pieces,
+ *            which may exceed max_regions; sum_y / sum_x / sum_conf = control words 0 / 1 / 2; y0 = control word 3. Records
+ *            1..min(M, max_regions) are the pieces; the kernels never write past record max_regions. */
+typedef struct InsarSplitRegion {
+  int64_t area;            /* pixels (header record: M) */
+  int64_t sum_y, sum_x;    /* centroid = sum / area */
+  int64_t sum_conf;        /* sum of llrint(clamp(conf, 0, 1) * 2^30); 0 without conf */
+  int32_t y0, x0, y1, x1;  /* half-open bounding box */
+  int32_t first;           /* smallest row-major pixel index */
+  int32_t cls;             /* mask[first]; 0 without mask */
+  int32_t parent;          /* labels[first]: the region the piece was cut from */
+  int32_t peak;            /* height at the piece's root */
+  int32_t peak_index;      /* row-major index of the root */
+  int32_t saddle;          /* greatest saddle towards a neighbouring piece; -1 if there is none */
+  int32_t _pad[2];
+} InsarSplitRegion;
+/* host only: bytes of scratch and of a table, and where the control words lie in the scratch. 1 <= max_pairs <= 2^24,
+ * 1 <= max_rounds <= 4096, max_regions >= 1. */
+int insar_split_scratch_bytes(int32_t H, int32_t W, int32_t max_regions, int64_t max_pairs, int32_t max_rounds,
+                              int64_t* scratch_bytes, int64_t* table_bytes, int64_t* ctrl_offset, int64_t* ctrl_bytes);
+/* 5 launches: clear, ascent, resolve (basin of every pixel), saddles (pair table; piece state of every basin), compact (edge
+ * list; control words 0..3 are final afterwards). */
+int insar_split_basins(const int32_t* labels, const int32_t* height, int32_t H, int32_t W, int64_t max_pairs, int32_t max_rounds,
+                       void* scratch, void* stream);
+/* 4 launches per round (best saddle, tie on the root index, decide, compress), over the edge list only: rounds first_round ..
+ * first_round + n_rounds - 1 <= max_rounds - 1. A round after the fixed point changes nothing. 0 <= threshold <= 2^20. */
+int insar_split_rounds(const int32_t* height, int32_t H, int32_t W, int32_t squared, int32_t threshold, int32_t first_round,
+                       int32_t n_rounds, int64_t max_pairs, int32_t max_rounds, void* scratch, void* stream);
+/* 6 launches: remaining saddles, piece and first pixel of every pixel, count / scan / number, relabel: labels_out int32 [H][W]
+ * (0 or the piece id) and the table. mask uint8 [H][W] and conf fp32 [H][W] nullable. */
+int insar_split_finish(const int32_t* labels, const int32_t* height, const uint8_t* mask /*nullable*/, const float* conf /*nullable*/,
+                       int32_t H, int32_t W, int32_t max_regions, int64_t max_pairs, int32_t max_rounds, void* scratch, void* table,
+                       int32_t* labels_out, void* stream);
+
 /* ---- region outlines (build-side addition; the reference has no post-processing): csrc/outline.hip ------------------------
  * The exact pixel-edge ("crack") outline of every region of a label map `labels` int32 [H][W] (row-major; 0 or an id >= 1, as
  * insar_regions_relabel writes it, but any int32 map is legal; H, W >= 1, H * W < 2^29), as ordered, closed rings of lattice

@@ -20,6 +20,7 @@ from .outlines import OutlineScratch, region_outlines, to_geojson, to_polygons  
 from .simplify import SimplifyScratch, simplify_outlines  # noqa: F401
 from .skeletons import SkeletonScratch, skeleton_table, thin_regions  # noqa: F401
 from .zonal import ZonalScratch, percentile, region_stats  # noqa: F401
+from .split import SplitScratch, split_regions  # noqa: F401
 from .rasterise import PolygonTable, RasterScratch, from_geojson, labels_from_geojson, pack_polygons, rasterise_polygons  # noqa: F401
 
 __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "ChannelAttentionModule", "MaxPool2d", "CrossEntropyLoss", "DiceLoss", "DiceCELoss", "Adam", "GraphedTrainStep",
@@ -35,4 +36,4 @@ __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "Cha
            "OutlineScratch", "region_outlines", "to_polygons", "to_geojson", "SimplifyScratch", "simplify_outlines",
            "SkeletonScratch", "thin_regions", "skeleton_table",
            "PolygonTable", "RasterScratch", "pack_polygons", "from_geojson", "rasterise_polygons", "labels_from_geojson",
-           "ZonalScratch", "region_stats", "percentile"]
+           "ZonalScratch", "region_stats", "percentile", "SplitScratch", "split_regions"]

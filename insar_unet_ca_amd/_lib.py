@@ -220,6 +220,10 @@ _SIGNATURES = {
     "insar_regions_flatten": [_I, _I, _P, _P],
     "insar_regions_number": [_P, _I, _I, _L, _I, _P, _P, _P],
     "insar_regions_relabel": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "insar_split_scratch_bytes": [_I, _I, _I, _L, _I, _P, _P, _P, _P],
+    "insar_split_basins": [_P, _P, _I, _I, _L, _I, _P, _P],
+    "insar_split_rounds": [_P, _I, _I, _I, _I, _I, _I, _L, _I, _P, _P],
+    "insar_split_finish": [_P, _P, _P, _P, _I, _I, _I, _L, _I, _P, _P, _P, _P],
     "insar_outline_scratch_bytes": [_I, _I, _I, _I, _P, _P],
     "insar_outline_launches": [_I],
     "insar_outline_edges": [_P, _I, _I, _I, _I, _P, _P, _P],

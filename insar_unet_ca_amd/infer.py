@@ -283,7 +283,8 @@ class ScenePredictor:
         return _finalize(acc, wsum, return_prob)
 
     def detect(self, scene, return_prob: bool = False, outlines: bool = False, skeletons: bool = False,
-               max_iterations: int = 32, measure: Optional[dict] = None, simplify: Optional[float] = None, **region_kwargs) -> dict:
+               max_iterations: int = 32, measure: Optional[dict] = None, simplify: Optional[float] = None, split=None,
+               **region_kwargs) -> dict:
         """`predict(scene)` followed by `label_regions(out["mask"], out["conf"], **region_kwargs)`: the predict outputs
         unchanged, plus "labels", "regions", "count" and the cleaned class map under "mask_clean". With `outlines=True` also
         "outlines" = `outlines.region_outlines(out["labels"])` with the connectivity the regions were labelled with, and
@@ -296,7 +297,11 @@ class ScenePredictor:
         {name: raster} or {name: (raster, kwargs)} also "stats"[name] = `zonal.region_stats(out["labels"], raster,
         count=out["count"], max_regions=..., **kwargs)`, rows aligned with out["regions"]["id"]: a raster is [H, W] or
         [C, H, W], float32, uint8 or int32, numpy or tensor (a host raster is copied once); the string "input" stands for the
-        scene that was predicted (a uint8 scene is measured as its byte values)."""
+        scene that was predicted (a uint8 scene is measured as its byte values). With `split` = True, a number (`min_depth`) or a
+        dict of `split.split_regions` keywords, the regions are cut along the necks of their distance map right after
+        `label_regions`: the pieces replace "labels", "regions" and "count" (the table gains parent, peak, peak_y, peak_x and
+        saddle), "split_rounds" and "split_converged" are added, "mask_clean" is unchanged, and outlines, skeletons and
+        `measure` run on the pieces. With None nothing of it runs."""
         if measure is not None and not isinstance(measure, dict):
             raise InsarError(f"measure: a dict of name -> raster or (raster, kwargs), got {type(measure).__name__}")
         out = dict(self.predict(scene, return_prob=return_prob))
@@ -307,6 +312,8 @@ class ScenePredictor:
             self._regions[key] = RegionScratch(H, W, out["mask"].device, max_regions)
         reg = label_regions(out["mask"], out["conf"], scratch=self._regions.get(key), **region_kwargs)
         out.update(labels=reg["labels"], regions=reg["regions"], count=reg["count"], mask_clean=reg["mask"])
+        if split is not None and split is not False:
+            self._split(out, split, max_regions)
         if simplify is not None and not outlines:
             raise InsarError("detect: simplify needs outlines=True")
         if outlines and simplify is not None:
@@ -318,6 +325,30 @@ class ScenePredictor:
         if measure is not None:
             self._measure(out, scene, measure, max_regions)
         return out
+
+    def _split(self, out: dict, split, max_regions: int) -> None:
+        from .split import DEFAULT_MAX_PAIRS, MAX_PAIRS, MAX_ROUNDS, SplitScratch, split_regions
+        if split is True:
+            kw = {}
+        elif isinstance(split, dict):
+            kw = dict(split)
+        elif isinstance(split, (int, float, np.integer, np.floating)) and not isinstance(split, bool):
+            kw = {"min_depth": split}
+        else:
+            raise InsarError(f"split: True, a number (min_depth) or a dict of split_regions keywords, got {split!r}")
+        for name in ("mask", "conf", "scratch"):
+            if name in kw:
+                raise InsarError(f"split: {name!r} is detect's to give")
+        kw.setdefault("max_regions", max_regions)
+        H, W = out["labels"].shape
+        key = (H, W, out["labels"].device, kw["max_regions"], kw.get("max_pairs", DEFAULT_MAX_PAIRS), kw.get("max_rounds", 64))
+        cache = self.__dict__.setdefault("_splits", {})
+        limits = (None, MAX_PAIRS, MAX_ROUNDS)                    # anything else is split_regions's to refuse by name
+        if key not in cache and all(isinstance(k, int) and k >= 1 and (m is None or k <= m) for k, m in zip(key[3:], limits)):
+            cache[key] = SplitScratch(H, W, key[2], *key[3:])
+        sp =split_regions(out["labels"], mask=out["mask_clean"], conf=out["conf"], scratch=cache.get(key), **kw)
+        out.update(labels=sp["labels"], regions=sp["regions"], count=sp["count"], split_rounds=sp["rounds"],
+                   split_converged=sp["converged"])
 
     def _measure(self, out: dict, scene, measure: dict, max_regions: int) -> None:
         from .zonal import ZonalScratch, region_stats
@@ -423,7 +454,7 @@ def predict_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw
 
 def detect_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw) -> dict:
     """One-shot ScenePredictor(model, ...).detect(scene, return_prob, ...): tile / overlap / batch / num_classes / tta go to
-    the predictor, `outlines`, `simplify`, `skeletons`, `max_iterations` and `measure` to `detect`, every other keyword to
+    the predictor, `outlines`, `simplify`, `skeletons`, `max_iterations`, `measure` and `split` to `detect`, every other keyword to
     `label_regions`."""
     pred_kw = {k: kw.pop(k) for k in ("tile", "overlap", "batch", "num_classes", "tta") if k in kw}
     return ScenePredictor(model, **pred_kw).detect(scene, return_prob=return_prob, **kw)
