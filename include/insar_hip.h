@@ -1058,6 +1058,60 @@ int insar_crops_draw(uint64_t key, int32_t n, int32_t K, int32_t tries, const fl
 int insar_crops_gather(const void* scene, int32_t scene_dtype, const uint8_t* labels, int32_t H, int32_t W, const int32_t* origins,
                        int32_t n, int32_t T, float* images, void* masks, int32_t mask_dtype, void* stream);
 
+/* ---- resampling rasters: fixed-point affine warp and multilook (build-side addition; the reference resizes tiles on the
+ * host): csrc/warp.hip ------------------------------------------------------------------------------------------------------
+ * A WARP is six int64 {a, b, c, d, e, f} in Q32 that take the pixel INDICES (x, y) of a destination h x w to a source H x W,
+ * H * W < 2^31; an integer index is a pixel centre. Per destination pixel, in int64 with wrap-around:
+ *   SXq = a x + b y + c, SYq = d x + e y + f;  sx = (SXq + 2^23) >> 24, sy = (SYq + 2^23) >> 24    (arithmetic shifts)
+ * are the source position in 1/256 pixel. The pixel is INSIDE iff -128 <= sx < 256 W - 128 and -128 <= sy < 256 H - 128: its
+ * centre lies on the source's pixel extent. Every other pixel is written as the fill value. For an inside pixel:
+ *   nearest:  ix = (sx + 128) >> 8, iy = (sy + 128) >> 8; the value is src[iy][ix].
+ *   bilinear: ix = sx >> 8, fx = sx & 255, iy = sy >> 8, fy = sy & 255; the taps v00 = src[y0][x0], v01 = src[y0][x1],
+ *             v10 = src[y1][x0], v11 = src[y1][x1] with x0 = max(ix, 0), x1 = min(ix + 1, W - 1), y0, y1 likewise.
+ *     uint8:   (v00 (256 - fx)(256 - fy) + v01 fx (256 - fy) + v10 (256 - fx) fy + v11 fx fy + 32768) >> 16, integers only.
+ *     float32: ((v00 * (256 - fx) + v01 * fx) * (256 - fy) + (v10 * (256 - fx) + v11 * fx) * fy) * 2^-16, the weights
+ *              converted to float32, every product and sum rounded to float32 in that order (no fused multiply-add). NaN
+ *              and infinity follow IEEE: a NaN tap gives NaN, also where its weight is 0. A NaN result is stored as the
+ *              quiet NaN 0x7fc00000, whatever payload the operations handed on.
+ * Nothing is read back, there are no atomics: every output is bitwise defined (tests/warp_ref.py restates all of it). Every
+ * argument is checked before the device is touched (INSAR_E_ARG, INSAR_E_SHAPE, INSAR_E_DTYPE, INSAR_E_ALIGN). */
+enum { INSAR_WARP_U8 = 0, INSAR_WARP_I32 = 1, INSAR_WARP_F32 = 2 };
+enum { INSAR_WARP_NEAREST = 0, INSAR_WARP_BILINEAR = 1 };
+/* dst [n][C][h][w] of the source's dtype <- src [C][H][W] (1 <= C <= 4) through the n warps of the device table `matrices`
+ * int64 [n][6]; h, w <= 32768. fill_bits: the fill value's bits (uint8: the low byte). valid (nullable): uint8 [n][h][w], 1
+ * where inside, else 0. Bilinear on int32 is refused. 16-byte stores (uint8: 4-byte) where w % 4 == 0 and dst is aligned to
+ * them, element-wise stores otherwise: misalignment is no error. 1 launch. */
+int insar_warp_raster(const void* src, int32_t dtype /*INSAR_WARP_U8 ...*/, int32_t C, int32_t H, int32_t W, const int64_t* matrices,
+                      int32_t n, int32_t h, int32_t w, int32_t mode /*INSAR_WARP_NEAREST ...*/, uint32_t fill_bits, void* dst,
+                      uint8_t* valid /*nullable*/, void* stream);
+/* The warped counterpart of insar_crops_gather, same arguments with the table of warps in place of the origins and T x T
+ * outputs (T % 4 == 0, T <= 32768): images float32 [n][1][T][T] <- bilinear; a uint8 scene's interpolated integer v then
+ * goes through x = v / 255; (x - 0.5) / 0.5 in float32 as insar_scene_gather does, a float32 scene's value is stored as it
+ * is. masks <- nearest. Outside pixels: image `fill`, label 255. With warps {2^32, 0, x0 2^32, 0, 2^32, y0 2^32} of tiles
+ * inside the scene the outputs equal insar_crops_gather's bit for bit (float32 scenes: finite values). 1 launch. */
+int insar_warp_gather(const void* scene, int32_t scene_dtype, const uint8_t* labels, int32_t H, int32_t W, const int64_t* matrices,
+                      int32_t n, int32_t T, float fill, float* images, void* masks, int32_t mask_dtype, void* stream);
+/* matrices int64 [n][6] <- one random rotation and zoom per sample about the centre of the T x T tile at origins[i] = (y0, x0)
+ * (device int32 [n][2], as insar_crops_draw writes them). angles: device int32 [1024][2], entry j = {rint(cos(2 pi j / 1024)
+ * 2^30), rint(sin(2 pi j / 1024) 2^30)} computed by the host in float64. 0 <= amax <= 512; zoom in Q8, source pixels per
+ * output pixel, 1 <= zoom_lo <= zoom_hi <= 4096. With r = aug_hash64(key ^ 0x9FB21C651E98DF25, i) (above):
+ *   k = (((r >> 32) (2 amax + 1)) >> 32) - amax;  z = zoom_lo + (((r & 0xffffffff) (zoom_hi - zoom_lo + 1)) >> 32)
+ *   (cs, sn) = angles[k & 1023];  a = e = (z cs + 32) >> 6;  b = (-(z sn) + 32) >> 6;  d = (z sn + 32) >> 6     (Q38 -> Q32)
+ *   c = ((2 x0 + T - 1) << 31) - (((a + b) (T - 1)) >> 1);  f = ((2 y0 + T - 1) << 31) - (((d + e) (T - 1)) >> 1)
+ * in int64 with wrap-around: the index x0 + (T - 1) / 2 of the tile's centre (x0 + T / 2 from the tile's corner) maps to
+ * itself. amax = 0 with zoom_lo = zoom_hi = 256 gives {2^32, 0, x0 2^32, 0, 2^32, y0 2^32}. 1 launch. */
+int insar_warp_draw(uint64_t key, const int32_t* origins, int32_t n, int32_t T, int32_t amax, int32_t zoom_lo, int32_t zoom_hi,
+                    const int32_t* angles, int64_t* matrices, void* stream);
+/* dst [C][h][w] <- the mean of src [C][H][W] (uint8 or float32, INSAR_WARP_U8 / _F32) over boxes of fy x fx pixels, 1 <= fy,
+ * fx <= 16, h = H / fy, w = W / fx (floor: the remainder rows and columns are dropped).
+ *   uint8:   (sum + n / 2) / n with n = fy fx, integers; count (nullable, int32 [C][h][w]) = n.
+ *   float32: the values that are not NaN are added to a float32 sum that starts at +0, box rows top to bottom and each row left
+ *            to right, every sum rounded to float32; the result is sum / (float32) count, or NaN where count < min_valid
+ *            (1 <= min_valid <= fy fx); count = the number of values that are not NaN. Every NaN written is 0x7fc00000.
+ * 1 launch. */
+int insar_multilook(const void* src, int32_t dtype, int32_t C, int32_t H, int32_t W, int32_t fy, int32_t fx, int32_t min_valid,
+                    void* dst, int32_t* count /*nullable*/, void* stream);
+
 /* ---- optimizer: optim.Adam(lr=1e-4) (:466,346), multi-tensor ------------------------------------
  * table: int64[ntensors][5] = {param*, grad*, exp_avg*, exp_avg_sq*, numel}; chunks: int32[nchunks][2]
  * = {tensor index, chunk index}; each chunk covers `chunk_elems` elements. */

@@ -22,6 +22,7 @@ from .skeletons import SkeletonScratch, skeleton_table, thin_regions  # noqa: F4
 from .zonal import ZonalScratch, percentile, region_stats  # noqa: F401
 from .split import SplitScratch, split_regions  # noqa: F401
 from .rasterise import PolygonTable, RasterScratch, from_geojson, labels_from_geojson, pack_polygons, rasterise_polygons  # noqa: F401
+from .warp import WarpSpec, draw_warps, gather_warped, grid_matrix, multilook, warp_raster  # noqa: F401
 
 __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "ChannelAttentionModule", "MaxPool2d", "CrossEntropyLoss", "DiceLoss", "DiceCELoss", "Adam", "GraphedTrainStep",
            "compute_metrics", "train_model", "validate_model", "save_history", "VOCSegDataset", "SyntheticTiles",
@@ -36,4 +37,5 @@ __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "Cha
            "OutlineScratch", "region_outlines", "to_polygons", "to_geojson", "SimplifyScratch", "simplify_outlines",
            "SkeletonScratch", "thin_regions", "skeleton_table",
            "PolygonTable", "RasterScratch", "pack_polygons", "from_geojson", "rasterise_polygons", "labels_from_geojson",
-           "ZonalScratch", "region_stats", "percentile", "SplitScratch", "split_regions"]
+           "ZonalScratch", "region_stats", "percentile", "SplitScratch", "split_regions",
+           "warp_raster", "grid_matrix", "multilook", "WarpSpec", "draw_warps", "gather_warped"]

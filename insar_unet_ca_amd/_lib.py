@@ -23,6 +23,8 @@ DIST_EQ, DIST_NE, DIST_EDGE = 0, 1, 2
 DIST_FAR = 0x7FFFFFFF
 RASTER_U8, RASTER_I32 = 0, 1
 ZONAL_F32, ZONAL_U8, ZONAL_I32 = 0, 1, 2
+WARP_U8, WARP_I32, WARP_F32 = 0, 1, 2
+WARP_NEAREST, WARP_BILINEAR = 0, 1
 IGEMM_OOB_ZERO = 1
 IGEMM_PINGPONG = 2
 
@@ -261,6 +263,10 @@ _SIGNATURES = {
     "insar_crops_sat": [_P, _I, _I, _I, _P],
     "insar_crops_draw": [C.c_uint64, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "insar_crops_gather": [_P, _I, _P, _I, _I, _P, _I, _I, _P, _P, _I, _P],
+    "insar_warp_raster": [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, C.c_uint32, _P, _P, _P],
+    "insar_warp_gather": [_P, _I, _P, _I, _I, _P, _I, _I, _F, _P, _P, _I, _P],
+    "insar_warp_draw": [C.c_uint64, _P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "insar_multilook": [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "insar_adam_step": [_P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P],
     "insar_scale_f32": [_P, _L, _F, _P],
     "insar_mul_dev_f32": [_P, _P, _L, _P, _P],

@@ -4,7 +4,8 @@ per-class summed-area table of the labels (`CropIndex`) and kept away from void 
 
 The draw is a pure function of (seed, rank, step): two runs, or a run resumed from `state_dict()`, see the same stream of
 crops, and nothing is read back from the device per batch (the only read-back is one `class_pixels()` per scene when a
-`SceneCrops` is built). Per batch: insar_crops_draw, insar_crops_gather, and the two launches of `Augment` if one is given.
+`SceneCrops` is built). Per batch: insar_crops_draw, insar_crops_gather, and the two launches of `Augment` if one is given;
+with a `WarpSpec` (warp.py) insar_crops_draw, insar_warp_draw, insar_warp_gather: one launch more, still nothing read back.
 
 The draw rule (include/insar_hip.h: insar_crops_draw; tests/crops_ref.py restates it): with h(i) = aug_hash64(key, i), sample s
 uses the counter base b = 65 s; its target class is the first c with float32(h(b) >> 40) * 2^-24 < cum[c]; try t < tries has
@@ -25,6 +26,7 @@ from . import _lib
 from ._lib import InsarError, call, ptr
 from .augment import MASK64, Augment, aug_hash64
 from .infer import MAX_CLASSES, _as_scene
+from .warp import WarpSpec, draw_warps, gather_warped
 
 CROP_STREAM = 0xDA942042E4DD58B5           # separates the crop keys from the augmentation table's and the noise seeds' (NOISE_STREAM)
 SCENE_STREAM = 0x2545F4914F6CDD1D          # the second hash of a batch key, which picks the scene
@@ -225,12 +227,17 @@ class SceneCrops:
     the scenes) gives the target-class distribution; a crop is accepted with >= ceil(min_fraction tile^2) pixels of its
     target class and <= floor(max_void_fraction tile^2) void pixels, after at most `tries` (1..64) tries, else the best try
     is taken (module docstring). `last_info` is the device table int32 [batch, 4] of the last batch: target class, accepted
-    try or -1, target pixels, void pixels. `state_dict()` / `load_state_dict()` carry {seed, rank, step, config}."""
+    try or -1, target pixels, void pixels. `state_dict()` / `load_state_dict()` carry {seed, rank, step, config}.
+
+    `warp`: a `WarpSpec` rotates and zooms every crop about the centre of its drawn tile (bilinear image, nearest labels;
+    what leaves the scene is 0 in the image and void in the mask); `last_matrices` then holds the batch's Q32 warps, int64
+    [batch, 6]. None is the axis-aligned path, launch for launch. Known limit: the class-balance test of the draw and the
+    counts in `last_info` refer to the axis-aligned tile at the drawn origin, not to the warped footprint."""
 
     def __init__(self, scenes, labels, tile: int = 256, batch: int = 16, steps_per_epoch: int = 100, num_classes: int = 2,
                  class_probs: Optional[Sequence[float]] = None, min_fraction: float = 0.01, max_void_fraction: float = 0.5,
                  tries: int = 16, cell: int = 8, seed: int = 0, rank: int = 0, augment: Optional[Augment] = None,
-                 mask_dtype: torch.dtype = torch.int64, device=None):
+                 mask_dtype: torch.dtype = torch.int64, device=None, warp: Optional[WarpSpec] = None):
         self.num_classes = _check_classes(num_classes)
         self.tile, self.batch = _check_int("tile", tile, 1), _check_int("batch", batch, 1)
         self.steps_per_epoch, self.cell = _check_int("steps_per_epoch", steps_per_epoch, 1), _check_int("cell", cell, 1)
@@ -244,7 +251,9 @@ class SceneCrops:
             raise InsarError("augment must be an Augment")
         if augment is not None and mask_dtype != torch.int64:
             raise InsarError("augment returns int64 masks: mask_dtype must be torch.int64 with it")
-        self.mask_dtype, self.augment = mask_dtype, augment
+        if warp is not None and not isinstance(warp, WarpSpec):
+            raise InsarError("warp must be a WarpSpec")
+        self.mask_dtype, self.augment, self.warp = mask_dtype, augment, warp
         self.min_fraction, self.max_void_fraction = float(min_fraction), float(max_void_fraction)
         self.min_count, self.max_void = count_limits(self.tile, min_fraction, max_void_fraction)
         if isinstance(scenes, (list, tuple)) != isinstance(labels, (list, tuple)):
@@ -272,15 +281,19 @@ class SceneCrops:
         self.cum = cumulative(self.class_probs)
         self.last_info: Optional[torch.Tensor] = None
         self.last_origins: Optional[torch.Tensor] = None
+        self.last_matrices: Optional[torch.Tensor] = None
         self.last_scene: Optional[int] = None
 
     def __len__(self) -> int:
         return self.steps_per_epoch
 
     def _config(self) -> dict:
-        return {"tile": self.tile, "batch": self.batch, "num_classes": self.num_classes, "class_probs": list(self.class_probs),
-                "min_fraction": self.min_fraction, "max_void_fraction": self.max_void_fraction, "tries": self.tries,
-                "cell": self.cell, "scene_shapes": [[ix.H, ix.W] for ix in self.indices]}
+        cfg = {"tile": self.tile, "batch": self.batch, "num_classes": self.num_classes, "class_probs": list(self.class_probs),
+               "min_fraction": self.min_fraction, "max_void_fraction": self.max_void_fraction, "tries": self.tries,
+               "cell": self.cell, "scene_shapes": [[ix.H, ix.W] for ix in self.indices]}
+        if self.warp is not None:
+            cfg["warp"] = self.warp.config()
+        return cfg
 
     def state_dict(self) -> dict:
         state = make_state(self.seed, self.rank, self.step, self._config())
@@ -307,8 +320,13 @@ class SceneCrops:
         index, scene = self.indices[i], self.scenes[i]
         with torch.cuda.device(scene.device):
             origins, info = draw_crops(index, key, self.batch, self.tile, self.cum, self.min_count, self.max_void, self.tries)
-            images, masks = gather_crops(scene, index.labels, origins, self.tile, self.mask_dtype)
-        self.last_info, self.last_origins, self.last_scene = info, origins, i
+            if self.warp is None:
+                matrices = None
+                images, masks = gather_crops(scene, index.labels, origins, self.tile, self.mask_dtype)
+            else:
+                matrices = draw_warps(key, origins, self.tile, self.warp)
+                images, masks = gather_warped(scene, index.labels, matrices, self.tile, self.mask_dtype)
+        self.last_info, self.last_origins, self.last_scene, self.last_matrices = info, origins, i, matrices
         self.step += 1
         if self.augment is not None:
             images, masks = self.augment(images, masks)
