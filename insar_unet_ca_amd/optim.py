@@ -19,16 +19,79 @@ from ._lib import call, ptr
 CHUNK = int(os.environ.get("INSAR_ADAM_CHUNK", "8192"))
 
 
+# ---- what Adam, AdamW and parallel.ShardedAdam share: launch tables, their cache, the in-place state restore ---------------
+def build_tables(rows, numels, dev):
+    """The two device tensors every Adam-family kernel reads: `rows` (one list of integer words per tensor, equal widths:
+    pointers, element count, float bits) as the int64 table [n, width], and one [tensor, chunk] int32 pair per CHUNK elements
+    of each tensor (`numels`, in row order). Returns (table, chunk_t, nchunks)."""
+    chunks = [[ti, ci] for ti, n in enumerate(numels) for ci in range((n + CHUNK - 1) // CHUNK)]
+    return torch.tensor(rows, dtype=torch.int64).to(dev), torch.tensor(chunks, dtype=torch.int32).to(dev), len(chunks)
+
+
+def rows_key(rows) -> tuple:
+    """Cache key of a table: every word of every row, so a gradient or moment tensor that moved never replays an old table."""
+    return tuple(map(tuple, rows))
+
+
+class TableCache(dict):
+    """key -> launch entry ((table, chunk_t, nchunks, ...)). Bounded: emptied when it holds more than 8 entries."""
+
+    def put(self, key, entry):
+        if len(self) > 8:
+            self.clear()
+        self[key] = entry
+        return entry
+
+
+def adam_tables(cache: TableCache, tensors, key=None):
+    """(table, chunk_t, nchunks) of the plain Adam kernel for (p, g, m, v) tuples: 5 words per row."""
+    rows = [[p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()] for p, g, m, v in tensors]
+    key = rows_key(rows) if key is None else key
+    hit = cache.get(key)
+    if hit is None:
+        hit = cache.put(key, build_tables(rows, [r[4] for r in rows], tensors[0][0].device))
+    return hit
+
+
+def restore_in_place(old, state) -> bool:
+    """After torch's load_state_dict has built fresh state tensors in `state`: copy them into the tensors `old` (parameter ->
+    its state before the load) held wherever shape, dtype and device agree, and put those back, so that their addresses
+    stay what pointer tables and a captured hipGraph hold. True if nothing had to be re-allocated and no parameter lost
+    its state."""
+    in_place = True
+    for p, st in state.items():
+        prev = old.get(p)
+        for k in ("exp_avg", "exp_avg_sq", "step"):
+            new, keep = st.get(k), (prev.get(k) if prev else None)
+            if (torch.is_tensor(new) and torch.is_tensor(keep) and keep.shape == new.shape and keep.dtype == new.dtype
+                    and keep.device == new.device):
+                keep.copy_(new)
+                st[k] = keep
+            elif new is not None:
+                in_place = False
+    return in_place and not set(old) - set(state)
+
+
+def _require_device(p, g, who="AdamW", one_text=False) -> None:
+    typed = p.dtype == torch.float32 and g.dtype == torch.float32 and p.is_contiguous() and g.is_contiguous()
+    if one_text and not (p.is_cuda and typed):       # Adam on the device-side step count words both refusals as one
+        raise _lib.InsarError(f"{who} HIP path: contiguous float32 ROCm parameters and gradients only")
+    if not p.is_cuda:
+        raise _lib.InsarError(f"{who} HIP path: parameters must live on a ROCm device (no CPU fallback)")
+    if not typed:
+        raise _lib.InsarError(f"{who} HIP path: contiguous float32 parameters and gradients only")
+
+
 class Adam(torch.optim.Adam):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, **kw):
         if weight_decay != 0 or amsgrad or kw.get("maximize") or kw.get("capturable") or kw.get("differentiable"):
             raise _lib.InsarError("Adam HIP path: weight_decay=0, amsgrad=False, maximize=False only")
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False, foreach=False, fused=False)
-        self._tables = {}
+        self._tables = TableCache()
         self.grad_scale = 1.0      # multiplies every gradient inside the kernel (DP pre-scaling)
         self._dev_state = None     # float[4] on the device: step count + bias corrections (enable_device_step)
         self._dev_pending = 0      # steps taken on the device that state['step'] has not been told about yet
-        self._fast = None          # (params, grads, step tensors, table, chunks, nchunks) of the last full step
+        self._fast = None          # (params, grads, step tensors, table, chunks, nchunks, param addresses) of the last full step
         self.generation = 0        # bumped whenever optimizer state had to be re-allocated (see load_state_dict)
         self._early_tables = {}    # (plan id, stage, gradient buffer) -> (table, chunks, nchunks, params)
         self._early_done = set()   # ids of the parameters already updated inside the current backward
@@ -101,16 +164,12 @@ class Adam(torch.optim.Adam):
                 tensors.append((p, plan.sink.view(p), st["exp_avg"], st["exp_avg_sq"]))
             if not tensors:
                 return
-            table, chunk_t, nchunks = self._table(("early",) + key, tensors)
             if len(self._early_tables) > 64:
                 self._early_tables.clear()
-            hit = self._early_tables[key] = (table, chunk_t, nchunks, [t[0] for t in tensors])
+            hit = self._early_tables[key] = adam_tables(self._tables, tensors, ("early",) + key) + ([t[0] for t in tensors],)
         table, chunk_t, nchunks, params = hit
-        b1, b2 = group["betas"]
-        t = float(self.state[params[0]]["step"]) + 1.0
         with plan.ctx.side_stream():             # ordered after everything this stage has enqueued on either stream
-            call("insar_adam_step", ptr(table), ptr(chunk_t), nchunks, CHUNK, float(group["lr"]), float(b1), float(b2),
-                 float(group["eps"]), 1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t), float(self.grad_scale), _lib.stream_ptr())
+            self._launch(group, table, chunk_t, nchunks, float(self.state[params[0]]["step"]) + 1.0)
             torch._C._increment_version(params)
             ws = plan.weightset.stage_sets(plan.sink.groups)[stage]
             if ws is not None and engine.PREP_SIDE:
@@ -123,13 +182,10 @@ class Adam(torch.optim.Adam):
         done, self._early_done = self._early_done, set()
         group = self.param_groups[0]
         rest = [p for p in group["params"] if p.grad is not None and id(p) not in done]
-        b1, b2 = group["betas"]
         t = float(self.state[group["params"][0]]["step"]) + 1.0
         if rest:                                 # stages that did not take part (a plan change mid-way): the same kernel on them
             tensors = [(p, p.grad, self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"]) for p in rest]
-            table, chunk_t, nchunks = self._table(tuple(x.data_ptr() for tup in tensors for x in tup), tensors)
-            call("insar_adam_step", ptr(table), ptr(chunk_t), nchunks, CHUNK, float(group["lr"]), float(b1), float(b2),
-                 float(group["eps"]), 1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t), float(self.grad_scale), _lib.stream_ptr())
+            self._launch(group, *adam_tables(self._tables, tensors), t)
             torch._C._increment_version(rest)
         for p in group["params"]:
             st = self.state.get(p)
@@ -158,21 +214,7 @@ class Adam(torch.optim.Adam):
         self._sync_host_steps()
         old = {p: dict(st) for p, st in self.state.items()}
         super().load_state_dict(state_dict)          # builds fresh state tensors
-        in_place = True
-        for p, st in self.state.items():
-            prev = old.get(p)
-            for k in ("exp_avg", "exp_avg_sq", "step"):
-                new = st.get(k)
-                keep = prev.get(k) if prev else None
-                if (torch.is_tensor(new) and torch.is_tensor(keep) and keep.shape == new.shape and keep.dtype == new.dtype
-                        and keep.device == new.device):
-                    keep.copy_(new)
-                    st[k] = keep
-                elif new is not None:
-                    in_place = False
-        if set(old) - set(self.state):
-            in_place = False
-        if not in_place:
+        if not restore_in_place(old, self.state):
             self._fast = None
             self._tables.clear()
             self._early_tables.clear()
@@ -184,22 +226,15 @@ class Adam(torch.optim.Adam):
             keep.copy_(self._dev_state)              # ... which go into the tensor a captured graph already points at
             self._dev_state = keep
 
-    def _table(self, key, tensors):
-        hit = self._tables.get(key)
-        if hit is not None:
-            return hit
-        dev = tensors[0][0].device
-        rows, chunks = [], []
-        for ti, (p, g, m, v) in enumerate(tensors):
-            rows.append([p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()])
-            for ci in range((p.numel() + CHUNK - 1) // CHUNK):
-                chunks.append([ti, ci])
-        table = torch.tensor(rows, dtype=torch.int64).to(dev)
-        chunk_t = torch.tensor(chunks, dtype=torch.int32).to(dev)
-        if len(self._tables) > 8:
-            self._tables.clear()
-        self._tables[key] = (table, chunk_t, len(chunks))
-        return self._tables[key]
+    def _launch(self, group, table, chunk_t, nchunks, t=None) -> None:
+        """The one launch site of both kernels. t: the step count this update is, held by the host (the bias corrections
+        are computed here, in double); None: the count lives on the device (enable_device_step)."""
+        b1, b2 = group["betas"]
+        head = (ptr(table), ptr(chunk_t), nchunks, CHUNK, float(group["lr"]), float(b1), float(b2), float(group["eps"]))
+        if t is None:
+            call("insar_adam_step_dev", *head, ptr(self._dev_state), float(self.grad_scale), _lib.stream_ptr())
+        else:
+            call("insar_adam_step", *head, 1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t), float(self.grad_scale), _lib.stream_ptr())
 
     def _fast_step(self) -> bool:
         """The steady-state step: same parameters, same gradient tensors (the flat-buffer views the model hands out every
@@ -217,16 +252,12 @@ class Adam(torch.optim.Adam):
             # keep the Parameter object but move its memory, and the table holds raw addresses
             if p is not q or p.grad is not g or p.data_ptr() != a:
                 return False
-        b1, b2 = group["betas"]
         if self._dev_state is not None:
-            call("insar_adam_step_dev", ptr(table), ptr(chunk_t), nchunks, CHUNK, float(group["lr"]), float(b1), float(b2),
-                 float(group["eps"]), ptr(self._dev_state), float(self.grad_scale), _lib.stream_ptr())
+            self._launch(group, table, chunk_t, nchunks)
         else:
             for st in steps:
                 st += 1
-            t = float(steps[0])
-            call("insar_adam_step", ptr(table), ptr(chunk_t), nchunks, CHUNK, float(group["lr"]), float(b1), float(b2),
-                 float(group["eps"]), 1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t), float(self.grad_scale), _lib.stream_ptr())
+            self._launch(group, table, chunk_t, nchunks, float(steps[0]))
         torch._C._increment_version(params)
         return True
 
@@ -249,36 +280,16 @@ class Adam(torch.optim.Adam):
             self._init_group(group, params, grads, exp_avgs, exp_avg_sqs, max_sqs, steps)
             if not params:
                 continue
-            b1, b2 = group["betas"]
-            if self._dev_state is not None:
-                tensors = []
-                for p, g, m, v in zip(params, grads, exp_avgs, exp_avg_sqs):
-                    if not p.is_cuda or p.dtype != torch.float32 or g.dtype != torch.float32 or not p.is_contiguous() or not g.is_contiguous():
-                        raise _lib.InsarError("Adam HIP path: contiguous float32 ROCm parameters and gradients only")
-                    tensors.append((p, g, m, v))
-                key = tuple(x.data_ptr() for tup in tensors for x in tup)
-                table, chunk_t, nchunks = self._table(key, tensors)
-                call("insar_adam_step_dev", ptr(table), ptr(chunk_t), nchunks, CHUNK, float(group["lr"]), float(b1), float(b2),
-                     float(group["eps"]), ptr(self._dev_state), float(self.grad_scale), _lib.stream_ptr())
-                torch._C._increment_version(params)
-                if len(self.param_groups) == 1:
-                    self._fast = (list(params), list(grads), list(steps), table, chunk_t, nchunks, [p.data_ptr() for p in params])
-                continue
-            by_step = {}
+            on_dev = self._dev_state is not None
+            by_step = {}                             # step count -> its tensors, one launch each (None: the device counts)
             for p, g, m, v, st in zip(params, grads, exp_avgs, exp_avg_sqs, steps):
-                if not p.is_cuda:
-                    raise _lib.InsarError("Adam HIP path: parameters must live on a ROCm device (no CPU fallback)")
-                if p.dtype != torch.float32 or g.dtype != torch.float32 or not p.is_contiguous() or not g.is_contiguous():
-                    raise _lib.InsarError("Adam HIP path: contiguous float32 parameters and gradients only")
-                st += 1
-                by_step.setdefault(float(st), []).append((p, g, m, v))
+                _require_device(p, g, "Adam", one_text=on_dev)
+                if not on_dev:
+                    st += 1
+                by_step.setdefault(None if on_dev else float(st), []).append((p, g, m, v))
             for t, tensors in by_step.items():
-                key = tuple(x.data_ptr() for tup in tensors for x in tup)
-                table, chunk_t, nchunks = self._table(key, tensors)
-                bc1 = 1.0 - b1 ** t
-                bc2_sqrt = math.sqrt(1.0 - b2 ** t)
-                call("insar_adam_step", ptr(table), ptr(chunk_t), nchunks, CHUNK, float(group["lr"]), float(b1), float(b2),
-                     float(group["eps"]), bc1, bc2_sqrt, float(self.grad_scale), _lib.stream_ptr())
+                table, chunk_t, nchunks = adam_tables(self._tables, tensors)
+                self._launch(group, table, chunk_t, nchunks, t)
                 torch._C._increment_version([p for p, _, _, _ in tensors])
             if len(self.param_groups) == 1 and len(by_step) == 1 and len(params) == len(group["params"]):
                 self._fast = (list(params), list(grads), list(steps), table, chunk_t, nchunks, [p.data_ptr() for p in params])
@@ -328,13 +339,6 @@ def split_decay_groups(model, weight_decay: float):
     return [{"params": decay, "weight_decay": float(weight_decay)}, {"params": exempt, "weight_decay": 0.0}]
 
 
-def _require_device(p, g) -> None:
-    if not p.is_cuda:
-        raise _lib.InsarError("AdamW HIP path: parameters must live on a ROCm device (no CPU fallback)")
-    if p.dtype != torch.float32 or g.dtype != torch.float32 or not p.is_contiguous() or not g.is_contiguous():
-        raise _lib.InsarError("AdamW HIP path: contiguous float32 parameters and gradients only")
-
-
 def _float_bits(x: float) -> int:
     return struct.unpack("<I", struct.pack("<f", x))[0]
 
@@ -373,7 +377,7 @@ class AdamW(torch.optim.AdamW):
         self._dev_pending = 0      # steps enqueued since the host last synced its step count
         self._host_t = 0           # step count as of the last sync
         self._ema = {}             # parameter -> its EMA tensor
-        self._tables = {}
+        self._tables = TableCache()
         self._fast = None
 
     def enable_device_step(self) -> None:
@@ -504,19 +508,7 @@ class AdamW(torch.optim.AdamW):
         extra = state_dict.get("insar_adamw") or {}
         old = {p: dict(st) for p, st in self.state.items()}
         super().load_state_dict({k: v for k, v in state_dict.items() if k != "insar_adamw"})
-        in_place = True
-        for p, st in self.state.items():
-            prev = old.get(p)
-            for k in ("exp_avg", "exp_avg_sq", "step"):
-                new, keep = st.get(k), (prev.get(k) if prev else None)
-                if (torch.is_tensor(new) and torch.is_tensor(keep) and keep.shape == new.shape and keep.dtype == new.dtype
-                        and keep.device == new.device):
-                    keep.copy_(new)
-                    st[k] = keep
-                elif new is not None:
-                    in_place = False
-        if set(old) - set(self.state):
-            in_place = False
+        in_place = restore_in_place(old, self.state)
         steps = {float(st["step"]) for st in self.state.values() if "step" in st}
         if len(steps) > 1:
             raise _lib.InsarError("AdamW.load_state_dict: parameters have different step counts")
@@ -542,23 +534,19 @@ class AdamW(torch.optim.AdamW):
             self._write_state(self._host_t, int(extra.get("skipped", 0)))
 
     # ---- the step --------------------------------------------------------------------------------------------------
-    def _table(self, key, tensors):
+    def _table(self, tensors):
+        """(table, chunk_t, nchunks, partials, config) for (p, g, m, v, ema, weight decay, lr multiplier) tuples: 8 words per
+        row, the two floats as their float32 bits; cached by the rows and the hyper-parameters the config is made from."""
+        rows = [[p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(e), p.numel(), _float_bits(wd), _float_bits(mult)]
+                for p, g, m, v, e, wd, mult in tensors]
+        key = (rows_key(rows), self._hyper())
         hit = self._tables.get(key)
-        if hit is not None:
-            return hit
-        dev = tensors[0][0].device
-        rows, chunks = [], []
-        for ti, (p, g, m, v, e, wd, mult) in enumerate(tensors):
-            rows.append([p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(e), p.numel(), _float_bits(wd), _float_bits(mult)])
-            for ci in range((p.numel() + CHUNK - 1) // CHUNK):
-                chunks.append([ti, ci])
-        table = torch.tensor(rows, dtype=torch.int64).to(dev)
-        chunk_t = torch.tensor(chunks, dtype=torch.int32).to(dev)
-        partials = torch.zeros(len(chunks), dtype=torch.float32, device=dev) if self._norm_pass else None
-        if len(self._tables) > 8:
-            self._tables.clear()
-        self._tables[key] = (table, chunk_t, len(chunks), partials, self._config())
-        return self._tables[key]
+        if hit is None:
+            dev = tensors[0][0].device
+            table, chunk_t, nchunks = build_tables(rows, [r[5] for r in rows], dev)
+            partials = torch.zeros(nchunks, dtype=torch.float32, device=dev) if self._norm_pass else None
+            hit = self._tables.put(key, (table, chunk_t, nchunks, partials, self._config()))
+        return hit
 
     def _launch(self, table, chunk_t, nchunks, partials, cfg) -> None:
         b1, b2 = self.param_groups[0]["betas"]
@@ -630,8 +618,7 @@ class AdamW(torch.optim.AdamW):
         if not tensors:
             return loss
         self._state_block(tensors[0][0].device)
-        key = tuple(x if isinstance(x, float) else ptr(x) for tup in tensors for x in tup) + (self._hyper(),)
-        launch = self._table(key, tensors)
+        launch = self._table(tensors)
         self._launch(*launch)
         params = [t[0] for t in tensors]
         torch._C._increment_version(params)

@@ -28,7 +28,7 @@ from typing import Callable, List, Optional, Tuple
 import torch
 import torch.distributed as dist
 
-from . import _lib, engine
+from . import _lib, engine, optim
 
 
 class BucketReducer:
@@ -325,26 +325,14 @@ class DataParallel(torch.nn.Module):
 
 def _hip_adam_rows(rows, lr, b1, b2, eps, bc1, bc2_sqrt) -> None:
     """One multi-tensor launch of the Adam kernel over (p, g, m, v) rows (the product path; no CPU fallback)."""
-    from . import _lib
-    from .optim import CHUNK
-    dev = rows[0][0].device
-    if dev.type != "cuda":
+    if not rows[0][0].is_cuda:
         raise _lib.InsarError("ShardedAdam HIP path: parameters must live on a ROCm device (no CPU fallback)")
-    table, chunks = [], []
-    for ti, (p, g, m, v) in enumerate(rows):
-        table.append([p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()])
-        chunks += [[ti, ci] for ci in range((p.numel() + CHUNK - 1) // CHUNK)]
-    key = tuple(r[0] for r in table)
-    cache = _hip_adam_rows.cache
-    if key not in cache:
-        cache.clear()
-        cache[key] = (torch.tensor(table, dtype=torch.int64).to(dev), torch.tensor(chunks, dtype=torch.int32).to(dev))
-    t, c = cache[key]
-    _lib.call("insar_adam_step", _lib.ptr(t), _lib.ptr(c), c.shape[0], CHUNK, float(lr), float(b1), float(b2), float(eps),
-              float(bc1), float(bc2_sqrt), 1.0, _lib.stream_ptr())
+    table, chunk_t, nchunks = optim.adam_tables(_row_tables, rows)
+    _lib.call("insar_adam_step", _lib.ptr(table), _lib.ptr(chunk_t), nchunks, optim.CHUNK, float(lr), float(b1), float(b2),
+              float(eps), float(bc1), float(bc2_sqrt), 1.0, _lib.stream_ptr())
 
 
-_hip_adam_rows.cache = {}
+_row_tables = optim.TableCache()
 
 
 class ShardedAdam:
