@@ -1112,6 +1112,56 @@ int insar_warp_draw(uint64_t key, const int32_t* origins, int32_t n, int32_t T, 
 int insar_multilook(const void* src, int32_t dtype, int32_t C, int32_t H, int32_t W, int32_t fy, int32_t fx, int32_t min_valid,
                     void* dst, int32_t* count /*nullable*/, void* stream);
 
+/* ---- detections through a stack of dates (build-side addition; the reference works on one tile of one date):
+ * csrc/stack.hip ---------------------------------------------------------------------------------------------------------
+ * State: two device tensors hit and valid, int64 [words][H][W], 1 <= words <= 4, H * W < 2^31, 8-byte aligned. Date t of
+ * T = 64 words is bit t & 63 of plane t >> 6. A date is VALID at a pixel where it was observed, a HIT where it is valid and
+ * a detection; readers take hit & valid, so a hit bit under a cleared valid bit counts for nothing. Everything is integers,
+ * one launch per entry point on the caller's stream, loops bounded by T, no work-group waits on another, nothing is read
+ * back. Every argument is checked before the device is touched. 16-byte accesses where H * W % 4 == 0 and the pointers allow
+ * it, guarded scalars otherwise: misalignment beyond an element's own is no error. */
+/* Dates t .. t + n - 1 <- mask uint8 [n][H][W] (n >= 1, t + n <= T; the dates may cross planes). Per pixel and date:
+ *   valid bit = mask != ignore && (valid_in == NULL || valid_in != 0)          ignore in -1..255, -1: no value is ignored
+ *   hit bit   = valid && class set holds mask && (conf == NULL || conf >= min_conf)       a NaN conf: valid, no hit
+ * class set: classes_w0 .. w3, class c is bit c & 63 of word c >> 6. min_conf finite. Exactly the n bits are set or cleared;
+ * every other bit of the words keeps its value. The n planes of every input are read once; a word whose 64 bits are all
+ * written is not read. valid_in uint8 [n][H][W], conf float32 [n][H][W], both nullable. The inputs are never written. */
+int insar_stack_push(const uint8_t* mask, const uint8_t* valid_in /*nullable*/, const float* conf /*nullable*/, float min_conf,
+                     uint64_t classes_w0, uint64_t classes_w1, uint64_t classes_w2, uint64_t classes_w3, int32_t ignore, int32_t n,
+                     int32_t t, int32_t words, int32_t H, int32_t W, int64_t* hit, int64_t* valid, void* stream);
+/* The k >= 0 oldest dates dropped in place: bit t <- bit t + k across planes, the top k bits <- 0. k >= T clears the stack
+ * without reading it; k = 0 is a launch that writes nothing. */
+int insar_stack_shift(int64_t* hit, int64_t* valid, int32_t words, int32_t H, int32_t W, int32_t k, void* stream);
+/* Per pixel over the window 0 <= t0 <= t1 <= T, defined by ONE scan over t = t0 .. t1 - 1 that skips the dates whose valid
+ * bit is 0 (a missing observation neither breaks nor extends a run):
+ *   n_valid, n_hit   int16   the valid dates, the hits among them
+ *   longest_run      int16   the most consecutive hits among the valid dates
+ *   run_start        int16   the date of the first hit of that run, of the earliest such run on ties; -1: no hit
+ *   first_hit, last_hit  int16   dates, -1: no hit
+ *   known            uint8   n_valid >= min_valid
+ *   persistent       uint8   known && n_hit >= min_hits && longest_run >= min_run && n_hit * den >= num * n_valid
+ * 0 <= min_hits, min_run, min_valid <= 32767; 0 <= num <= den, 1 <= den < 2^31 (int64 products). Every plane [H][W] is
+ * nullable: a null one is neither computed into memory nor touched; all null is INSAR_E_ARG. An empty window gives 0 and -1.
+ * The kernel walks the maximal runs of (hit | ~valid) inside the window and counts the hits under each: bitwise the scan. */
+int insar_stack_summary(const int64_t* hit, const int64_t* valid, int32_t words, int32_t H, int32_t W, int32_t t0, int32_t t1,
+                        int32_t min_hits, int32_t min_run, int32_t min_valid, int32_t num, int32_t den, int16_t* n_valid,
+                        int16_t* n_hit, int16_t* longest_run, int16_t* run_start, int16_t* first_hit, int16_t* last_hit,
+                        uint8_t* known, uint8_t* persistent, void* stream);
+/* Per label of a map and per date of a window: the series table. labels int32 [H][W] as in insar_zonal_accumulate (<= 0
+ * background, 1..max_regions counted, larger ones counted in the header and nothing else). With nt = t1 - t0 (0..256) the
+ * table is int32: a header of four words (word 0: out_of_range), then max_regions rows of 1 + 2 nt words
+ *   {area, hits[nt], valids[nt]}      area: pixels of the label; hits / valids: its pixels that are hits / valid at t0 + i
+ * so the first `count` rows are one contiguous read. 1 <= max_regions <= 2^24. Call clear, then series, on one stream.
+ * Agent-scope relaxed integer atomic adds only, after folding: each wave takes 4 x 64 consecutive pixels, one ballot per date
+ * gives every run of equal labels its count (one add per run and date that is not 0); the label a work-group sees most (the
+ * vote of csrc/zonal.hip) is summed without atomics in the lanes (lane i holds date i of a plane), added per work-group in
+ * LDS when the vote changes and at the end, and sent to the table from there. hit / valid under background pixels are not
+ * read. The table is bitwise reproducible. */
+int insar_stack_series_bytes(int32_t max_regions, int32_t n_dates, int64_t* table_bytes);   /* host only; a multiple of 16 */
+int insar_stack_series_clear(void* table, int32_t max_regions, int32_t n_dates, void* stream);
+int insar_stack_series(const int64_t* hit, const int64_t* valid, int32_t words, const int32_t* labels, int32_t H, int32_t W,
+                       int32_t t0, int32_t t1, int32_t max_regions, void* table, void* stream);
+
 /* ---- optimizer: optim.Adam(lr=1e-4) (:466,346), multi-tensor ------------------------------------
  * table: int64[ntensors][5] = {param*, grad*, exp_avg*, exp_avg_sq*, numel}; chunks: int32[nchunks][2]
  * = {tensor index, chunk index}; each chunk covers `chunk_elems` elements. */

@@ -267,6 +267,12 @@ _SIGNATURES = {
     "insar_warp_gather": [_P, _I, _P, _I, _I, _P, _I, _I, _F, _P, _P, _I, _P],
     "insar_warp_draw": [C.c_uint64, _P, _I, _I, _I, _I, _I, _P, _P, _P],
     "insar_multilook": [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "insar_stack_push": [_P, _P, _P, _F, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "insar_stack_shift": [_P, _P, _I, _I, _I, _I, _P],
+    "insar_stack_summary": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "insar_stack_series_bytes": [_I, _I, _P],
+    "insar_stack_series_clear": [_P, _I, _I, _P],
+    "insar_stack_series": [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P],
     "insar_adam_step": [_P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P],
     "insar_scale_f32": [_P, _L, _F, _P],
     "insar_mul_dev_f32": [_P, _P, _L, _P, _P],

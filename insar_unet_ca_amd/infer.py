@@ -446,6 +446,53 @@ class ScenePredictor:
         out.update(score=score, gt_labels=truth["labels"], gt_regions=truth["regions"], gt_count=truth["count"])
         return out
 
+    def detect_stack(self, scenes, *, valids=None, min_conf: float = 0.0, classes=1, words: Optional[int] = None,
+                     **follow_kwargs) -> dict:
+        """One co-registered scene per date, oldest first: `predict` of each, its mask and confidence pushed into a
+        `stack.DetectionStack` (`push(mask, conf=conf, min_conf=min_conf, classes=classes, valid=valids[i])`), then
+        `stack.follow_sites(stack, **follow_kwargs)`: its result plus "stack". `valids`: None or one entry per scene, each None
+        or a uint8 [H, W] map (numpy or tensor), 0 = not observed at that date. `words`: planes of 64 dates (None: as many as
+        the scenes need). Nothing scene-sized is kept per date beyond the stack's bits: a date's mask and confidence are
+        released before the next scene is predicted."""
+        from .stack import MAX_DATES, DetectionStack, follow_sites
+        try:
+            scenes = list(scenes)
+        except TypeError:
+            raise InsarError(f"detect_stack: scenes must be a sequence of 2-D scenes, got {type(scenes).__name__}") from None
+        n = len(scenes)
+        if not 1 <= n <= MAX_DATES:
+            raise InsarError(f"detect_stack: {n} scenes: 1..{MAX_DATES}")
+        shapes = {tuple(getattr(s, "shape", ())) for s in scenes}
+        if len(shapes) != 1 or len(next(iter(shapes))) != 2:
+            raise InsarError(f"detect_stack: the scenes must share one 2-D shape (co-register them first), got {sorted(shapes)}")
+        H, W = next(iter(shapes))
+        _check_geometry(H, W, self.tile, self.overlap)
+        if valids is not None:
+            valids = list(valids)
+            if len(valids) != n:
+                raise InsarError(f"detect_stack: {len(valids)} validity maps for {n} scenes")
+        words = (n + 63) // 64 if words is None else words
+        if isinstance(words, bool) or not isinstance(words, (int, np.integer)) or not (n + 63) // 64 <= words <= 4:
+            raise InsarError(f"words={words!r}: an integer in {(n + 63) // 64}..4 for {n} scenes")
+        try:
+            device = next(self.model.parameters()).device
+        except StopIteration:
+            raise InsarError("ScenePredictor: the model has no parameters") from None
+        st = DetectionStack(H, W, device, int(words))
+        for i, scene in enumerate(scenes):
+            v = None if valids is None else valids[i]
+            if v is not None:
+                v = torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v
+                if not isinstance(v, torch.Tensor) or v.dtype != torch.uint8 or tuple(v.shape) != (H, W):
+                    raise InsarError(f"detect_stack: valids[{i}] must be a uint8 [{H}, {W}] numpy array or tensor")
+                v = v.detach().to(device).contiguous()
+            out = self.predict(scene)
+            st.push(out["mask"], conf=out["conf"], min_conf=min_conf, classes=classes, valid=v)
+            del out
+        res = follow_sites(st, **follow_kwargs)
+        res["stack"] = st
+        return res
+
 
 def predict_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw) -> Dict[str, torch.Tensor]:
     """One-shot ScenePredictor(model, **kw).predict(scene, return_prob)."""
