@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from functools import partial
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -24,6 +25,7 @@ import torch
 
 from . import _lib
 from ._lib import InsarError, call, ptr
+from ._scene import check_int
 from .augment import MASK64, Augment, aug_hash64
 from .infer import MAX_CLASSES, _as_scene
 from .warp import WarpSpec, draw_warps, gather_warped
@@ -34,14 +36,11 @@ MAX_TRIES = 64
 _MASK_CODES = {torch.uint8: _lib.AUG_MASK_U8, torch.int64: _lib.AUG_MASK_I64}
 
 
-def _check_int(name: str, v, lowest: int) -> int:
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lowest:
-        raise InsarError(f"{name}={v!r}: an integer >= {lowest}")
-    return int(v)
+_int = partial(check_int, None, integral_floats=False)        # the strict rule, the argument named without a tool
 
 
 def _check_classes(K) -> int:
-    K = _check_int("num_classes", K, 0)
+    K = _int("num_classes", K, 0)
     if not 2 <= K <= MAX_CLASSES:
         raise InsarError(f"num_classes={K}: the crop kernels cover 2..{MAX_CLASSES} classes")
     return K
@@ -131,7 +130,7 @@ class CropIndex:
 
     def __init__(self, labels, num_classes: int, cell: int = 8, device=None):
         self.num_classes = _check_classes(num_classes)
-        self.cell = _check_int("cell", cell, 1)
+        self.cell = _int("cell", cell, 1)
         if device is None:
             device = labels.device if isinstance(labels, torch.Tensor) and labels.is_cuda else torch.device("cuda")
         self.labels = _as_labels(labels, torch.device(device))
@@ -239,12 +238,12 @@ class SceneCrops:
                  tries: int = 16, cell: int = 8, seed: int = 0, rank: int = 0, augment: Optional[Augment] = None,
                  mask_dtype: torch.dtype = torch.int64, device=None, warp: Optional[WarpSpec] = None):
         self.num_classes = _check_classes(num_classes)
-        self.tile, self.batch = _check_int("tile", tile, 1), _check_int("batch", batch, 1)
-        self.steps_per_epoch, self.cell = _check_int("steps_per_epoch", steps_per_epoch, 1), _check_int("cell", cell, 1)
-        self.tries = _check_int("tries", tries, 1)
+        self.tile, self.batch = _int("tile", tile, 1), _int("batch", batch, 1)
+        self.steps_per_epoch, self.cell = _int("steps_per_epoch", steps_per_epoch, 1), _int("cell", cell, 1)
+        self.tries = _int("tries", tries, 1)
         if self.tries > MAX_TRIES:
             raise InsarError(f"tries={tries}: at most {MAX_TRIES} (one lane of a wave per try)")
-        self.seed, self.rank, self.step = _check_int("seed", seed, 0) & MASK64, _check_int("rank", rank, 0), 0
+        self.seed, self.rank, self.step = _int("seed", seed, 0) & MASK64, _int("rank", rank, 0), 0
         if mask_dtype not in _MASK_CODES:
             raise InsarError(f"mask_dtype {mask_dtype}: torch.int64 or torch.uint8")
         if augment is not None and not isinstance(augment, Augment):

@@ -16,7 +16,7 @@ where it exceeds max_distance^2 or the image has no site; `nearest` the index y 
 """
 from __future__ import annotations
 
-import ctypes as C
+from functools import partial
 from typing import Optional
 
 import numpy as np
@@ -24,45 +24,38 @@ import torch
 
 from . import _lib
 from ._lib import InsarError, call, ptr
+from ._scene import Scratch, check_int, check_map, check_on_device, pinned, query_bytes, read_back
 
 FAR = _lib.DIST_FAR
 MAX_DIM = 32767
 MAX_CLASSES = 8
+_int = partial(check_int, integral_floats=True)      # this module's integers may come as floats with an integral value
 
 
 def scratch_bytes(B: int, H: int, W: int) -> int:
     """Bytes of scratch of a B x H x W map. Host arithmetic only."""
-    s = C.c_int64(0)
-    call("insar_dist_scratch_bytes", int(B), int(H), int(W), C.byref(s))
-    return int(s.value)
+    return query_bytes("insar_dist_scratch_bytes", B, H, W, outputs=1)
 
 
-class DistanceScratch:
+class DistanceScratch(Scratch):
     """The buffers of one (B, H, W): the column pass's result and, once `boundary_counts` has used it, the counts with the
     pinned host copy they are read back into. Nothing in them has to survive between calls."""
+    KEY, SHOW, DEVICE_AT = ("B", "H", "W"), "{} x {} x {}", 3
 
     def __init__(self, B: int, H: int, W: int, device):
-        self.B, self.H, self.W = int(B), int(H), int(W)
-        self.scratch = torch.empty(scratch_bytes(B, H, W), dtype=torch.uint8, device=device)
+        super().__init__((B, H, W), device, scratch=scratch_bytes(B, H, W))
         self.counts = self.host = None
 
     def count_buffers(self):
         if self.counts is None:
             self.counts = torch.empty(MAX_CLASSES * 3, dtype=torch.int64, device=self.scratch.device)
-            self.host = torch.empty(MAX_CLASSES * 3, dtype=torch.int64, pin_memory=True)
+            self.host = pinned(MAX_CLASSES * 3, torch.int64)
         return self.counts, self.host
 
 
-def _check_map(who: str, name: str, m, dtypes=(torch.uint8, torch.int32)):
+def _map_dims(who: str, name: str, m, dtypes=(torch.uint8, torch.int32)):
     """(B, H, W) of a 2-D or 3-D map; everything but the device is checked here."""
-    if not isinstance(m, torch.Tensor):
-        raise InsarError(f"{who}: {name} must be a torch tensor, got {type(m).__name__}")
-    if m.dtype not in dtypes:
-        raise InsarError(f"{who}: {name} must be {' or '.join(str(d).replace('torch.', '') for d in dtypes)}, got {m.dtype}")
-    if m.dim() not in (2, 3):
-        raise InsarError(f"{who}: {name} must be 2-D [H, W] or 3-D [B, H, W], got {m.dim()}-D {tuple(m.shape)}")
-    if not m.is_contiguous():
-        raise InsarError(f"{who}: {name} must be contiguous")
+    check_map(who, name, m, dtypes, dims=(2, 3), one_fault=True)
     B = 1 if m.dim() == 2 else m.shape[0]
     H, W = m.shape[-2], m.shape[-1]
     if B < 1 or H < 1 or W < 1 or H > MAX_DIM or W > MAX_DIM or B * H * W >= 1 << 31:
@@ -70,34 +63,14 @@ def _check_map(who: str, name: str, m, dtypes=(torch.uint8, torch.int32)):
     return int(B), int(H), int(W)
 
 
-def _check_device(who: str, name: str, m: torch.Tensor) -> None:
-    if not m.is_cuda:
-        raise InsarError(f"{who}: {name} must be a ROCm tensor (no CPU fallback)")
-
-
-def _check_int(who: str, name: str, v, lo: int, hi: Optional[int] = None) -> int:
-    ok = isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and np.isfinite(v) and int(v) == v
-    if not ok or v < lo or (hi is not None and v > hi):
-        raise InsarError(f"{who}: {name}={v!r}: an integer {f'in {lo}..{hi}' if hi is not None else f'>= {lo}'}")
-    return int(v)
-
-
 def _check_sites(who: str, sites, ignore_value):
     """(mode, value) of the C entry point."""
     if isinstance(sites, str) and sites == "edge":
-        return _lib.DIST_EDGE, -1 if ignore_value is None else _check_int(who, "ignore_value", ignore_value, 0, (1 << 31) - 1)
+        return _lib.DIST_EDGE, -1 if ignore_value is None else _int(who, "ignore_value", ignore_value, 0, (1 << 31) - 1)
     if isinstance(sites, (tuple, list)) and len(sites) == 2 and sites[0] in ("eq", "ne"):
-        v = _check_int(who, f"sites[1] of {sites[0]!r}", sites[1], -(1 << 31), (1 << 31) - 1)
+        v = _int(who, f"sites[1] of {sites[0]!r}", sites[1], -(1 << 31), (1 << 31) - 1)
         return (_lib.DIST_EQ if sites[0] == "eq" else _lib.DIST_NE), v
     raise InsarError(f"{who}: sites={sites!r}: \"edge\", (\"eq\", v) or (\"ne\", v)")
-
-
-def _check_scratch(who: str, scratch, B: int, H: int, W: int, device) -> None:
-    if not isinstance(scratch, DistanceScratch):
-        raise InsarError(f"{who}: scratch must be a DistanceScratch, got {type(scratch).__name__}")
-    if (scratch.B, scratch.H, scratch.W) != (B, H, W) or scratch.scratch.device != device:
-        raise InsarError(f"{who}: scratch of {scratch.B} x {scratch.H} x {scratch.W} on {scratch.scratch.device} for a "
-                         f"{B} x {H} x {W} map on {device}")
 
 
 def distance_transform(m: torch.Tensor, *, sites="edge", max_distance: Optional[int] = 32, ignore_value: Optional[int] = None,
@@ -111,12 +84,12 @@ def distance_transform(m: torch.Tensor, *, sites="edge", max_distance: Optional[
     `ignore_value` belongs to sites="edge" alone. Two launches on the current stream; no read-back, no synchronisation.
     `scratch`: a DistanceScratch of this shape to reuse (else allocated)."""
     who = "distance_transform"
-    B, H, W = _check_map(who, "m", m)
+    B, H, W = _map_dims(who, "m", m)
     mode, value = _check_sites(who, sites, ignore_value)
-    R = 0 if max_distance is None else _check_int(who, "max_distance", max_distance, 1, (1 << 31) - 1)
+    R = 0 if max_distance is None else _int(who, "max_distance", max_distance, 1, (1 << 31) - 1)
     if scratch is not None:
-        _check_scratch(who, scratch, B, H, W, m.device)
-    _check_device(who, "m", m)
+        DistanceScratch.check(who, scratch, (B, H, W), m.device)
+    check_on_device(who, "m", m)
     if scratch is None:
         scratch = DistanceScratch(B, H, W, m.device)
     out = {"d2": torch.empty(m.shape, dtype=torch.int32, device=m.device)}
@@ -133,9 +106,9 @@ def void_band(mask: torch.Tensor, width: int, *, void_value: int = 255, ignore_v
     (d2 <= width^2 of the "edge" transform; width 0: the border pixels themselves), `mask` elsewhere. Pixels of
     `ignore_value` never make a border, and stay what they are."""
     who = "void_band"
-    _check_map(who, "mask", mask, dtypes=(torch.uint8,))
-    width = _check_int(who, "width", width, 0, MAX_DIM)
-    void_value = _check_int(who, "void_value", void_value, 0, 255)
+    _map_dims(who, "mask", mask, dtypes=(torch.uint8,))
+    width = _int(who, "width", width, 0, MAX_DIM)
+    void_value = _int(who, "void_value", void_value, 0, 255)
     d2 = distance_transform(mask, sites="edge", max_distance=max(width, 1), ignore_value=ignore_value)["d2"]
     return torch.where(d2 <= width * width, torch.full_like(mask, void_value), mask)
 
@@ -145,8 +118,8 @@ def expand_labels(labels: torch.Tensor, distance: int) -> torch.Tensor:
     label of its nearest labelled pixel (of several, the one with the smallest index y * W + x); labelled pixels are
     unchanged, so regions never merge."""
     who = "expand_labels"
-    B, H, W = _check_map(who, "labels", labels, dtypes=(torch.int32,))
-    distance = _check_int(who, "distance", distance, 0, MAX_DIM)
+    B, H, W = _map_dims(who, "labels", labels, dtypes=(torch.int32,))
+    distance = _int(who, "distance", distance, 0, MAX_DIM)
     out = distance_transform(labels, sites=("ne", 0), max_distance=max(distance, 1), return_nearest=True)
     near = out["nearest"].view(B, H * W)
     grown = torch.gather(labels.view(B, H * W), 1, near.clamp(min=0).long()).view(labels.shape)
@@ -155,13 +128,13 @@ def expand_labels(labels: torch.Tensor, distance: int) -> torch.Tensor:
 
 
 def _check_counts_args(who: str, pred, gt, distance, num_classes, void_value):
-    B, H, W = _check_map(who, "pred", pred, dtypes=(torch.uint8,))
-    _check_map(who, "gt", gt, dtypes=(torch.uint8,))
+    B, H, W = _map_dims(who, "pred", pred, dtypes=(torch.uint8,))
+    _map_dims(who, "gt", gt, dtypes=(torch.uint8,))
     if pred.dim() != 2 or tuple(gt.shape) != (H, W):
         raise InsarError(f"{who}: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must be 2-D maps of one shape")
-    K = _check_int(who, "num_classes", num_classes, 2, MAX_CLASSES)
-    d = _check_int(who, "distance", distance, 0, MAX_DIM)
-    vv = -1 if void_value is None else _check_int(who, "void_value", void_value, 0, 255)
+    K = _int(who, "num_classes", num_classes, 2, MAX_CLASSES)
+    d = _int(who, "distance", distance, 0, MAX_DIM)
+    vv = -1 if void_value is None else _int(who, "void_value", void_value, 0, 255)
     return H, W, K, d, vv
 
 
@@ -174,10 +147,9 @@ def boundary_counts(pred: torch.Tensor, gt: torch.Tensor, distance: int, num_cla
     who = "boundary_counts"
     H, W, K, d, vv = _check_counts_args(who, pred, gt, distance, num_classes, void_value)
     if scratch is not None:
-        _check_scratch(who, scratch, 1, H, W, pred.device)
-    _check_device(who, "pred", pred)
-    if gt.device != pred.device:
-        raise InsarError(f"{who}: gt on {gt.device}, pred on {pred.device}")
+        DistanceScratch.check(who, scratch, (1, H, W), pred.device)
+    check_on_device(who, "pred", pred)
+    check_on_device(who, "gt", gt, like=pred)
     if scratch is None:
         scratch = DistanceScratch(1, H, W, pred.device)
     counts, host = scratch.count_buffers()
@@ -186,9 +158,8 @@ def boundary_counts(pred: torch.Tensor, gt: torch.Tensor, distance: int, num_cla
     with torch.cuda.device(pred.device):
         call("insar_dist_boundary_counts", ptr(pred), ptr(gt), ptr(d2p), ptr(d2g), H, W, d * d, K, vv, ptr(counts),
              _lib.stream_ptr())
-        host.copy_(counts, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-    return host.numpy()[:3 * K].reshape(K, 3).copy()
+        raw = read_back(host, counts)
+    return raw[:3 * K].reshape(K, 3).copy()
 
 
 def boundary_iou(counts) -> dict:

@@ -208,10 +208,8 @@ class ScenePredictor:
         self.model, self.tile, self.overlap, self.batch, self.num_classes = model, int(tile), int(overlap), int(batch), int(num_classes)
         self._geom: dict = {}            # (H, W, device) -> (origins, origins_dev, buf, acc, wsum)
         self._tiles: dict = {}           # device -> float32 [batch, 1, tile, tile]
-        self._regions: dict = {}         # (H, W, device, max_regions) -> RegionScratch
         self._tta: dict = {}             # device -> (tables int32 [8, batch, 4], tiles' and logits' transformed copies)
-        self._overlaps: dict = {}        # (H, W, device, max_pairs) -> OverlapScratch
-        self._distance: dict = {}        # (H, W, device) -> DistanceScratch
+        self._cache: dict = {}           # (Scratch class, key, device) -> the scratch of a scene tool
 
     def _buffers(self, H: int, W: int, device: torch.device):
         key = (H, W, device)
@@ -226,11 +224,23 @@ class ScenePredictor:
         """Drop the cached buffers (they are scene-sized)."""
         self._geom.clear()
         self._tiles.clear()
-        self._regions.clear()
         self._tta.clear()
-        self._overlaps.clear()
-        self._distance.clear()
-        self.__dict__.pop("_zonal", None)
+        self._cache.clear()
+
+    def _scratch(self, cls, device, *key):
+        """The scratch of class `cls` for `key` on `device`, built on first use and kept until `release()`; None for a key the
+        class does not take, so that the tool itself refuses the argument by name."""
+        k = (cls, key, device)
+        if k not in self._cache:
+            scratch = cls.build(device, *key)
+            if scratch is None:
+                return None
+            self._cache[k] = scratch
+        return self._cache[k]
+
+    def _cached(self, cls) -> list:
+        """The scratch objects of class `cls` that are held now."""
+        return [s for (c, _, _), s in self._cache.items() if c is cls]
 
     def _tta_buffers(self, device: torch.device):
         if device not in self._tta:
@@ -307,19 +317,15 @@ class ScenePredictor:
         out = dict(self.predict(scene, return_prob=return_prob))
         H, W = out["mask"].shape
         max_regions = region_kwargs.get("max_regions", DEFAULT_MAX_REGIONS)
-        key = (H, W, out["mask"].device, max_regions)
-        if key not in self._regions and isinstance(max_regions, int) and max_regions >= 1:
-            self._regions[key] = RegionScratch(H, W, out["mask"].device, max_regions)
-        reg = label_regions(out["mask"], out["conf"], scratch=self._regions.get(key), **region_kwargs)
+        reg = label_regions(out["mask"], out["conf"], scratch=self._scratch(RegionScratch, out["mask"].device, H, W, max_regions),
+                            **region_kwargs)
         out.update(labels=reg["labels"], regions=reg["regions"], count=reg["count"], mask_clean=reg["mask"])
         if split is not None and split is not False:
             self._split(out, split, max_regions)
         if simplify is not None and not outlines:
             raise InsarError("detect: simplify needs outlines=True")
-        if outlines and simplify is not None:
-            self._trace_simplified(out, region_kwargs.get("connectivity", 8), simplify)
-        elif outlines:
-            self._trace(out, region_kwargs.get("connectivity", 8))
+        if outlines:
+            self._trace(out, region_kwargs.get("connectivity", 8), simplify)
         if skeletons:
             self._thin(out, max_iterations, max_regions)
         if measure is not None:
@@ -327,7 +333,7 @@ class ScenePredictor:
         return out
 
     def _split(self, out: dict, split, max_regions: int) -> None:
-        from .split import DEFAULT_MAX_PAIRS, MAX_PAIRS, MAX_ROUNDS, SplitScratch, split_regions
+        from .split import DEFAULT_MAX_PAIRS, SplitScratch, split_regions
         if split is True:
             kw = {}
         elif isinstance(split, dict):
@@ -341,19 +347,15 @@ class ScenePredictor:
                 raise InsarError(f"split: {name!r} is detect's to give")
         kw.setdefault("max_regions", max_regions)
         H, W = out["labels"].shape
-        key = (H, W, out["labels"].device, kw["max_regions"], kw.get("max_pairs", DEFAULT_MAX_PAIRS), kw.get("max_rounds", 64))
-        cache = self.__dict__.setdefault("_splits", {})
-        limits = (None, MAX_PAIRS, MAX_ROUNDS)                    # anything else is split_regions's to refuse by name
-        if key not in cache and all(isinstance(k, int) and k >= 1 and (m is None or k <= m) for k, m in zip(key[3:], limits)):
-            cache[key] = SplitScratch(H, W, key[2], *key[3:])
-        sp =split_regions(out["labels"], mask=out["mask_clean"], conf=out["conf"], scratch=cache.get(key), **kw)
+        scratch = self._scratch(SplitScratch, out["labels"].device, H, W, kw["max_regions"], kw.get("max_pairs", DEFAULT_MAX_PAIRS),
+                                kw.get("max_rounds", 64))
+        sp = split_regions(out["labels"], mask=out["mask_clean"], conf=out["conf"], scratch=scratch, **kw)
         out.update(labels=sp["labels"], regions=sp["regions"], count=sp["count"], split_rounds=sp["rounds"],
                    split_converged=sp["converged"])
 
     def _measure(self, out: dict, scene, measure: dict, max_regions: int) -> None:
         from .zonal import ZonalScratch, region_stats
         dev = out["labels"].device
-        cache = self.__dict__.setdefault("_zonal", {})
         out["stats"] = {}
         for name, spec in measure.items():
             raster, kw = spec if isinstance(spec, tuple) else (spec, {})
@@ -366,48 +368,29 @@ class ScenePredictor:
             if not isinstance(raster, torch.Tensor):
                 raise InsarError(f"measure[{name!r}]: numpy array or torch tensor, got {type(raster).__name__}")
             raster = raster.detach().to(dev).contiguous()
-            bins, channels = kw.get("bins", 0), raster.shape[0] if raster.dim() == 3 else 1
-            key = (dev, max_regions, bins, channels)
-            if key not in cache and isinstance(bins, int) and 0 <= bins <= 256 and 1 <= channels <= 4 \
-                    and isinstance(max_regions, int) and max_regions >= 1:
-                cache[key] = ZonalScratch(dev, max_regions, bins, channels)
-            out["stats"][name] = region_stats(out["labels"], raster, count=out["count"], max_regions=max_regions,
-                                              scratch=cache.get(key), **kw)
+            scratch = self._scratch(ZonalScratch, dev, max_regions, kw.get("bins", 0), raster.shape[0] if raster.dim() == 3 else 1)
+            out["stats"][name] = region_stats(out["labels"], raster, count=out["count"], max_regions=max_regions, scratch=scratch, **kw)
 
     def _thin(self, out: dict, max_iterations: int, max_regions: int) -> None:
         from .skeletons import SkeletonScratch, thin_regions
         H, W = out["labels"].shape
-        cache = self.__dict__.setdefault("_skeletons", {})
-        key = (H, W, out["labels"].device, max_iterations, max_regions)
-        if key not in cache and isinstance(max_iterations, int) and 1 <= max_iterations <= 32768:
-            cache[key] = SkeletonScratch(H, W, out["labels"].device, max_iterations, max_regions)
-        sk = thin_regions(out["labels"], max_iterations=max_iterations, max_regions=max_regions, scratch=cache.get(key))
+        sk = thin_regions(out["labels"], max_iterations=max_iterations, max_regions=max_regions,
+                          scratch=self._scratch(SkeletonScratch, out["labels"].device, H, W, max_iterations, max_regions))
         out["skeleton"], out["skeleton_converged"] = sk["skeleton"], sk["converged"]
         # region ids are labels: row id - 1 of the table; a kept region always has a pixel, hence a record
         rows = np.asarray(out["regions"]["id"], dtype=np.int64) - 1
         for f in ("length", "mean_width", "max_width", "orientation", "n_end", "n_junction"):
             out["regions"][f] = sk["table"][f][rows]
 
-    def _trace(self, out: dict, connectivity: int) -> None:
-        from .outlines import OutlineScratch, perimeters, region_outlines
-        H, W = out["labels"].shape
-        cache = self.__dict__.setdefault("_outlines", {})
-        key = (H, W, out["labels"].device)
-        if key not in cache:
-            cache[key] = OutlineScratch(H, W, out["labels"].device)
-        out["outlines"] = region_outlines(out["labels"], connectivity=connectivity, scratch=cache[key])
-        out["regions"]["perimeter"] = perimeters(out["outlines"]["rings"], out["regions"]["id"])
-
-    def _trace_simplified(self, out: dict, connectivity: int, tolerance: float) -> None:
-        from .outlines import OutlineScratch, perimeters, region_outlines
+    def _trace(self, out: dict, connectivity: int, tolerance: Optional[float] = None) -> None:
+        """The outlines of out["labels"]; with a tolerance, traced vertex by vertex and simplified against the label map."""
+        from .outlines import DEFAULT_MAX_EDGES, DEFAULT_MAX_RINGS, DEFAULT_MAX_VERTICES, OutlineScratch, perimeters, region_outlines
         from .simplify import simplify_outlines
         H, W = out["labels"].shape
-        cache = self.__dict__.setdefault("_outlines", {})
-        key = (H, W, out["labels"].device)
-        if key not in cache:
-            cache[key] = OutlineScratch(H, W, out["labels"].device)
-        raw = region_outlines(out["labels"], connectivity=connectivity, corners_only=False, scratch=cache[key])
-        out["outlines"] = simplify_outlines(raw, out["labels"], tolerance=tolerance)
+        scratch = self._scratch(OutlineScratch, out["labels"].device, H, W, DEFAULT_MAX_RINGS, DEFAULT_MAX_VERTICES, DEFAULT_MAX_EDGES)
+        out["outlines"] = region_outlines(out["labels"], connectivity=connectivity, corners_only=tolerance is None, scratch=scratch)
+        if tolerance is not None:
+            out["outlines"] = simplify_outlines(out["outlines"], out["labels"], tolerance=tolerance)
         out["regions"]["perimeter"] = perimeters(out["outlines"]["rings"], out["regions"]["id"])
 
     def evaluate(self, scene, gt_mask, *, iou_threshold: float = 0.5, gt_min_area: int = 1, max_pairs: int = DEFAULT_MAX_PAIRS,
@@ -430,18 +413,12 @@ class ScenePredictor:
         gt_cls = torch.where(gt == 255, torch.zeros_like(gt), gt)
         max_regions = region_kwargs.get("max_regions", DEFAULT_MAX_REGIONS)
         truth = label_regions(gt_cls, None, connectivity=region_kwargs.get("connectivity", 8), min_area=gt_min_area,
-                              max_regions=max_regions, scratch=self._regions.get((H, W, dev, max_regions)))
-        key = (H, W, dev, max_pairs)
-        if key not in self._overlaps and isinstance(max_pairs, int) and max_pairs >= 1:
-            self._overlaps[key] = OverlapScratch(dev, max_pairs)
+                              max_regions=max_regions, scratch=self._scratch(RegionScratch, dev, H, W, max_regions))
         score = match_regions(out, truth, void=gt, void_value=255, iou_threshold=iou_threshold, max_pairs=max_pairs,
-                              num_classes=self.num_classes, scratch=self._overlaps.get(key))
+                              num_classes=self.num_classes, scratch=self._scratch(OverlapScratch, dev, max_pairs))
         if boundary_distance is not None:
-            key = (H, W, dev)
-            if key not in self._distance:
-                self._distance[key] = DistanceScratch(1, H, W, dev)
             counts = boundary_counts(out["mask_clean"], gt, boundary_distance, self.num_classes, void_value=255,
-                                     scratch=self._distance[key])
+                                     scratch=self._scratch(DistanceScratch, dev, 1, H, W))
             score["boundary"] = {"distance": int(boundary_distance), "counts": counts, **boundary_iou(counts)}
         out.update(score=score, gt_labels=truth["labels"], gt_regions=truth["regions"], gt_count=truth["count"])
         return out

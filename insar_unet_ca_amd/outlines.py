@@ -11,7 +11,6 @@ output is bitwise reproducible.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -19,6 +18,7 @@ import torch
 
 from . import _lib
 from ._lib import InsarError, call, ptr
+from ._scene import Scratch, check_int, check_map, check_on_device, query_bytes, read_back
 
 DEFAULT_MAX_RINGS = 65536
 DEFAULT_MAX_VERTICES = 1 << 22
@@ -34,9 +34,7 @@ RING_FIELDS = ("ring", "label", "start", "count", "edges", "area2", "hole", "y0"
 
 def scratch_bytes(H: int, W: int, max_rings: int = DEFAULT_MAX_RINGS, max_edges: int = DEFAULT_MAX_EDGES):
     """(scratch bytes, table bytes) of an H x W scene with max_edges edge slots and max_rings rings. Host arithmetic only."""
-    s, t = C.c_int64(0), C.c_int64(0)
-    call("insar_outline_scratch_bytes", int(H), int(W), int(max_rings), int(max_edges), C.byref(s), C.byref(t))
-    return int(s.value), int(t.value)
+    return query_bytes("insar_outline_scratch_bytes", H, W, max_rings, max_edges, outputs=2)
 
 
 def launches(n_edges: int) -> int:
@@ -44,39 +42,29 @@ def launches(n_edges: int) -> int:
     return call("insar_outline_launches", int(n_edges))
 
 
-class OutlineScratch:
+class OutlineScratch(Scratch):
     """The device buffers of one (H, W, max_rings, max_vertices, max_edges): scratch, the ring table, and the pinned host
     copy the table is read back into. Nothing in them has to survive between calls. The vertex array is the caller's: every
     call returns a fresh one."""
+    KEY, DEVICE_AT = ("H", "W", "max_rings", "max_vertices", "max_edges"), 2
 
     def __init__(self, H: int, W: int, device: torch.device, max_rings: int = DEFAULT_MAX_RINGS,
                  max_vertices: int = DEFAULT_MAX_VERTICES, max_edges: int = DEFAULT_MAX_EDGES):
         sb, tb = scratch_bytes(H, W, max_rings, max_edges)
-        self.H, self.W = int(H), int(W)
-        self.max_rings, self.max_vertices, self.max_edges = int(max_rings), int(max_vertices), int(max_edges)
-        self.scratch = torch.empty(sb, dtype=torch.uint8, device=device)
-        self.table = torch.empty(tb, dtype=torch.uint8, device=device)
-        self.host = torch.empty(tb, dtype=torch.uint8, pin_memory=True)
-
-    def key(self):
-        return (self.H, self.W, self.max_rings, self.max_vertices, self.max_edges)
+        super().__init__((H, W, max_rings, max_vertices, max_edges), device, scratch=sb, table=tb, host=tb)
 
 
 def _check_args(labels, connectivity, max_rings, max_vertices, max_edges) -> None:
-    if not isinstance(labels, torch.Tensor):
-        raise InsarError(f"region_outlines: labels must be a torch tensor, got {type(labels).__name__}")
-    if labels.dtype != torch.int32 or labels.dim() != 2 or not labels.is_contiguous():
-        raise InsarError(f"region_outlines: labels must be a contiguous 2-D int32 tensor, got {labels.dtype} {tuple(labels.shape)}")
+    who = "region_outlines"
+    check_map(who, "labels", labels, (torch.int32,))
     H, W = labels.shape
     if H < 1 or W < 1 or H * W >= MAX_PIXELS:
-        raise InsarError(f"region_outlines: scene {H} x {W}: need H, W >= 1 and H * W < 2^29")
+        raise InsarError(f"{who}: scene {H} x {W}: need H, W >= 1 and H * W < 2^29")
     if connectivity not in (4, 8):
         raise InsarError(f"connectivity={connectivity!r}: 4 or 8")
     for name, v in (("max_rings", max_rings), ("max_vertices", max_vertices), ("max_edges", max_edges)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1 or v > 1 << 30:
-            raise InsarError(f"{name}={v!r}: a positive integer, at most 2^30")
-    if not labels.is_cuda:
-        raise InsarError("region_outlines: labels must be a ROCm tensor (no CPU fallback)")
+        check_int(who, name, v, 1, 1 << 30, integral_floats=False)
+    check_on_device(who, "labels", labels)
 
 
 def rings_from_table(raw: np.ndarray, n_rings: int) -> Dict[str, np.ndarray]:
@@ -117,19 +105,13 @@ def region_outlines(labels: torch.Tensor, *, connectivity: int = 8, corners_only
     max_rings, max_vertices, max_edges = int(max_rings), int(max_vertices), int(max_edges)
     if scratch is None:
         scratch = OutlineScratch(H, W, labels.device, max_rings, max_vertices, max_edges)
-    elif scratch.key() != (H, W, max_rings, max_vertices, max_edges) or scratch.scratch.device != labels.device:
-        raise InsarError(f"region_outlines: scratch of {scratch.H} x {scratch.W}, max_rings={scratch.max_rings}, "
-                         f"max_vertices={scratch.max_vertices}, max_edges={scratch.max_edges} for a {H} x {W} scene, "
-                         f"max_rings={max_rings}, max_vertices={max_vertices}, max_edges={max_edges}")
+    else:
+        OutlineScratch.check("region_outlines", scratch, (H, W, max_rings, max_vertices, max_edges), labels.device)
     sp, tp = ptr(scratch.scratch), ptr(scratch.table)
-    header = scratch.host[:RING_DTYPE.itemsize]
     with torch.cuda.device(labels.device):
         s = _lib.stream_ptr()
-        stream = torch.cuda.current_stream()
         call("insar_outline_edges", ptr(labels), H, W, int(connectivity), max_edges, sp, tp, s)
-        header.copy_(scratch.table[:RING_DTYPE.itemsize], non_blocking=True)
-        stream.synchronize()
-        E = int(header.numpy().view(RING_DTYPE)["edges"][0])
+        E = int(read_back(scratch.host, scratch.table, RING_DTYPE.itemsize).view(RING_DTYPE)["edges"][0])
         if E > max_edges:
             raise InsarError(f"region_outlines: {E} boundary edges exceed max_edges={max_edges}: raise max_edges or min_area")
         if E == 0:
@@ -143,9 +125,7 @@ def region_outlines(labels: torch.Tensor, *, connectivity: int = 8, corners_only
         call("insar_outline_write", H, W, E, int(bool(corners_only)), max_rings, vcap, max_edges, sp, tp, ptr(vertices), s)
         # a ring has four edges or more: R <= E / 4 bounds the records worth copying, whatever max_rings is
         nbytes = RING_DTYPE.itemsize * (1 + min(max_rings, E // 4))
-        scratch.host[:nbytes].copy_(scratch.table[:nbytes], non_blocking=True)
-        stream.synchronize()
-    raw = scratch.host.numpy()[:nbytes]
+        raw = read_back(scratch.host, scratch.table, nbytes)
     head = raw.view(RING_DTYPE)[0]
     R, V = int(head["label"]), int(head["count"])
     if R > max_rings:

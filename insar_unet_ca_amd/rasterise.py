@@ -10,7 +10,6 @@ exterior) becomes `overlap_value`, the pipeline's void. Integers only: the map i
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Callable, Dict, List, Optional, Union
 
 import numpy as np
@@ -18,6 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import InsarError, call, ptr
+from ._scene import Scratch, check_int, check_map, inverse_affine, query_bytes
 
 SUBPIXEL = 256                           # fixed-point units per pixel
 COORD_LIMIT = 1 << 24                    # |X|, |Y| <= 2^24: every product of the crossing rule fits int64
@@ -42,9 +42,7 @@ def launches() -> int:
 
 def scratch_bytes(H: int, W: int, max_crossings: int) -> int:
     """Bytes of scratch for an H x W scene with room for max_crossings crossing records. Host arithmetic only."""
-    s = C.c_int64(0)
-    call("insar_raster_scratch_bytes", int(H), int(W), int(max_crossings), C.byref(s))
-    return int(s.value)
+    return query_bytes("insar_raster_scratch_bytes", H, W, max_crossings, outputs=1)
 
 
 def _exact_sum(a: np.ndarray) -> int:
@@ -119,17 +117,6 @@ def _value_of(values, label) -> int:
     return int(v)
 
 
-def _inverse_affine(transform):
-    A = np.asarray(transform, dtype=np.float64)
-    if A.shape != (2, 3):
-        raise InsarError(f"transform must be a 2 x 3 affine, got shape {A.shape}")
-    det = A[0, 0] * A[1, 1] - A[0, 1] * A[1, 0]
-    if not np.isfinite(A).all() or det == 0:
-        raise InsarError("transform is singular or not finite")
-    inv = np.array([[A[1, 1], -A[0, 1]], [-A[1, 0], A[0, 0]]]) / det
-    return inv, A[:, 2].copy()
-
-
 def _quantise(ring, inverse) -> np.ndarray:
     """A ring as int64 [n, 2] = (Y, X) in 1/256 pixel: (y, x) as given without a transform, else the inverse affine of world
     (x, y), in float64; then np.rint(v * 256)."""
@@ -169,7 +156,7 @@ def pack_polygons(polygons: List[dict], *, transform=None, values: Union[None, d
     inverted here in float64. `values`: label -> burnt value as a dict or a callable, None for the label itself.
     Vertices outside the scene are legal; one further than 65536 pixels from the origin raises InsarError. Zero-area rings
     and horizontal edges are dropped."""
-    inverse = None if transform is None else _inverse_affine(transform)
+    inverse = None if transform is None else inverse_affine(transform)
     parts = []
     for entry in polygons:
         value = _value_of(values, entry["label"])
@@ -210,19 +197,13 @@ def from_geojson(fc: dict, *, transform=None, value_property: str = "label", val
     return pack_polygons(entries, transform=transform, values=values)
 
 
-class RasterScratch:
+class RasterScratch(Scratch):
     """The device scratch of one (H, W) with room for `max_crossings` crossing records. Nothing in it has to survive between
     calls. The label map and the overlap count are the caller's: every call returns fresh ones."""
+    KEY, DEVICE_AT = ("H", "W", "max_crossings"), 2
 
     def __init__(self, H: int, W: int, device, max_crossings: int):
-        self.H, self.W, self.max_crossings = int(H), int(W), int(max_crossings)
-        self.scratch = torch.empty(scratch_bytes(H, W, max_crossings), dtype=torch.uint8, device=device)
-
-
-def _int_arg(name, v, lo, hi) -> int:
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-        raise InsarError(f"rasterise_polygons: {name}={v!r}: an integer in {lo} .. {hi}")
-    return int(v)
+        super().__init__((H, W, max_crossings), device, scratch=scratch_bytes(H, W, max_crossings))
 
 
 def rasterise_polygons(table: PolygonTable, H: int, W: int, *, dtype: torch.dtype = torch.uint8, fill: int = 0,
@@ -242,13 +223,14 @@ def rasterise_polygons(table: PolygonTable, H: int, W: int, *, dtype: torch.dtyp
         raise InsarError(f"rasterise_polygons: table must be a PolygonTable, got {type(table).__name__}")
     if dtype not in _DTYPES:
         raise InsarError(f"rasterise_polygons: dtype {dtype}: torch.uint8 or torch.int32")
-    H, W = _int_arg("H", H, 1, (1 << 31) - 1), _int_arg("W", W, 1, (1 << 31) - 1)
+    who = "rasterise_polygons"
+    H, W = (check_int(who, n, v, 1, (1 << 31) - 1, integral_floats=False) for n, v in (("H", H), ("W", W)))
     if W > MAX_WIDTH:
         raise InsarError(f"rasterise_polygons: scene width {W} above {MAX_WIDTH}")
     if H * W >= 1 << 31:
         raise InsarError(f"rasterise_polygons: scene {H} x {W} has 2^31 pixels or more")
     lo, hi = (0, 255) if dtype == torch.uint8 else (-(1 << 31), (1 << 31) - 1)
-    fill, overlap_value = _int_arg("fill", fill, lo, hi), _int_arg("overlap_value", overlap_value, lo, hi)
+    fill, overlap_value = (check_int(who, n, v, lo, hi, integral_floats=False) for n, v in (("fill", fill), ("overlap_value", overlap_value)))
     if table.row_value_bound >= 1 << 31:
         raise InsarError(f"rasterise_polygons: the values of the edges crossing one row sum to {table.row_value_bound} in "
                          f"magnitude: 2^31 or more leaves the int32 sums of the kernels")
@@ -256,11 +238,7 @@ def rasterise_polygons(table: PolygonTable, H: int, W: int, *, dtype: torch.dtyp
     if n_cross > MAX_CROSSINGS:
         raise InsarError(f"rasterise_polygons: {n_cross} edge-row crossings, at most 2^30")
     if base is not None:
-        if not isinstance(base, torch.Tensor):
-            raise InsarError(f"rasterise_polygons: base must be a torch tensor, got {type(base).__name__}")
-        if base.dtype != dtype or tuple(base.shape) != (H, W) or not base.is_contiguous():
-            raise InsarError(f"rasterise_polygons: base must be a contiguous {dtype} tensor [{H}, {W}], got {base.dtype} "
-                             f"{tuple(base.shape)}")
+        check_map(who, "base", base, (dtype,), shape=(H, W), of="the scene")
         if device is not None and torch.device(device) != base.device:
             raise InsarError(f"rasterise_polygons: base lives on {base.device}, device={device}")
         device = base.device

@@ -10,7 +10,6 @@ sum of llrint(clamp(conf, 0, 1) * 2^30)); the float fields of the table are form
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Optional
 
 import numpy as np
@@ -18,6 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import InsarError, call, ptr
+from ._scene import Scratch, check_int, check_map, check_on_device, query_bytes, read_back
 
 CONF_SCALE = 1 << 30
 DEFAULT_MAX_REGIONS = 65536
@@ -31,44 +31,33 @@ assert REGION_DTYPE.itemsize == 64
 
 def scratch_bytes(H: int, W: int, max_regions: int = DEFAULT_MAX_REGIONS):
     """(scratch bytes, table bytes) of an H x W scene with room for max_regions regions. Host arithmetic only."""
-    s, t = C.c_int64(0), C.c_int64(0)
-    call("insar_regions_scratch_bytes", int(H), int(W), int(max_regions), C.byref(s), C.byref(t))
-    return int(s.value), int(t.value)
+    return query_bytes("insar_regions_scratch_bytes", H, W, max_regions, outputs=2)
 
 
-class RegionScratch:
+class RegionScratch(Scratch):
     """The device buffers of one (H, W, max_regions): scene-sized scratch, the region table, and the pinned host copy the
     table is read back into. Nothing in them has to survive between calls."""
+    KEY, SHOW, DEVICE_AT = ("H", "W", "max_regions"), "{} x {}, max_regions={}", 2
 
     def __init__(self, H: int, W: int, device: torch.device, max_regions: int = DEFAULT_MAX_REGIONS):
         sb, tb = scratch_bytes(H, W, max_regions)
-        self.H, self.W, self.max_regions = int(H), int(W), int(max_regions)
-        self.scratch = torch.empty(sb, dtype=torch.uint8, device=device)
-        self.table = torch.empty(tb, dtype=torch.uint8, device=device)
-        self.host = torch.empty(tb, dtype=torch.uint8, pin_memory=True)
+        super().__init__((H, W, max_regions), device, scratch=sb, table=tb, host=tb)
 
 
 def _check_args(mask, conf, connectivity, min_area, min_conf, max_regions) -> None:
-    if not isinstance(mask, torch.Tensor):
-        raise InsarError(f"label_regions: mask must be a torch tensor, got {type(mask).__name__}")
-    if not mask.is_cuda:
-        raise InsarError("label_regions: mask must be a ROCm tensor (no CPU fallback)")
-    if mask.dtype != torch.uint8 or mask.dim() != 2 or not mask.is_contiguous():
-        raise InsarError(f"label_regions: mask must be a contiguous 2-D uint8 tensor, got {mask.dtype} {tuple(mask.shape)}")
+    who = "label_regions"
+    check_on_device(who, "mask", mask)
+    check_map(who, "mask", mask, (torch.uint8,))
     H, W = mask.shape
     if H < 1 or W < 1 or H * W >= 1 << 31:
-        raise InsarError(f"label_regions: scene {H} x {W}: need H, W >= 1 and H * W < 2^31")
+        raise InsarError(f"{who}: scene {H} x {W}: need H, W >= 1 and H * W < 2^31")
     if conf is not None:
-        if not isinstance(conf, torch.Tensor) or not conf.is_cuda or conf.device != mask.device:
-            raise InsarError("label_regions: conf must be a ROCm tensor on the mask's device (no CPU fallback)")
-        if conf.dtype != torch.float32 or tuple(conf.shape) != (H, W) or not conf.is_contiguous():
-            raise InsarError(f"label_regions: conf must be a contiguous float32 [{H}, {W}] tensor, got {conf.dtype} {tuple(conf.shape)}")
+        check_on_device(who, "conf", conf, like=mask)
+        check_map(who, "conf", conf, (torch.float32,), shape=(H, W), of="mask")
     if connectivity not in (4, 8):
         raise InsarError(f"connectivity={connectivity!r}: 4 or 8")
-    if int(min_area) != min_area or min_area < 1:
-        raise InsarError(f"min_area={min_area!r}: a positive integer")
-    if int(max_regions) != max_regions or max_regions < 1:
-        raise InsarError(f"max_regions={max_regions!r}: a positive integer")
+    check_int(who, "min_area", min_area, 1, integral_floats=True)
+    check_int(who, "max_regions", max_regions, 1, integral_floats=True)
     if not np.isfinite(np.float32(min_conf)):
         raise InsarError(f"min_conf={min_conf!r}: a finite number")
 
@@ -118,15 +107,13 @@ def label_regions(mask: torch.Tensor, conf: Optional[torch.Tensor] = None, *, co
     max_regions = int(max_regions)
     if scratch is None:
         scratch = RegionScratch(H, W, mask.device, max_regions)
-    elif (scratch.H, scratch.W, scratch.max_regions) != (H, W, max_regions) or scratch.scratch.device != mask.device:
-        raise InsarError(f"label_regions: scratch of {scratch.H} x {scratch.W}, max_regions={scratch.max_regions} for a "
-                         f"{H} x {W} scene, max_regions={max_regions}")
+    else:
+        RegionScratch.check("label_regions", scratch, (H, W, max_regions), mask.device)
     labels = torch.empty(H, W, dtype=torch.int32, device=mask.device)
     mask_out = torch.empty(H, W, dtype=torch.uint8, device=mask.device)
     with torch.cuda.device(mask.device):
         _launch(mask, conf, int(connectivity), int(min_area), float(np.float32(min_conf)), max_regions, scratch.scratch,
                 scratch.table, labels, mask_out)
-        scratch.host.copy_(scratch.table, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-    regions = regions_from_table(scratch.host.numpy(), max_regions, conf is not None)
+        raw = read_back(scratch.host, scratch.table)
+    regions = regions_from_table(raw, max_regions, conf is not None)
     return {"labels": labels, "mask": mask_out, "count": int(len(regions["id"])), "regions": regions}

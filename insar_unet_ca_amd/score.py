@@ -12,7 +12,6 @@ in the device buffer is not.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -20,6 +19,7 @@ import torch
 
 from . import _lib
 from ._lib import InsarError, call, ptr
+from ._scene import Scratch, check_int, check_map, check_on_device, query_bytes, read_back
 from .distance import boundary_iou
 
 DEFAULT_MAX_PAIRS = 262144
@@ -33,50 +33,34 @@ SCORE_FIELDS = ("tp", "fp", "fn", "precision", "recall", "f1", "sq", "rq", "pq")
 
 def scratch_bytes(max_pairs: int = DEFAULT_MAX_PAIRS) -> Tuple[int, int]:
     """(table bytes, output bytes) for room for max_pairs pairs. Host arithmetic only."""
-    t, o = C.c_int64(0), C.c_int64(0)
-    call("insar_overlap_scratch_bytes", int(max_pairs), C.byref(t), C.byref(o))
-    return int(t.value), int(o.value)
+    return query_bytes("insar_overlap_scratch_bytes", max_pairs, outputs=2)
 
 
-class OverlapScratch:
+class OverlapScratch(Scratch):
     """The device buffers of one max_pairs: the hash table, the compacted output and the pinned host copy the output is read
     back into. They do not depend on the scene size; nothing in them has to survive between calls."""
+    KEY = ("max_pairs",)
 
     def __init__(self, device: torch.device, max_pairs: int = DEFAULT_MAX_PAIRS):
         tb, ob = scratch_bytes(max_pairs)
-        self.max_pairs = int(max_pairs)
-        self.table = torch.empty(tb, dtype=torch.uint8, device=device)
-        self.out = torch.empty(ob, dtype=torch.uint8, device=device)
-        self.host = torch.empty(ob, dtype=torch.uint8, pin_memory=True)
-
-
-def _check_labels(name: str, t) -> None:
-    if not isinstance(t, torch.Tensor):
-        raise InsarError(f"region_overlaps: {name} must be a torch tensor, got {type(t).__name__}")
-    if not t.is_cuda:
-        raise InsarError(f"region_overlaps: {name} must be a ROCm tensor (no CPU fallback)")
-    if t.dtype != torch.int32 or t.dim() != 2 or not t.is_contiguous():
-        raise InsarError(f"region_overlaps: {name} must be a contiguous 2-D int32 tensor, got {t.dtype} {tuple(t.shape)}")
+        super().__init__((max_pairs,), device, table=tb, out=ob, host=ob)
 
 
 def _check_args(pred_labels, gt_labels, void, void_value, max_pairs) -> None:
-    _check_labels("pred_labels", pred_labels)
-    _check_labels("gt_labels", gt_labels)
+    who = "region_overlaps"
+    for name, t in (("pred_labels", pred_labels), ("gt_labels", gt_labels)):
+        check_on_device(who, name, t)
+        check_map(who, name, t, (torch.int32,))
     H, W = pred_labels.shape
     if H < 1 or W < 1 or H * W >= 1 << 31:
-        raise InsarError(f"region_overlaps: scene {H} x {W}: need H, W >= 1 and H * W < 2^31")
-    if tuple(gt_labels.shape) != (H, W) or gt_labels.device != pred_labels.device:
-        raise InsarError(f"region_overlaps: gt_labels {tuple(gt_labels.shape)} on {gt_labels.device}: expected ({H}, {W}) on "
-                         f"{pred_labels.device}")
+        raise InsarError(f"{who}: scene {H} x {W}: need H, W >= 1 and H * W < 2^31")
+    check_map(who, "gt_labels", gt_labels, (torch.int32,), shape=(H, W), of="pred_labels")
+    check_on_device(who, "gt_labels", gt_labels, like=pred_labels)
     if void is not None:
-        if not isinstance(void, torch.Tensor) or not void.is_cuda or void.device != pred_labels.device:
-            raise InsarError("region_overlaps: void must be a ROCm tensor on the labels' device (no CPU fallback)")
-        if void.dtype != torch.uint8 or tuple(void.shape) != (H, W) or not void.is_contiguous():
-            raise InsarError(f"region_overlaps: void must be a contiguous uint8 [{H}, {W}] tensor, got {void.dtype} {tuple(void.shape)}")
-        if int(void_value) != void_value or not 0 <= void_value <= 255:
-            raise InsarError(f"void_value={void_value!r}: an integer in 0..255")
-    if int(max_pairs) != max_pairs or not 1 <= max_pairs <= MAX_PAIRS_LIMIT:
-        raise InsarError(f"max_pairs={max_pairs!r}: an integer in 1..{MAX_PAIRS_LIMIT}")
+        check_on_device(who, "void", void, like=pred_labels)
+        check_map(who, "void", void, (torch.uint8,), shape=(H, W))
+        check_int(who, "void_value", void_value, 0, 255, integral_floats=True)
+    check_int(who, "max_pairs", max_pairs, 1, MAX_PAIRS_LIMIT, integral_floats=True)
 
 
 def _launch(pred_labels: torch.Tensor, gt_labels: torch.Tensor, void: Optional[torch.Tensor], void_value: int, max_pairs: int,
@@ -115,14 +99,12 @@ def region_overlaps(pred_labels: torch.Tensor, gt_labels: torch.Tensor, void: Op
     max_pairs = int(max_pairs)
     if scratch is None:
         scratch = OverlapScratch(pred_labels.device, max_pairs)
-    elif scratch.max_pairs != max_pairs or scratch.table.device != pred_labels.device:
-        raise InsarError(f"region_overlaps: scratch of max_pairs={scratch.max_pairs} on {scratch.table.device} for "
-                         f"max_pairs={max_pairs} on {pred_labels.device}")
+    else:
+        OverlapScratch.check("region_overlaps", scratch, (max_pairs,), pred_labels.device)
     with torch.cuda.device(pred_labels.device):
         _launch(pred_labels, gt_labels, void, int(void_value), max_pairs, scratch.table, scratch.out)
-        scratch.host.copy_(scratch.out, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-    return overlaps_from_raw(scratch.host.numpy(), max_pairs)
+        raw = read_back(scratch.host, scratch.out)
+    return overlaps_from_raw(raw, max_pairs)
 
 
 # ---- scores ---------------------------------------------------------------------------------------------------------------
@@ -301,9 +283,8 @@ class DetectionScore:
     too, and `compute()` then reports "boundary" = {"distance", "counts", "iou", "mean_iou", "scenes"} of the sums."""
 
     def __init__(self, num_classes: int, iou_threshold: float = 0.5):
-        if int(num_classes) != num_classes or num_classes < 2:
-            raise InsarError(f"num_classes={num_classes!r}: an integer >= 2")
-        self.num_classes, self.iou_threshold = int(num_classes), float(iou_threshold)
+        self.num_classes = check_int("DetectionScore", "num_classes", num_classes, 2, integral_floats=True)
+        self.iou_threshold = float(iou_threshold)
         self.reset()
 
     def reset(self) -> None:

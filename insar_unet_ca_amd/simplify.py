@@ -16,7 +16,6 @@ arcs never cross at a large tolerance. Douglas-Peucker does not give that, and n
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Optional
 
@@ -25,6 +24,7 @@ import torch
 
 from . import _lib
 from ._lib import InsarError, call, ptr
+from ._scene import Scratch, check_int, check_map, check_on_device, pinned, query_bytes, read_back
 from .outlines import RING_DTYPE
 
 # A round is one level of the recursion. A segment of n vertices that splits evenly is done after log2 n rounds (17 for 10^5
@@ -42,9 +42,7 @@ _COPIED = ("label", "edges", "leader", "area2")
 
 def scratch_bytes(max_vertices: int, max_rings: int):
     """(scratch bytes, table bytes) for these capacities. Host arithmetic only."""
-    s, t = C.c_int64(0), C.c_int64(0)
-    call("insar_simplify_scratch_bytes", int(max_vertices), int(max_rings), C.byref(s), C.byref(t))
-    return int(s.value), int(t.value)
+    return query_bytes("insar_simplify_scratch_bytes", max_vertices, max_rings, outputs=2)
 
 
 def launches(rounds: int) -> int:
@@ -57,23 +55,16 @@ def eps2q(tolerance: float) -> int:
     return int(round(float(tolerance) * 16)) ** 2
 
 
-class SimplifyScratch:
+class SimplifyScratch(Scratch):
     """The device buffers of one (max_vertices, max_rings, H, W): scratch, the input and the output ring table, and the pinned
     host copies of the tables and of one round counter. Nothing in them has to survive between calls. The vertex and index
     arrays are the caller's: every call returns fresh ones. H and W only name the scene the scratch serves."""
+    KEY, DEVICE_AT = ("max_vertices", "max_rings", "H", "W"), 4
 
     def __init__(self, max_vertices: int, max_rings: int, H: int, W: int, device):
         sb, tb = scratch_bytes(max_vertices, max_rings)
-        self.max_vertices, self.max_rings, self.H, self.W = int(max_vertices), int(max_rings), int(H), int(W)
-        self.scratch = torch.empty(sb, dtype=torch.uint8, device=device)
-        self.table_in = torch.empty(tb, dtype=torch.uint8, device=device)
-        self.table = torch.empty(tb, dtype=torch.uint8, device=device)
-        self.host_in = torch.empty(tb, dtype=torch.uint8, pin_memory=True)
-        self.host = torch.empty(tb, dtype=torch.uint8, pin_memory=True)
-        self.counter = torch.empty(4, dtype=torch.uint8, pin_memory=True)
-
-    def key(self):
-        return (self.max_vertices, self.max_rings, self.H, self.W)
+        super().__init__((max_vertices, max_rings, H, W), device, scratch=sb, table_in=tb, table=tb, host=tb)
+        self.host_in, self.counter = pinned(tb), pinned(4)
 
 
 def _empty(device, outlines: dict) -> dict:
@@ -103,14 +94,10 @@ def _check_args(outlines, labels, tolerance, max_rounds):
         raise InsarError(f"{who}: tolerance={tolerance!r}: a number of pixels")
     if not math.isfinite(float(tolerance)) or not 0.0 <= float(tolerance) <= MAX_TOLERANCE:
         raise InsarError(f"{who}: tolerance={tolerance!r}: finite, 0 .. {MAX_TOLERANCE:g}")
-    if isinstance(max_rounds, bool) or not isinstance(max_rounds, (int, np.integer)) or not 1 <= max_rounds <= MAX_ROUNDS:
-        raise InsarError(f"{who}: max_rounds={max_rounds!r}: an integer in 1 .. {MAX_ROUNDS}")
+    check_int(who, "max_rounds", max_rounds, 1, MAX_ROUNDS, integral_floats=False)
     H = W = 0
     if labels is not None:
-        if not isinstance(labels, torch.Tensor):
-            raise InsarError(f"{who}: labels must be a torch tensor, got {type(labels).__name__}")
-        if labels.dtype != torch.int32 or labels.dim() != 2 or not labels.is_contiguous():
-            raise InsarError(f"{who}: labels must be a contiguous 2-D int32 tensor, got {labels.dtype} {tuple(labels.shape)}")
+        check_map(who, "labels", labels, (torch.int32,))
         H, W = labels.shape
         if not (1 <= H <= MAX_DIM and 1 <= W <= MAX_DIM):
             raise InsarError(f"{who}: label map {H} x {W}: 1 <= H, W <= {MAX_DIM}")
@@ -168,8 +155,7 @@ def simplify_outlines(outlines: dict, labels: Optional[torch.Tensor] = None, *, 
     V = int(v.shape[0])
     if V == 0:
         return _empty(v.device, outlines)
-    if not v.is_cuda:
-        raise InsarError("simplify_outlines: vertices must be a ROCm tensor (no CPU fallback)")
+    check_on_device("simplify_outlines", "vertices", v)
     if scratch is None:
         scratch = SimplifyScratch(V, R, H, W, v.device)
     elif scratch.max_vertices < V or scratch.max_rings < R or scratch.scratch.device != v.device \
@@ -191,7 +177,6 @@ def simplify_outlines(outlines: dict, labels: Optional[torch.Tensor] = None, *, 
     sp, tp, ip = ptr(scratch.scratch), ptr(scratch.table), ptr(scratch.table_in)
     with torch.cuda.device(v.device):
         s = _lib.stream_ptr()
-        stream = torch.cuda.current_stream()
         scratch.table_in[:nbytes].copy_(scratch.host_in[:nbytes], non_blocking=True)
         call("insar_simplify_setup", ptr(v), V, ip, R, ptr(labels), H, W, vm, rm, sp, s)
         r, total = 0, max_rounds + 1                             # the last round is the probe
@@ -200,14 +185,10 @@ def simplify_outlines(outlines: dict, labels: Optional[torch.Tensor] = None, *, 
             call("insar_simplify_rounds", ptr(v), V, ip, R, q2, r, n, max_rounds, vm, rm, sp, s)
             r += n
             if r < total:
-                scratch.counter.copy_(scratch.scratch[4 * (r - 1):4 * r], non_blocking=True)
-                stream.synchronize()
-                if int(scratch.counter.numpy().view(np.int32)[0]) == 0:
+                if int(read_back(scratch.counter, scratch.scratch[4 * (r - 1):4 * r]).view(np.int32)[0]) == 0:
                     break
         call("insar_simplify_finish", ptr(v), V, ip, R, max_rounds, vm, rm, sp, tp, ptr(out_v), ptr(out_k), s)
-        scratch.host[:nbytes].copy_(scratch.table[:nbytes], non_blocking=True)
-        stream.synchronize()
-    raw = scratch.host.numpy()[:nbytes].view(RING_DTYPE)
+        raw = read_back(scratch.host, scratch.table, nbytes).view(RING_DTYPE)
     head, rec = raw[0], raw[1:]
     kept = int(head["count"])
     out = {"ring": np.arange(R, dtype=np.int32)}

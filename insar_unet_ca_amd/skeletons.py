@@ -20,7 +20,6 @@ from the bottom left to the top right 135.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Optional
 
 import numpy as np
@@ -28,7 +27,8 @@ import torch
 
 from . import _lib
 from ._lib import InsarError, call, ptr
-from .distance import DistanceScratch, _check_int, distance_transform
+from ._scene import Scratch, check_int, check_map, check_on_device, query_bytes, read_back
+from .distance import DistanceScratch, distance_transform
 from .regions import DEFAULT_MAX_REGIONS
 
 MAX_DIM = 32767
@@ -48,9 +48,7 @@ TABLE_FIELDS = ("label", "n", "length", "mean_width", "max_width", "orientation"
 
 def scratch_bytes(H: int, W: int, max_iterations: int = 32, max_regions: int = DEFAULT_MAX_REGIONS):
     """(scratch bytes, table bytes) of an H x W map thinned for max_iterations with max_regions records. Host arithmetic only."""
-    s, t = C.c_int64(0), C.c_int64(0)
-    call("insar_skeleton_scratch_bytes", int(H), int(W), int(max_iterations), int(max_regions), C.byref(s), C.byref(t))
-    return int(s.value), int(t.value)
+    return query_bytes("insar_skeleton_scratch_bytes", H, W, max_iterations, max_regions, outputs=2)
 
 
 def launches(H: int, W: int, max_iterations: int = 32, widths: bool = True) -> int:
@@ -61,21 +59,16 @@ def launches(H: int, W: int, max_iterations: int = 32, widths: bool = True) -> i
     return n
 
 
-class SkeletonScratch:
+class SkeletonScratch(Scratch):
     """The device buffers of one (H, W, max_iterations, max_regions): the bit planes and flags, the table, the pinned host copy
     the table is read back into, and the distance transform's scratch once widths have used it. Nothing in them has to survive
     between calls. The skeleton map is the caller's: every call returns a fresh one."""
+    KEY, DEVICE_AT = ("H", "W", "max_iterations", "max_regions"), 2
 
     def __init__(self, H: int, W: int, device, max_iterations: int = 32, max_regions: int = DEFAULT_MAX_REGIONS):
         sb, tb = scratch_bytes(H, W, max_iterations, max_regions)
-        self.H, self.W, self.max_iterations, self.max_regions = int(H), int(W), int(max_iterations), int(max_regions)
-        self.scratch = torch.empty(sb, dtype=torch.uint8, device=device)
-        self.table = torch.empty(tb, dtype=torch.uint8, device=device)
-        self.host = torch.empty(tb, dtype=torch.uint8, pin_memory=True)
+        super().__init__((H, W, max_iterations, max_regions), device, scratch=sb, table=tb, host=tb)
         self.distance = None
-
-    def key(self):
-        return (self.H, self.W, self.max_iterations, self.max_regions)
 
     def distance_scratch(self) -> DistanceScratch:
         if self.distance is None:
@@ -86,26 +79,17 @@ class SkeletonScratch:
 def _check_args(labels, max_iterations, widths, max_regions, scratch):
     """Everything but the device."""
     who = "thin_regions"
-    if not isinstance(labels, torch.Tensor):
-        raise InsarError(f"{who}: labels must be a torch tensor, got {type(labels).__name__}")
-    if labels.dtype != torch.int32 or labels.dim() != 2 or not labels.is_contiguous():
-        raise InsarError(f"{who}: labels must be a contiguous 2-D int32 tensor, got {labels.dtype} {tuple(labels.shape)}")
+    check_map(who, "labels", labels, (torch.int32,))
     H, W = labels.shape
     if H < 1 or W < 1 or H > MAX_DIM or W > MAX_DIM:
         raise InsarError(f"{who}: map {H} x {W}: need 1 <= H, W <= {MAX_DIM}")
-    mi = _check_int(who, "max_iterations", max_iterations, 1, MAX_ITERATIONS)
+    mi = check_int(who, "max_iterations", max_iterations, 1, MAX_ITERATIONS, integral_floats=True)
     if not isinstance(widths, (bool, np.bool_)):
         raise InsarError(f"{who}: widths={widths!r}: True or False")
-    if isinstance(max_regions, bool) or not isinstance(max_regions, (int, np.integer)) or max_regions < 1 or max_regions > 1 << 30:
-        raise InsarError(f"max_regions={max_regions!r}: a positive integer, at most 2^30")
+    max_regions = check_int(who, "max_regions", max_regions, 1, 1 << 30, integral_floats=False)
     if scratch is not None:
-        if not isinstance(scratch, SkeletonScratch):
-            raise InsarError(f"{who}: scratch must be a SkeletonScratch, got {type(scratch).__name__}")
-        if scratch.key() != (H, W, mi, int(max_regions)) or scratch.scratch.device != labels.device:
-            raise InsarError(f"{who}: scratch of {scratch.H} x {scratch.W}, max_iterations={scratch.max_iterations}, "
-                             f"max_regions={scratch.max_regions} on {scratch.scratch.device} for a {H} x {W} map, "
-                             f"max_iterations={mi}, max_regions={int(max_regions)} on {labels.device}")
-    return int(H), int(W), mi, int(max_regions)
+        SkeletonScratch.check(who, scratch, (H, W, mi, max_regions), labels.device)
+    return int(H), int(W), mi, max_regions
 
 
 def stats_from_table(raw: np.ndarray, n_labels: int) -> Dict[str, np.ndarray]:
@@ -177,8 +161,7 @@ def thin_regions(labels: torch.Tensor, *, max_iterations: int = 32, widths: bool
     whatever the map holds, and ONE read-back, of the table, at the end. A label above `max_regions` raises InsarError.
     `scratch`: a SkeletonScratch of this map size, max_iterations and max_regions to reuse (else allocated)."""
     H, W, mi, max_regions = _check_args(labels, max_iterations, widths, max_regions, scratch)
-    if not labels.is_cuda:
-        raise InsarError("thin_regions: labels must be a ROCm tensor (no CPU fallback)")
+    check_on_device("thin_regions", "labels", labels)
     if scratch is None:
         scratch = SkeletonScratch(H, W, labels.device, mi, max_regions)
     steps = launches(H, W, mi, False) - 2
@@ -195,9 +178,7 @@ def thin_regions(labels: torch.Tensor, *, max_iterations: int = 32, widths: bool
         call("insar_skeleton_stats", ptr(labels), ptr(d2), H, W, mi, max_regions, sp, tp, ptr(skeleton), s)
         # the header first in the same copy: the records worth reading are bounded by the pixels, whatever max_regions is
         nbytes = STAT_DTYPE.itemsize * (1 + min(max_regions, H * W))
-        scratch.host[:nbytes].copy_(scratch.table[:nbytes], non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-    raw = scratch.host.numpy()[:nbytes]
+        raw = read_back(scratch.host, scratch.table, nbytes)
     head = raw.view(STAT_DTYPE)[0]
     largest = int(head["n_junction"])
     if int(head["n_orth"]) != 0 or largest > max_regions:

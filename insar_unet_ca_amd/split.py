@@ -21,7 +21,6 @@ the scene edge, and a label that fills the whole map is one plateau and comes ba
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Optional
 
 import numpy as np
@@ -29,7 +28,8 @@ import torch
 
 from . import _lib
 from ._lib import InsarError, call, ptr
-from .distance import MAX_DIM, DistanceScratch, _check_int, distance_transform
+from ._scene import Scratch, check_int, check_map, check_on_device, pinned, query_bytes, read_back
+from .distance import MAX_DIM, DistanceScratch, distance_transform
 from .regions import CONF_SCALE, DEFAULT_MAX_REGIONS
 
 DEFAULT_MAX_PAIRS = 1 << 20
@@ -50,37 +50,20 @@ assert SPLIT_DTYPE.itemsize == 80
 def scratch_bytes(H: int, W: int, max_regions: int = DEFAULT_MAX_REGIONS, max_pairs: int = DEFAULT_MAX_PAIRS,
                   max_rounds: int = 64):
     """(scratch bytes, table bytes, offset of the control words in the scratch, their bytes). Host arithmetic only."""
-    s, t, o, c = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
-    call("insar_split_scratch_bytes", int(H), int(W), int(max_regions), int(max_pairs), int(max_rounds), C.byref(s), C.byref(t),
-         C.byref(o), C.byref(c))
-    return int(s.value), int(t.value), int(o.value), int(c.value)
+    return query_bytes("insar_split_scratch_bytes", H, W, max_regions, max_pairs, max_rounds, outputs=4)
 
 
-class SplitScratch:
+class SplitScratch(Scratch):
     """The device buffers of one (H, W, max_regions, max_pairs, max_rounds): scratch, the piece table, and the pinned host
     copies of the table and the control words. Nothing in them has to survive between calls."""
+    KEY, DEVICE_AT = ("H", "W", "max_regions", "max_pairs", "max_rounds"), 2
 
     def __init__(self, H: int, W: int, device, max_regions: int = DEFAULT_MAX_REGIONS, max_pairs: int = DEFAULT_MAX_PAIRS,
                  max_rounds: int = 64):
         sb, tb, off, cb = scratch_bytes(H, W, max_regions, max_pairs, max_rounds)
-        self.H, self.W = int(H), int(W)
-        self.max_regions, self.max_pairs, self.max_rounds = int(max_regions), int(max_pairs), int(max_rounds)
-        self.scratch = torch.empty(sb, dtype=torch.uint8, device=device)
-        self.ctrl = self.scratch[off:off + cb]
-        self.table = torch.empty(tb, dtype=torch.uint8, device=device)
-        self.host = torch.empty(tb, dtype=torch.uint8, pin_memory=True)
-        self.ctrl_host = torch.empty(cb, dtype=torch.uint8, pin_memory=True)
+        super().__init__((H, W, max_regions, max_pairs, max_rounds), device, scratch=sb, table=tb, host=tb)
+        self.ctrl, self.ctrl_host = self.scratch[off:off + cb], pinned(cb)
         self.distance = None                                      # DistanceScratch of the default height map, made on first use
-
-
-def _check_map(who: str, name: str, m, dtype, shape=None):
-    if not isinstance(m, torch.Tensor):
-        raise InsarError(f"{who}: {name} must be a torch tensor, got {type(m).__name__}")
-    if m.dtype != dtype or m.dim() != 2 or not m.is_contiguous():
-        raise InsarError(f"{who}: {name} must be a contiguous 2-D {str(dtype).replace('torch.', '')} tensor, got {m.dtype} "
-                         f"{tuple(m.shape)}")
-    if shape is not None and tuple(m.shape) != tuple(shape):
-        raise InsarError(f"{who}: {name} {tuple(m.shape)} for labels {tuple(shape)}")
 
 
 def _threshold(who: str, min_depth, squared: bool) -> int:
@@ -97,16 +80,16 @@ def _threshold(who: str, min_depth, squared: bool) -> int:
 def _check_args(labels, mask, conf, height, squared, min_depth, max_distance, max_regions, max_pairs, max_rounds, scratch):
     """(H, W, squared, T, R): everything but the launches; the devices are looked at last."""
     who = "split_regions"
-    _check_map(who, "labels", labels, torch.int32)
+    check_map(who, "labels", labels, (torch.int32,))
     H, W = labels.shape
     if H < 1 or W < 1 or H > MAX_DIM or W > MAX_DIM or H * W >= 1 << 31:
         raise InsarError(f"{who}: labels {H} x {W}: need 1 <= H, W <= {MAX_DIM} and H * W < 2^31")
     if mask is not None:
-        _check_map(who, "mask", mask, torch.uint8, (H, W))
+        check_map(who, "mask", mask, (torch.uint8,), shape=(H, W))
     if conf is not None:
-        _check_map(who, "conf", conf, torch.float32, (H, W))
+        check_map(who, "conf", conf, (torch.float32,), shape=(H, W))
     if height is not None:
-        _check_map(who, "height", height, torch.int32, (H, W))
+        check_map(who, "height", height, (torch.int32,), shape=(H, W))
         if max_distance is not None:
             raise InsarError(f"{who}: max_distance belongs to the default height map, not to height=")
     if squared is None:
@@ -114,22 +97,16 @@ def _check_args(labels, mask, conf, height, squared, min_depth, max_distance, ma
     if not isinstance(squared, (bool, np.bool_)):
         raise InsarError(f"{who}: squared={squared!r}: True, False or None")
     T = _threshold(who, min_depth, bool(squared))
-    R = 0 if max_distance is None else _check_int(who, "max_distance", max_distance, 1, MAX_DIM)
-    _check_int(who, "max_regions", max_regions, 1, (1 << 31) - 2)
-    _check_int(who, "max_pairs", max_pairs, 1, MAX_PAIRS)
-    _check_int(who, "max_rounds", max_rounds, 1, MAX_ROUNDS)
+    R = 0 if max_distance is None else check_int(who, "max_distance", max_distance, 1, MAX_DIM, integral_floats=True)
+    caps = (check_int(who, "max_regions", max_regions, 1, (1 << 31) - 2, integral_floats=True),
+            check_int(who, "max_pairs", max_pairs, 1, MAX_PAIRS, integral_floats=True),
+            check_int(who, "max_rounds", max_rounds, 1, MAX_ROUNDS, integral_floats=True))
     if scratch is not None:
-        if not isinstance(scratch, SplitScratch):
-            raise InsarError(f"{who}: scratch must be a SplitScratch, got {type(scratch).__name__}")
-        have = (scratch.H, scratch.W, scratch.max_regions, scratch.max_pairs, scratch.max_rounds)
-        if have != (H, W, int(max_regions), int(max_pairs), int(max_rounds)) or scratch.scratch.device != labels.device:
-            raise InsarError(f"{who}: scratch of (H, W, max_regions, max_pairs, max_rounds) = {have} on {scratch.scratch.device} for "
-                             f"{(H, W, int(max_regions), int(max_pairs), int(max_rounds))} on {labels.device}")
-    if not labels.is_cuda:
-        raise InsarError(f"{who}: labels must be a ROCm tensor (no CPU fallback)")
+        SplitScratch.check(who, scratch, (H, W) + caps, labels.device)
+    check_on_device(who, "labels", labels)
     for name, t in (("mask", mask), ("conf", conf), ("height", height)):
-        if t is not None and t.device != labels.device:
-            raise InsarError(f"{who}: {name} on {t.device}, labels on {labels.device}")
+        if t is not None:
+            check_on_device(who, name, t, like=labels)
     return int(H), int(W), bool(squared), T, R
 
 
@@ -186,15 +163,12 @@ def split_regions(labels: torch.Tensor, *, mask: Optional[torch.Tensor] = None, 
     out = torch.empty(H, W, dtype=torch.int32, device=labels.device)
     with torch.cuda.device(labels.device):
         s = _lib.stream_ptr()
-        stream = torch.cuda.current_stream()
         call("insar_split_basins", ptr(labels), ptr(height), H, W, max_pairs, max_rounds, ptr(scratch.scratch), s)
         done, rounds, converged = 0, max_rounds, False
         while done < max_rounds and not converged:
             n = min(ROUNDS_PER_READ, max_rounds - done)
             call("insar_split_rounds", ptr(height), H, W, int(squared), T, done, n, max_pairs, max_rounds, ptr(scratch.scratch), s)
-            scratch.ctrl_host.copy_(scratch.ctrl, non_blocking=True)
-            stream.synchronize()
-            ctrl = scratch.ctrl_host.numpy().view(np.int32)
+            ctrl = read_back(scratch.ctrl_host, scratch.ctrl).view(np.int32)
             if done == 0:
                 if ctrl[2]:
                     raise InsarError(f"{who}: height is negative on {int(ctrl[2])} foreground pixels")
@@ -207,9 +181,7 @@ def split_regions(labels: torch.Tensor, *, mask: Optional[torch.Tensor] = None, 
                 rounds, converged = int(idle[0]), True
         call("insar_split_finish", ptr(labels), ptr(height), ptr(mask), ptr(conf), H, W, max_regions, max_pairs, max_rounds,
              ptr(scratch.scratch), ptr(scratch.table), ptr(out), s)
-        scratch.host.copy_(scratch.table, non_blocking=True)
-        stream.synchronize()
-    raw = scratch.host.numpy()
+        raw = read_back(scratch.host, scratch.table)
     regions = pieces_from_table(raw, W, max_regions, conf is not None)
     return {"labels": out, "regions": regions, "count": int(len(regions["id"])), "raw_basins": int(raw.view(SPLIT_DTYPE)["y0"][0]),
             "rounds": rounds, "converged": converged}

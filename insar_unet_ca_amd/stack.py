@@ -13,7 +13,6 @@ Everything the device computes is an integer and defined by one scan over the da
 observation neither breaks nor extends a run. Nothing is read back before the series table."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Dict, Iterable, Optional, Sequence
 
@@ -22,6 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import InsarError, call, ptr
+from ._scene import Scratch, check_int, check_on_device, is_int, query_bytes, read_back
 from .regions import DEFAULT_MAX_REGIONS, label_regions
 
 MAX_WORDS = 4
@@ -31,18 +31,14 @@ _PLANE_DTYPE = {p: (torch.uint8 if p in ("known", "persistent") else torch.int16
 SERIES_HEADER = 4                                                 # int32 words before the first row of the table
 
 
-def _is_int(v) -> bool:
-    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
-
-
 def class_words(classes) -> tuple:
     """The class set as four 64-bit words: class c is bit c & 63 of word c >> 6. `classes`: one class or an iterable."""
-    cs = [classes] if _is_int(classes) else classes
+    cs = [classes] if is_int(classes) else classes
     try:
         cs = list(cs)
     except TypeError:
         raise InsarError(f"classes={classes!r}: a class or an iterable of classes in 0..255") from None
-    if not cs or not all(_is_int(c) and 0 <= c <= 255 for c in cs):
+    if not cs or not all(is_int(c) and 0 <= c <= 255 for c in cs):
         raise InsarError(f"classes={classes!r}: at least one class, each an integer in 0..255")
     w = [0, 0, 0, 0]
     for c in cs:
@@ -55,23 +51,27 @@ def _check_fraction(name: str, f) -> tuple:
         num, den = f
     except (TypeError, ValueError):
         raise InsarError(f"{name}={f!r}: two integers (num, den)") from None
-    if not (_is_int(num) and _is_int(den)) or den < 1 or den >= 1 << 31 or not 0 <= num <= den:
+    if not (is_int(num) and is_int(den)) or den < 1 or den >= 1 << 31 or not 0 <= num <= den:
         raise InsarError(f"{name}={f!r}: integers with 0 <= num <= den, 1 <= den < 2^31")
     return int(num), int(den)
 
 
 def _check_window(T: int, n_dates: int, t0, t1) -> tuple:
     t1 = n_dates if t1 is None else t1
-    if not (_is_int(t0) and _is_int(t1)) or not 0 <= t0 <= t1 <= T:
+    if not (is_int(t0) and is_int(t1)) or not 0 <= t0 <= t1 <= T:
         raise InsarError(f"window t0={t0!r}, t1={t1!r}: integers with 0 <= t0 <= t1 <= {T} dates")
     return int(t0), int(t1)
 
 
+def _check_caps(who: str, max_regions, count=None) -> None:
+    check_int(who, "max_regions", max_regions, 1, 1 << 24, integral_floats=False)
+    if count is not None:
+        check_int(who, "count", count, 0, max_regions, integral_floats=False, expect=f"an integer in 0..max_regions={max_regions}")
+
+
 def series_bytes(max_regions: int = DEFAULT_MAX_REGIONS, n_dates: int = 64) -> int:
     """Bytes of the series table for max_regions rows of n_dates dates. Host arithmetic only."""
-    b = C.c_int64(0)
-    call("insar_stack_series_bytes", int(max_regions), int(n_dates), C.byref(b))
-    return int(b.value)
+    return query_bytes("insar_stack_series_bytes", max_regions, n_dates, outputs=1)
 
 
 class DetectionStack:
@@ -85,11 +85,9 @@ class DetectionStack:
     """
 
     def __init__(self, H: int, W: int, device, words: int = 1):
-        if not (_is_int(H) and _is_int(W)) or H < 1 or W < 1 or H * W >= 1 << 31:
+        if not (is_int(H) and is_int(W)) or H < 1 or W < 1 or H * W >= 1 << 31:
             raise InsarError(f"DetectionStack: grid {H!r} x {W!r}: integers with H, W >= 1 and H * W < 2^31")
-        if not _is_int(words) or not 1 <= words <= MAX_WORDS:
-            raise InsarError(f"words={words!r}: an integer in 1..{MAX_WORDS} (64 dates each)")
-        self.H, self.W, self.words = int(H), int(W), int(words)
+        self.H, self.W, self.words = int(H), int(W), check_int("DetectionStack", "words", words, 1, MAX_WORDS, integral_floats=False)
         self.device = torch.device(device)
         self.hit = torch.zeros(self.words, self.H, self.W, dtype=torch.int64, device=self.device)
         self.valid = torch.zeros(self.words, self.H, self.W, dtype=torch.int64, device=self.device)
@@ -100,8 +98,7 @@ class DetectionStack:
         return 64 * self.words
 
     def _on_device(self, who: str) -> None:
-        if not self.hit.is_cuda:
-            raise InsarError(f"{who}: the stack must live on a ROCm device (no CPU fallback)")
+        check_on_device(who, "the stack", self.hit)
 
     def _plane_input(self, who: str, name: str, x, dtype, n: Optional[int]):
         if not isinstance(x, torch.Tensor):
@@ -130,12 +127,11 @@ class DetectionStack:
         if conf is not None:
             self._plane_input(who, "conf", conf, torch.float32, n)
         t = self.n_dates if t is None else t
-        if not _is_int(t) or t < 0 or t + n > self.T:
-            raise InsarError(f"{who}: dates {t!r}..{t + n - 1 if _is_int(t) else '?'} beyond the stack's 0..{self.T - 1} ({self.words} words)")
+        if not is_int(t) or t < 0 or t + n > self.T:
+            raise InsarError(f"{who}: dates {t!r}..{t + n - 1 if is_int(t) else '?'} beyond the stack's 0..{self.T - 1} ({self.words} words)")
         cw = class_words(classes)
-        ignore = -1 if ignore is None else ignore
-        if not _is_int(ignore) or not -1 <= ignore <= 255:
-            raise InsarError(f"ignore={ignore!r}: a class value in 0..255, or None")
+        ignore = check_int(who, "ignore", -1 if ignore is None else ignore, -1, 255, integral_floats=False,
+                           expect="a class value in 0..255, or None")
         try:
             mc = float(np.float32(min_conf))
         except (TypeError, ValueError):
@@ -144,8 +140,8 @@ class DetectionStack:
             raise InsarError(f"min_conf={min_conf!r}: a finite number")
         self._on_device(who)
         for name, x in (("mask", mask), ("valid", valid), ("conf", conf)):
-            if x is not None and (not x.is_cuda or x.device != self.hit.device):
-                raise InsarError(f"{who}: {name} must be a ROCm tensor on the stack's device (no CPU fallback)")
+            if x is not None:
+                check_on_device(who, name, x, like=self.hit)
         with torch.cuda.device(self.hit.device):
             call("insar_stack_push", ptr(mask), ptr(valid), ptr(conf), mc, cw[0], cw[1], cw[2], cw[3], int(ignore), n, int(t), self.words,
                  self.H, self.W, ptr(self.hit), ptr(self.valid), _lib.stream_ptr())
@@ -154,8 +150,7 @@ class DetectionStack:
 
     def shift(self, k: int) -> None:
         """Drop the k oldest dates in place: date t takes date t + k, the top k dates become unobserved. k >= T clears."""
-        if not _is_int(k) or k < 0 or k >= 1 << 31:
-            raise InsarError(f"shift: k={k!r}: a non-negative integer")
+        check_int("DetectionStack.shift", "k", k, 0, (1 << 31) - 1, integral_floats=False)
         self._on_device("DetectionStack.shift")
         with torch.cuda.device(self.hit.device):
             call("insar_stack_shift", ptr(self.hit), ptr(self.valid), self.words, self.H, self.W, int(k), _lib.stream_ptr())
@@ -170,8 +165,7 @@ class DetectionStack:
         allocated."""
         t0, t1 = _check_window(self.T, self.n_dates, t0, t1)
         for name, v in (("min_hits", min_hits), ("min_run", min_run), ("min_valid", min_valid)):
-            if not _is_int(v) or not 0 <= v <= 32767:
-                raise InsarError(f"{name}={v!r}: an integer in 0..32767")
+            check_int("DetectionStack.summary", name, v, 0, 32767, integral_floats=False)
         num, den = _check_fraction("min_fraction", min_fraction)
         want = [want] if isinstance(want, str) else list(want)
         if not want or any(p not in SUMMARY_PLANES for p in want) or len(set(want)) != len(want):
@@ -197,29 +191,22 @@ class DetectionStack:
             if not isinstance(x, torch.Tensor) or x.dtype != torch.int64 or tuple(x.shape) != want:
                 raise InsarError(f"load_state_dict: {name} must be an int64 tensor {want}, got "
                                  f"{getattr(x, 'dtype', type(x).__name__)} {tuple(getattr(x, 'shape', ()))}")
-        if not _is_int(n_dates) or not 0 <= n_dates <= self.T:
-            raise InsarError(f"load_state_dict: n_dates={n_dates!r} outside 0..{self.T}")
+        check_int("load_state_dict", "n_dates", n_dates, 0, self.T, integral_floats=False)
         self.hit.copy_(hit)
         self.valid.copy_(valid)
         self.n_dates = int(n_dates)
 
 
-class StackScratch:
+class StackScratch(Scratch):
     """The device series table of one (max_regions, n_dates) and the pinned host copy it is read back into. Nothing in it
     has to survive between calls. `table`: a contiguous uint8 device tensor of exactly `series_bytes(...)` bytes, 16-byte
     aligned, to use instead of a fresh allocation."""
+    KEY = ("max_regions", "n_dates")
 
     def __init__(self, device: torch.device, max_regions: int = DEFAULT_MAX_REGIONS, n_dates: int = 64,
                  table: Optional[torch.Tensor] = None):
         tb = series_bytes(max_regions, n_dates)
-        self.max_regions, self.n_dates = int(max_regions), int(n_dates)
-        if table is None:
-            table = torch.empty(tb, dtype=torch.uint8, device=device)
-        elif (not isinstance(table, torch.Tensor) or table.dtype != torch.uint8 or table.dim() != 1 or table.numel() != tb
-              or not table.is_contiguous() or table.data_ptr() % 16):
-            raise InsarError(f"StackScratch: table must be a contiguous 16-byte aligned uint8 tensor of {tb} bytes")
-        self.table = table
-        self.host = torch.empty(tb, dtype=torch.uint8, pin_memory=True)
+        super().__init__((max_regions, n_dates), device, table=self.adopt_table("StackScratch", table, tb), host=tb)
 
 
 def scan_runs(hit: np.ndarray, valid: np.ndarray, t0: int = 0) -> Dict[str, np.ndarray]:
@@ -261,31 +248,25 @@ def series_from_table(raw: np.ndarray, *, max_regions: int, n_dates: int, count:
 
 
 def _check_series_args(stack, labels, max_regions, count, t0, t1, active_fraction, scratch):
+    who = "site_series"
     if not isinstance(stack, DetectionStack):
-        raise InsarError(f"site_series: stack must be a DetectionStack, got {type(stack).__name__}")
+        raise InsarError(f"{who}: stack must be a DetectionStack, got {type(stack).__name__}")
     if not isinstance(labels, torch.Tensor):
-        raise InsarError(f"site_series: labels must be a torch tensor, got {type(labels).__name__}")
+        raise InsarError(f"{who}: labels must be a torch tensor, got {type(labels).__name__}")
     if labels.dtype != torch.int32 or tuple(labels.shape) != (stack.H, stack.W):
-        raise InsarError(f"site_series: labels must be an int32 [{stack.H}, {stack.W}] tensor, got {labels.dtype} {tuple(labels.shape)}")
+        raise InsarError(f"{who}: labels must be an int32 [{stack.H}, {stack.W}] tensor, got {labels.dtype} {tuple(labels.shape)}")
     if not labels.is_contiguous():
-        raise InsarError("site_series: labels must be contiguous")
-    if not _is_int(max_regions) or not 1 <= max_regions <= 1 << 24:
-        raise InsarError(f"max_regions={max_regions!r}: an integer in 1..2^24")
-    if count is not None and (not _is_int(count) or not 0 <= count <= max_regions):
-        raise InsarError(f"count={count!r}: an integer in 0..max_regions={max_regions}")
+        raise InsarError(f"{who}: labels must be contiguous")
+    _check_caps(who, max_regions, count)
     t0, t1 = _check_window(stack.T, stack.n_dates, t0, t1)
     _check_fraction("active_fraction", active_fraction)
+    key = (int(max_regions), t1 - t0)
     if scratch is not None:
-        got = (getattr(scratch, "max_regions", None), getattr(scratch, "n_dates", None))
-        table = getattr(scratch, "table", None)
-        want = series_bytes(max_regions, t1 - t0)
-        if got != (int(max_regions), t1 - t0) or not isinstance(table, torch.Tensor) or table.numel() != want:
-            raise InsarError(f"site_series: scratch of max_regions={got[0]}, n_dates={got[1]} for max_regions={max_regions}, "
-                             f"n_dates={t1 - t0} ({want} bytes)")
-    if not stack.hit.is_cuda or not labels.is_cuda or labels.device != stack.hit.device:
-        raise InsarError("site_series: the stack and labels must be ROCm tensors on one device (no CPU fallback)")
+        StackScratch.check(who, scratch, key, table_bytes=series_bytes(*key))
+    stack._on_device(who)
+    check_on_device(who, "labels", labels, like=stack.hit)
     if scratch is not None and scratch.table.device != labels.device:
-        raise InsarError("site_series: the scratch lives on another device")
+        raise InsarError(f"{who}: the scratch lives on {scratch.table.device}, labels on {labels.device}")
     return t0, t1
 
 
@@ -312,9 +293,8 @@ def site_series(stack: DetectionStack, labels: torch.Tensor, *, max_regions: int
         call("insar_stack_series_clear", ptr(scratch.table), max_regions, nt, s)
         call("insar_stack_series", ptr(stack.hit), ptr(stack.valid), stack.words, ptr(labels), stack.H, stack.W, t0, t1, max_regions,
              ptr(scratch.table), s)
-        scratch.host[:nbytes].copy_(scratch.table[:nbytes], non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-    return series_from_table(scratch.host.numpy()[:nbytes], max_regions=max_regions, n_dates=nt, count=count, t0=t0,
+        raw = read_back(scratch.host, scratch.table, nbytes)
+    return series_from_table(raw, max_regions=max_regions, n_dates=nt, count=count, t0=t0,
                              active_fraction=active_fraction)
 
 
@@ -335,8 +315,7 @@ def follow_sites(stack: DetectionStack, *, connectivity: int = 8, min_area: int 
     want = [want] if isinstance(want, str) else list(want)
     if "persistent" not in want:
         want.append("persistent")
-    if not _is_int(max_regions) or not 1 <= max_regions <= 1 << 24:
-        raise InsarError(f"max_regions={max_regions!r}: an integer in 1..2^24")
+    _check_caps("follow_sites", max_regions)
     _check_fraction("active_fraction", active_fraction)
     planes = stack.summary(t0, t1, want=want, **rule)
     reg = label_regions(planes["persistent"], connectivity=connectivity, min_area=min_area, max_regions=max_regions,

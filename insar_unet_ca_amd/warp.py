@@ -24,8 +24,8 @@ import torch
 
 from . import _lib
 from ._lib import InsarError, call, ptr
+from ._scene import check_int, check_on_device, inverse_affine, is_int
 from .augment import MASK64
-from .rasterise import _inverse_affine
 
 WARP_STREAM = 0x9FB21C651E98DF25            # separates the warp draws from the crop draws of one batch key
 Q32 = 1 << 32
@@ -82,7 +82,7 @@ def grid_matrix(src_transform, dst_transform) -> np.ndarray:
     (x, y) to world coordinates, world = A @ (x, y, 1), in the convention of `to_polygons(transform=)` and `from_geojson`:
     lattice points are pixel corners, pixel (i, j) has its centre at lattice (j + 0.5, i + 0.5). The source transform is
     inverted as `pack_polygons` inverts one; a singular or non-finite transform raises InsarError."""
-    inv, t = _inverse_affine(src_transform)
+    inv, t = inverse_affine(src_transform)
     B = np.asarray(dst_transform, dtype=np.float64)
     if B.shape != (2, 3):
         raise InsarError(f"transform must be a 2 x 3 affine, got shape {B.shape}")
@@ -94,8 +94,7 @@ def grid_matrix(src_transform, dst_transform) -> np.ndarray:
 
 
 def _check_source(who: str, src, dtypes) -> Tuple[int, int, int]:
-    if not isinstance(src, torch.Tensor) or not src.is_cuda:
-        raise InsarError(f"{who}: src must be a ROCm tensor (no CPU fallback)")
+    check_on_device(who, "src", src)
     if src.dtype not in dtypes:
         raise InsarError(f"{who}: src dtype {src.dtype}: {' or '.join(str(d) for d in dtypes)}")
     if src.dim() not in (2, 3) or not src.is_contiguous():
@@ -186,7 +185,7 @@ def multilook(src: torch.Tensor, fy: int, fx: Optional[int] = None, *, min_valid
     C, H, W = _check_source(who, src, (torch.uint8, torch.float32))
     fx = fy if fx is None else fx
     for name, v in (("fy", fy), ("fx", fx), ("min_valid", min_valid)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        if not is_int(v):
             raise InsarError(f"{who}: {name}={v!r}: an integer")
     fy, fx, min_valid = int(fy), int(fx), int(min_valid)
     if not (1 <= fy <= 16 and 1 <= fx <= 16):
@@ -239,8 +238,7 @@ def draw_warps(key: int, origins: torch.Tensor, tile: int, spec: WarpSpec) -> to
     if (not isinstance(origins, torch.Tensor) or not origins.is_cuda or origins.dtype != torch.int32 or origins.dim() != 2
             or origins.shape[1] != 2 or origins.shape[0] < 1 or not origins.is_contiguous()):
         raise InsarError("draw_warps: origins must be a contiguous int32 [n, 2] ROCm tensor")
-    if isinstance(tile, bool) or not isinstance(tile, (int, np.integer)) or not 1 <= tile <= MAX_DIM:
-        raise InsarError(f"draw_warps: tile={tile!r}: an integer in 1..{MAX_DIM}")
+    check_int("draw_warps", "tile", tile, 1, MAX_DIM, integral_floats=False)
     n = int(origins.shape[0])
     with torch.cuda.device(origins.device):
         angles = _device_angles(origins.device)
@@ -270,7 +268,7 @@ def gather_warped(scene: Optional[torch.Tensor], labels: Optional[torch.Tensor],
     if mask_dtype not in _MASK_CODES:
         raise InsarError(f"{who}: mask_dtype {mask_dtype}: torch.int64 or torch.uint8")
     n = _check_matrices(who, matrices, ref.device)
-    if isinstance(tile, bool) or not isinstance(tile, (int, np.integer)) or tile < 4 or tile % 4 or tile > MAX_DIM:
+    if check_int(who, "tile", tile, 4, MAX_DIM, integral_floats=False) % 4:
         raise InsarError(f"{who}: tile={tile!r}: a positive multiple of 4, at most {MAX_DIM}")
     if isinstance(fill, bool) or not isinstance(fill, (int, float, np.integer, np.floating)):
         raise InsarError(f"{who}: fill={fill!r}: a number")

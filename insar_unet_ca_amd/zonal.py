@@ -12,7 +12,6 @@ the table is bitwise reproducible; the float fields are formed on the host in fl
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Dict, Optional
 
@@ -21,6 +20,7 @@ import torch
 
 from . import _lib
 from ._lib import InsarError, call, ptr
+from ._scene import Scratch, check_int, check_on_device, query_bytes, read_back
 from .regions import DEFAULT_MAX_REGIONS
 
 MAX_CHANNELS = 4
@@ -38,27 +38,19 @@ _ELEM = {torch.float32: _lib.ZONAL_F32, torch.uint8: _lib.ZONAL_U8, torch.int32:
 
 def scratch_bytes(max_regions: int = DEFAULT_MAX_REGIONS, bins: int = 0, channels: int = 1) -> int:
     """Bytes of the table for max_regions regions, `bins` histogram bins and `channels` channels. Host arithmetic only."""
-    t = C.c_int64(0)
-    call("insar_zonal_scratch_bytes", int(max_regions), int(bins), int(channels), C.byref(t))
-    return int(t.value)
+    return query_bytes("insar_zonal_scratch_bytes", max_regions, bins, channels, outputs=1)
 
 
-class ZonalScratch:
+class ZonalScratch(Scratch):
     """The device table of one (max_regions, bins, channels) and the pinned host copy it is read back into. Nothing in it
     has to survive between calls. `table`: a contiguous uint8 device tensor of exactly `scratch_bytes(...)` bytes, 16-byte
     aligned, to use instead of a fresh allocation (a view into a larger buffer, for instance)."""
+    KEY = ("max_regions", "bins", "channels")
 
     def __init__(self, device: torch.device, max_regions: int = DEFAULT_MAX_REGIONS, bins: int = 0, channels: int = 1,
                  table: Optional[torch.Tensor] = None):
         tb = scratch_bytes(max_regions, bins, channels)
-        self.max_regions, self.bins, self.channels = int(max_regions), int(bins), int(channels)
-        if table is None:
-            table = torch.empty(tb, dtype=torch.uint8, device=device)
-        elif (not isinstance(table, torch.Tensor) or table.dtype != torch.uint8 or table.dim() != 1 or table.numel() != tb
-              or not table.is_contiguous() or table.data_ptr() % 16):
-            raise InsarError(f"ZonalScratch: table must be a contiguous 16-byte aligned uint8 tensor of {tb} bytes")
-        self.table = table
-        self.host = torch.empty(tb, dtype=torch.uint8, pin_memory=True)
+        super().__init__((max_regions, bins, channels), device, table=self.adopt_table("ZonalScratch", table, tb), host=tb)
 
 
 def quantise_scalar(v: float, scale: float) -> int:
@@ -70,6 +62,7 @@ def quantise_scalar(v: float, scale: float) -> int:
 def _check_args(labels, raster, max_regions, count, scale, nodata, bins, range_, scratch=None):
     """Every refusal, none of which needs a device; the one of host tensors comes last, so that the others can be met on the
     host. Returns (channels, has_nodata, nodata, q_lo, q_hi)."""
+    who = "region_stats"
     if not isinstance(labels, torch.Tensor) or not isinstance(raster, torch.Tensor):
         raise InsarError(f"region_stats: labels and raster must be torch tensors, got {type(labels).__name__}, {type(raster).__name__}")
     if labels.dtype != torch.int32 or labels.dim() != 2:
@@ -86,10 +79,9 @@ def _check_args(labels, raster, max_regions, count, scale, nodata, bins, range_,
         raise InsarError(f"region_stats: {channels} channels: 1..{MAX_CHANNELS}")
     if not labels.is_contiguous() or not raster.is_contiguous():
         raise InsarError("region_stats: labels and raster must be contiguous")
-    if isinstance(max_regions, bool) or int(max_regions) != max_regions or not 1 <= max_regions <= 1 << 24:
-        raise InsarError(f"max_regions={max_regions!r}: an integer in 1..2^24")
-    if count is not None and (isinstance(count, bool) or int(count) != count or not 0 <= count <= max_regions):
-        raise InsarError(f"count={count!r}: an integer in 0..max_regions={max_regions}")
+    check_int(who, "max_regions", max_regions, 1, 1 << 24, integral_floats=True)
+    if count is not None:
+        check_int(who, "count", count, 0, max_regions, integral_floats=True, expect=f"an integer in 0..max_regions={max_regions}")
     try:
         scale_ok = math.isfinite(float(scale)) and float(scale) > 0
     except (TypeError, ValueError):
@@ -106,8 +98,7 @@ def _check_args(labels, raster, max_regions, count, scale, nodata, bins, range_,
             if nd != int(nd) or not lo_t <= int(nd) <= hi_t:
                 raise InsarError(f"nodata={nodata!r} is no value of a {raster.dtype} raster")
         has_nodata = 1
-    if isinstance(bins, bool) or int(bins) != bins or not 0 <= bins <= MAX_BINS:
-        raise InsarError(f"bins={bins!r}: an integer in 0..{MAX_BINS}")
+    check_int(who, "bins", bins, 0, MAX_BINS, integral_floats=True)
     q_lo = q_hi = 0
     if bins > 0:
         try:
@@ -120,17 +111,13 @@ def _check_args(labels, raster, max_regions, count, scale, nodata, bins, range_,
         q_lo, q_hi = quantise_scalar(lo, qs), quantise_scalar(hi, qs)
         if q_lo >= q_hi:
             raise InsarError(f"range={range_!r}: lo >= hi after quantisation ({q_lo} >= {q_hi})")
+    key = (int(max_regions), int(bins), channels)
     if scratch is not None:
-        got = (getattr(scratch, "max_regions", None), getattr(scratch, "bins", None), getattr(scratch, "channels", None))
-        table = getattr(scratch, "table", None)
-        want = scratch_bytes(max_regions, bins, channels)
-        if got != (int(max_regions), int(bins), channels) or not isinstance(table, torch.Tensor) or table.numel() != want:
-            raise InsarError(f"region_stats: scratch of max_regions={got[0]}, bins={got[1]}, channels={got[2]} for "
-                             f"max_regions={max_regions}, bins={bins}, channels={channels} ({want} bytes)")
-    if not labels.is_cuda or not raster.is_cuda or raster.device != labels.device:
-        raise InsarError("region_stats: labels and raster must be ROCm tensors on one device (no CPU fallback)")
+        ZonalScratch.check(who, scratch, key, table_bytes=scratch_bytes(*key))
+    check_on_device(who, "labels", labels)
+    check_on_device(who, "raster", raster, like=labels)
     if scratch is not None and scratch.table.device != labels.device:
-        raise InsarError("region_stats: the scratch lives on another device")
+        raise InsarError(f"{who}: the scratch lives on {scratch.table.device}, labels on {labels.device}")
     return channels, has_nodata, nd, q_lo, q_hi
 
 
@@ -247,8 +234,7 @@ def region_stats(labels: torch.Tensor, raster: torch.Tensor, *, max_regions: int
         call("insar_zonal_clear", ptr(scratch.table), max_regions, bins, channels, s)
         call("insar_zonal_accumulate", ptr(labels), ptr(raster), _ELEM[raster.dtype], channels, H, W, float(scale), has_nodata, nd,
              bins, q_lo, q_hi, max_regions, ptr(scratch.table), s)
-        scratch.host.copy_(scratch.table, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-    return stats_from_table(scratch.host.numpy(), max_regions=max_regions, channels=channels, bins=bins, count=count, shape=(H, W),
+        raw = read_back(scratch.host, scratch.table)
+    return stats_from_table(raw, max_regions=max_regions, channels=channels, bins=bins, count=count, shape=(H, W),
                             scale=float(scale), is_float=raster.dtype == torch.float32, q_range=(q_lo, q_hi),
                             squeeze=raster.dim() == 2)

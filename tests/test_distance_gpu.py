@@ -300,7 +300,7 @@ def test_evaluate_with_and_without_the_boundary_score(dev):
     assert set(plain) == {"mask", "conf", "labels", "regions", "count", "mask_clean", "score", "gt_labels", "gt_regions", "gt_count"}
     score_keys = {"gt_match", "gt_iou", "pred_match", "pred_iou", "pred_area", "gt_area", "iou_threshold", "num_classes",
                   "confusion", "per_class", "overall", "ap", "ap_mean", "overlaps"}
-    assert set(plain["score"]) == score_keys and not pred._distance
+    assert set(plain["score"]) == score_keys and not pred._cached(iu.DistanceScratch)
     acc, total = iu.DetectionScore(2, 0.3), np.zeros((2, 3), dtype=np.int64)
     for scene, g in zip(scenes, truths):
         ev = pred.evaluate(scene, g, boundary_distance=3, **kw)
@@ -325,6 +325,6 @@ def test_evaluate_with_and_without_the_boundary_score(dev):
     np.testing.assert_allclose(got["iou"], iu.boundary_iou(total)["iou"], rtol=1e-12)
     one = iu.evaluate_scene(net, scenes[1], truths[1], tile=T, overlap=o, batch=4, num_classes=2, boundary_distance=3, **kw)
     assert (one["score"]["boundary"]["counts"] == want).all()
-    assert len(pred._distance) == 1
+    assert len(pred._cached(iu.DistanceScratch)) == 1
     pred.release()
-    assert not pred._distance
+    assert not pred._cached(iu.DistanceScratch)

@@ -349,6 +349,6 @@ def test_detect_is_predict_plus_label_regions(dev):
     for k in ("mask", "conf", "prob", "labels", "mask_clean"):
         assert torch.equal(det[k], one[k]), k
     assert one["count"] == det["count"] and all(one["regions"][k].tobytes() == v.tobytes() for k, v in det["regions"].items())
-    assert len(pred._regions) == 1
+    assert len(pred._cached(iu.regions.RegionScratch)) == 1
     pred.release()
-    assert not pred._regions and not pred._geom
+    assert not pred._cached(iu.regions.RegionScratch) and not pred._geom

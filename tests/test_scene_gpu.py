@@ -300,3 +300,61 @@ def test_refusals(dev, trained_unet):
     with pytest.raises(InsarError, match="ROCm"):
         iu.stitch_logits(lg.cpu(), origins, 600, 700, T, 32)
     assert trained_unet.training
+
+
+# ---- one scratch cache for every scene tool ---------------------------------------------------------------------------------
+class _SignNet(torch.nn.Module):
+    """Class 1 wherever the (normalised) scene is positive; one parameter, so that the predictor finds its device."""
+
+    def __init__(self):
+        super().__init__()
+        self.gain = torch.nn.Parameter(torch.tensor(4.0))
+
+    def forward(self, x):
+        return torch.cat([torch.zeros_like(x), self.gain * x], dim=1)
+
+
+def _same(a, b, what):
+    if isinstance(a, dict):
+        assert a.keys() == b.keys(), what
+        for k in a:
+            _same(a[k], b[k], f"{what}[{k!r}]")
+    elif isinstance(a, torch.Tensor):
+        assert _bitwise(a, b), what
+    elif isinstance(a, np.ndarray):
+        assert a.dtype == b.dtype and a.shape == b.shape, what
+        assert (a == b).all() if a.dtype == object else np.array_equal(a, b, equal_nan=a.dtype.kind == "f"), what
+    else:
+        assert a == b or (a != a and b != b), what
+
+
+def test_release_empties_the_one_scratch_cache(dev):
+    """A ragged 96 x 80 scene (tile 64, overlap 16: two tiles each way) through every tool detect and evaluate can chain.
+    `release()` used to forget the split, skeleton and outline scratch; scratch rebuilt after it gives the same tables."""
+    import insar_unet_ca_amd as iu
+    from insar_unet_ca_amd import regions, score
+    H, W = 96, 80
+    yy, xx = np.mgrid[:H, :W]
+    discs = [(30, 24, 13), (30, 46, 13), (70, 60, 9), (80, 12, 6)]           # the first two touch: one region, two pieces
+    inside = np.zeros((H, W), dtype=bool)
+    for cy, cx, r in discs:
+        inside |= (yy - cy) ** 2 + (xx - cx) ** 2 <= r * r
+    scene = np.where(inside, 1.0, -1.0).astype(np.float32)
+    gt = np.roll(inside, 2, axis=1).astype(np.uint8)
+    gt[:3] = 255
+    pred = iu.ScenePredictor(_SignNet().to(dev), tile=64, overlap=16, batch=3, num_classes=2)
+    kw = dict(outlines=True, simplify=1.0, skeletons=True, split=True, measure={"input": "input"})
+    first = pred.detect(scene, **kw)
+    assert first["count"] >= 4 and first["split_converged"] and (first["mask"].cpu().numpy() == inside).all()
+    ev = pred.evaluate(scene, gt, boundary_distance=2)
+    assert ev["score"]["overall"]["tp"] == 3 and ev["score"]["boundary"]["distance"] == 2
+    held = {cls for cls, _, _ in pred._cache}
+    assert held == {regions.RegionScratch, iu.SplitScratch, iu.OutlineScratch, iu.SkeletonScratch, iu.ZonalScratch,
+                    score.OverlapScratch, iu.DistanceScratch}
+    assert len(pred._cache) == len(held) and all(d == dev for _, _, d in pred._cache)
+    pred.release()
+    assert not pred._cache and not pred._geom and not pred._tiles
+    again = pred.detect(scene, **kw)
+    assert len(pred._cache) == 5
+    for k in ("labels", "regions", "count", "mask_clean", "outlines", "skeleton", "stats", "split_rounds"):
+        _same(first[k], again[k], k)

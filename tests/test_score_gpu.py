@@ -311,10 +311,10 @@ def test_evaluate_is_detect_plus_the_oracle_score(dev):
         assert_match_equal(other["score"], ref, "evaluate again")
         assert torch.equal(other["labels"], ev["labels"]) and torch.equal(other["gt_labels"], ev["gt_labels"])
         assert all(a.tobytes() == b.tobytes() for a, b in zip(other["score"]["overlaps"], ev["score"]["overlaps"]))
-    assert len(pred._regions) == 1 and len(pred._overlaps) == 1
+    assert len(pred._cached(iu.regions.RegionScratch)) == 1 and len(pred._cached(iu.score.OverlapScratch)) == 1
     acc = iu.DetectionScore(2, 0.3)
     acc.update(ev["score"])
     acc.update(ev2["score"])
     assert acc.compute()["overall"]["tp"] == 2 * s["tp"]
     pred.release()
-    assert not pred._regions and not pred._overlaps
+    assert not pred._cached(iu.regions.RegionScratch) and not pred._cached(iu.score.OverlapScratch)

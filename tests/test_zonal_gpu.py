@@ -356,7 +356,7 @@ def test_detect_with_measure(dev):
     pred = iu.ScenePredictor(net, tile=T, overlap=o, batch=4, num_classes=2)
     kw = dict(connectivity=8, min_area=3, min_conf=float(pred.predict(scene)["conf"].median()))
     plain = pred.detect(scene, **kw)
-    assert "stats" not in plain and not pred.__dict__.get("_zonal")
+    assert "stats" not in plain and not pred._cached(iu.ZonalScratch)
     hist_kw = dict(bins=8, range=(-2.0, 2.0), nodata=0.0)
     det = pred.detect(scene, measure={"scene": "input", "aux": aux, "aux_dev": (torch.from_numpy(aux).to(dev), hist_kw)}, **kw)
     assert set(det) == set(plain) | {"stats"} and det["count"] == plain["count"] > 1
@@ -386,6 +386,6 @@ def test_detect_with_measure(dev):
     ev = pred.evaluate(scene, gt, measure={"aux": aux}, **kw)
     assert ev["stats"]["aux"]["sum_q"].tobytes() == det["stats"]["aux"]["sum_q"].tobytes() and "score" in ev
     assert "stats" not in pred.evaluate(scene, gt, **kw)
-    assert len(pred.__dict__["_zonal"]) == 2
+    assert len(pred._cached(iu.ZonalScratch)) == 2
     pred.release()
-    assert "_zonal" not in pred.__dict__
+    assert not pred._cached(iu.ZonalScratch)
