@@ -56,7 +56,8 @@ const char* insar_last_error(void);
 
 /* Kernel-variant selectors for same-process A/B measurements (tools/, bench.py --tune): named integer knobs read by
  * the launchers at launch time. Every value of every knob selects between kernels that the parity tests hold to
- * the same tolerances; unknown names return INSAR_E_ARG. Not part of the reference's surface (it has no kernels). */
+ * the same tolerances (tests/test_switch_routes_gpu.py, test_switch_wgrad_gpu.py, test_wgrad3_exact_gpu.py), except
+ * wgrad3x_var, which only experiment builds read and the product library ignores; unknown names return INSAR_E_ARG. Not part of the reference's surface (it has no kernels). */
 int insar_tune_set(const char* name, int32_t value);
 int insar_tune_get(const char* name);   /* value, or INSAR_E_ARG */
 

@@ -1,7 +1,9 @@
 """The INSAR_* environment switches, seen from outside: which ones exist, their defaults, and which are set to something else.
 
 Every switch is read where it is used (`os.environ.get("INSAR_X", "default")` in engine.py, deeplab.py, optim.py, tape.py,
-_lib.py, bench.py); they select between launch paths the GPU tests show to be equal, for diagnostics and same-box A/B runs.
+_lib.py, bench.py); they select between launch paths the GPU tests show to be equal, for diagnostics and same-box A/B runs
+(tests/test_switch_coverage_host.py names the test behind each one; the exempt ones select no kernel: INSAR_HIP_LIB a path,
+INSAR_TUNE a list of knobs, INSAR_TAPE host replay, INSAR_SIDE_PRIORITY and INSAR_SIDE_CU_MASK scheduling hints).
 A stray variable on a box would change WHICH kernels a measurement runs without leaving a trace, so the bench line carries
 `switches` (this module's `non_default()`), and the default `bench.py` run refuses to measure with any of them set
 (`--allow-switches` overrides). The table is read off the package's own source, so a new switch cannot be forgotten here.

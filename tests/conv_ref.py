@@ -113,3 +113,36 @@ def assert_exact_in_bf16(*tensors):
 def assert_sums_exact_in_fp32(y):
     assert y.dtype == torch.int64
     assert int(y.abs().sum((0, 2, 3)).max()) < SUM_LIMIT and int((y * y).sum((0, 2, 3)).max()) < SUM_LIMIT
+
+
+# ---- the layers of tests/test_switch_routes_gpu.py ----------------------------------------------------------------------------------
+# (Cin, Cout, (B, H, W)). The GPU cases find their batches from the library's queries and the device's CU count and refuse a
+# shape that is not listed here (these are the ones of a 256-CU device); tests/test_conv_ref_host.py asserts the exactness
+# bounds of each.
+SWITCH_SEED = 4242
+SWITCH_ROUTE_LAYERS = [(64, 64, (3, 30, 30)), (128, 128, (2, 16, 32)), (64, 128, (4, 128, 128)), (128, 256, (4, 128, 128)),
+                       (256, 256, (2, 60, 72)), (64, 256, (4, 128, 130))]
+
+
+def consumer_sums(dx, yv, scale, shift):
+    """(sum dx * mask, sum dx * mask * yv) per channel, mask = [scale * yv + shift > 0] (InsarBstat, include/insar_hip.h): the
+    BatchNorm-backward sums a producer GEMM writes for the unit that consumes dx. Asserts the bound under which fp32 holds
+    every partial sum exactly."""
+    mask = (scale.reshape(1, -1, 1, 1) * yv + shift.reshape(1, -1, 1, 1) > 0).to(torch.int64)
+    assert bool(mask.any()) and not bool(mask.all())
+    t = dx * mask
+    assert int(t.abs().sum((0, 2, 3)).max()) < SUM_LIMIT and int((t * yv).abs().sum((0, 2, 3)).max()) < SUM_LIMIT
+    return t.sum((0, 2, 3)), (t * yv).sum((0, 2, 3))
+
+
+def switch_operands(device, cin, cout, shape):
+    """integer_operands with the consumer of dx: its raw conv output yv in {-1, 0, 1}, integer scale in {1, 2} and shift in
+    {-1, 0, 1}, and its exact sums (b1, b2)."""
+    B, H, W = shape
+    o = integer_operands(SWITCH_SEED, B, cin, cout, H, W, device=device)
+    gen = torch.Generator().manual_seed(SWITCH_SEED + 1)
+    o.yv = torch.randint(-1, 2, tuple(o.dx.shape), generator=gen, dtype=torch.int64).to(device)
+    o.cscale = torch.randint(1, 3, (cin,), generator=gen, dtype=torch.int64).to(device)
+    o.cshift = torch.randint(-1, 2, (cin,), generator=gen, dtype=torch.int64).to(device)
+    o.b1, o.b2 = consumer_sums(o.dx, o.yv, o.cscale, o.cshift)
+    return o

@@ -47,6 +47,49 @@ def mock_abi(monkeypatch, answers=None) -> list:
     return calls
 
 
+class LaunchLog(list):
+    """(entry point, its arguments, stream the call was issued on) in issue order, as record_calls collects them."""
+
+    def names(self):
+        return [n for n, _, _ in self]
+
+    def args(self, name):
+        return [a for n, a, _ in self if n == name]
+
+    def count(self, name):
+        return sum(1 for n, _, _ in self if n == name)
+
+    def streams(self, name):
+        return [s for n, _, s in self if n == name]
+
+
+def small_ints(args) -> tuple:
+    """The integer arguments of a call that are not addresses (flags, extents, nsplit, counts): what two runs with
+    different allocations must still agree on."""
+    return tuple(a for a in args if isinstance(a, int) and not isinstance(a, bool) and abs(a) < 2 ** 31)
+
+
+def record_calls(monkeypatch, modules=None) -> LaunchLog:
+    """Wrap the real C ABI `call` of the package's launching modules (all of them, or the ones given): every call is
+    logged with its arguments and torch's current stream handle, then made. Undone with the monkeypatch."""
+    import sys
+    from insar_unet_ca_amd import _lib
+    log, orig = LaunchLog(), _lib.call
+
+    def recording_call(name, *a):
+        log.append((name, a, _lib.stream_ptr()))
+        return orig(name, *a)
+
+    recording_call.wraps = orig
+    if modules is None:      # every module that launches: it holds the ABI's `call`, or an earlier recorder of this kind
+        modules = [m for k, m in list(sys.modules.items()) if k.startswith("insar_unet_ca_amd.") and m is not _lib
+                   and (getattr(m, "call", None) is orig or getattr(getattr(m, "call", None), "wraps", None) is orig)]
+    assert modules
+    for m in modules:
+        monkeypatch.setattr(m, "call", recording_call)
+    return log
+
+
 def to_np(t):
     if isinstance(t, torch.Tensor):
         return t.detach().double().cpu().numpy()

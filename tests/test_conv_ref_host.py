@@ -177,3 +177,18 @@ def test_pixel_left_out_of_the_statistics_is_rejected_exactly(ints, old_small, o
     assert min(figs[0]) > OLD_STAT_TOL
     assert figs[1][0] > OLD_STAT_TOL
     assert 0 < figs[1][1] <= OLD_STAT_TOL
+
+
+@pytest.mark.parametrize("layer", R.SWITCH_ROUTE_LAYERS, ids=lambda l: f"{l[0]}-{l[1]}-" + "x".join(map(str, l[2])))
+def test_switch_route_operands_are_exact_in_bf16_and_fp32(layer):
+    """The operands of tests/test_switch_routes_gpu.py at each of its shapes: |y|, |dx| <= 256 (bf16 holds them), the
+    per-channel sums of |y| and y^2 and the consumer's sums of |dx * mask| and |dx * mask * yv| below 2^24 (any fp32
+    summation order is exact). The generator asserts these; here the margins are printed and held."""
+    cin, cout, shape = layer
+    o = R.switch_operands("cpu", cin, cout, shape)
+    out = max(int(o.y.abs().max()), int(o.dx.abs().max()))
+    sums = max(int(o.y.abs().sum((0, 2, 3)).max()), int((o.y * o.y).sum((0, 2, 3)).max()))
+    mask = (o.cscale.reshape(1, -1, 1, 1) * o.yv + o.cshift.reshape(1, -1, 1, 1) > 0).to(torch.int64)
+    cons = max(int((o.dx * mask).abs().sum((0, 2, 3)).max()), int((o.dx * mask * o.yv).abs().sum((0, 2, 3)).max()))
+    print("%s: largest output %d (limit %d), largest per-channel sum %d, consumer sum %d (limit %d)" % (layer, out, R.OUT_LIMIT, sums, cons, R.SUM_LIMIT))
+    assert out <= R.OUT_LIMIT and sums < R.SUM_LIMIT and cons < R.SUM_LIMIT

@@ -256,3 +256,43 @@ def test_swapped_slices_are_rejected_exactly():
     print("two slices swapped: %d of %d slabs differ; present criterion max_rel = %.3e" % (differ, nsplit * 8, fig))
     assert rejected and differ == 2
     assert fig <= 1e-13 < OLD_TOL
+
+
+def _lid(l):
+    return f"{l[0]}-{l[1]}-" + "x".join(map(str, l[2]))
+
+
+@pytest.mark.parametrize("layer", G.SWITCH_LAYERS, ids=_lid)
+def test_switch_wgrad_operands_keep_every_partial_sum_exact(layer):
+    """The layers of tests/test_switch_wgrad_gpu.py with its seed: |x|, |g| <= 1 and B*H*W < 2^24, so every partial sum of
+    the products over ANY subset of the pixels (whatever nsplit and slab partition the engine picks) is an integer below
+    2^24 in magnitude, which fp32 holds; the largest element of the reference gradient is printed and held to the bound."""
+    cin, cout, (B, H, W) = layer
+    o = G.integer_operands(G.SWITCH_SEED, B, cin, cout, H, W)
+    big = int(o.dw.abs().max())
+    print("%s: largest |dw| %d, pixels %d (limit %d)" % (layer, big, B * H * W, R.SUM_LIMIT))
+    assert int(o.x.abs().max()) <= 1 and int(o.g.abs().max()) <= 1 and B * H * W < R.SUM_LIMIT and 0 < big < R.SUM_LIMIT
+
+
+@pytest.mark.parametrize("layer", G.UNIT_LAYERS, ids=_lid)
+def test_switch_unit_operands_and_reference(layer):
+    """The 1x1 and the dilated unit of the WGRAD_FILL_DL cases: the same bound, and conv_weight_grad against autograd of
+    torch.nn.functional.conv2d in float64 on a small grid of the same kind."""
+    cin, cout, (B, H, W), k, dil = layer
+    o = G.unit_operands(G.SWITCH_SEED, layer)
+    big = int(o.dw.abs().max())
+    print("%s: largest |dw| %d, pixels %d (limit %d)" % (layer, big, B * H * W, R.SUM_LIMIT))
+    assert int(o.x.abs().max()) <= 1 and int(o.g.abs().max()) <= 1 and B * H * W < R.SUM_LIMIT and 0 < big < R.SUM_LIMIT
+    gen = torch.Generator().manual_seed(3)
+    x = torch.randn((2, 5, 7, 9), generator=gen, dtype=torch.float64)
+    g = torch.randn((2, 4, 7, 9), generator=gen, dtype=torch.float64)
+    w = torch.zeros((4, 5, k, k), dtype=torch.float64, requires_grad=True)
+    F.conv2d(x, w, padding=dil * (k // 2), dilation=dil).backward(g)
+    assert max_rel(G.conv_weight_grad(x, g, k, dil), w.grad) <= 1e-13
+
+
+def test_switch_transposed_conv_operands_keep_every_partial_sum_exact():
+    """UpPlan's operands in the WGRAD_FILL_T cases (x in [-2, 2], dout in [-3, 3], one product per input pixel and tap for dW,
+    four output pixels per input pixel for dbias): every partial sum below 2^24."""
+    B, cin, h, w = G.UP_SHAPE
+    assert G.UP_X_MAX * G.UP_G_MAX * B * h * w < R.SUM_LIMIT and G.UP_G_MAX * 4 * B * h * w < R.SUM_LIMIT

@@ -77,6 +77,29 @@ def conv3x3_weight_grad(x, g):
     return dw.permute(1, 2, 0).reshape(co, ci, 3, 3).contiguous()
 
 
+def conv_weight_grad(x, g, k=3, dil=1):
+    """dw of a k x k (k in {1, 3}) / stride-1 convolution with dilation dil and padding dil*(k-1)/2 (the 1x1 and dilated units of
+    DeepLabV3-CA): dw[co, ci, ky, kx] = sum_{n, oy, ox} g[n, co, oy, ox] * x[n, ci, oy + (ky - k//2)*dil, ox + (kx - k//2)*dil],
+    zero outside x. x [B][Ci][H][W], g [B][Co][H][W] -> [Co][Ci][k][k]; int64 exactly (through float64, bounded below 2^53)."""
+    assert k in (1, 3) and dil >= 1
+    B, ci, H, W = x.shape
+    co = g.shape[1]
+    assert g.shape[0] == B and tuple(g.shape[2:]) == (H, W)
+    exact = x.dtype == torch.int64
+    if exact:
+        assert g.dtype == torch.int64 and float(x.abs().max()) * float(g.abs().max()) * B * H * W < 2.0 ** 53
+    p = dil * (k // 2)
+    xp = torch.zeros((B, H + 2 * p, W + 2 * p, ci), dtype=torch.float64, device=x.device)
+    xp[:, p:p + H, p:p + W] = x.permute(0, 2, 3, 1).double()
+    g_rows = g.permute(0, 2, 3, 1).reshape(B * H * W, co).double()
+    dw = torch.zeros((co, ci, k, k), dtype=torch.float64, device=x.device)
+    for ky in range(k):
+        for kx in range(k):
+            v = xp[:, ky * dil:ky * dil + H, kx * dil:kx * dil + W].reshape(B * H * W, ci)
+            dw[:, :, ky, kx] = g_rows.t() @ v
+    return dw.to(torch.int64) if exact else dw
+
+
 def num_steps(B, H, W, step_pixels=STEP):
     assert (B * H * W) % step_pixels == 0
     return B * H * W // step_pixels
@@ -121,6 +144,31 @@ def integer_operands(seed, B, cin, cout, H, W, device="cpu"):
     o = R.integer_operands(seed, B, cin, cout, H, W, device=device)
     assert int(o.x.abs().max()) <= 1 and int(o.g.abs().max()) <= 1
     return SimpleNamespace(x=o.x, g=o.g, dw=conv3x3_weight_grad(o.x, o.g))
+
+
+# ---- the layers of tests/test_switch_wgrad_gpu.py (tests/test_wgrad3_ref_host.py asserts the exactness bound of each) -----------
+SWITCH_SEED = 77
+LAYER_128 = (128, 128, (4, 64, 64))        # wgrad3<128, 128>; 3y with WGRAD_Y & 2; 3k with WGRAD_K
+LAYER_X = (256, 128, (4, 64, 64))          # wgrad3x<256, 128>; 3y with WGRAD_Y & 1; wgrad3 with WGRAD_X = 0
+LAYER_DEEP = (512, 512, (2, 64, 64))       # 48 tiles of 128 x 128: the default grid cap binds
+LAYER_ODD = (256, 256, (2, 8, 24))         # W = 24: no row-of-taps kernel, the per-tap kernel's 256 x 256 tile
+SWITCH_LAYERS = [LAYER_128, LAYER_X, LAYER_DEEP, LAYER_ODD]
+# (Cin, Cout, (B, H, W), k, dilation): the DeepLabV3-CA units of the WGRAD_FILL_DL cases
+UNIT_1X1 = (512, 256, (2, 64, 64), 1, 1)
+UNIT_DILATED = (128, 128, (2, 64, 64), 3, 2)
+UNIT_LAYERS = [UNIT_1X1, UNIT_DILATED]
+UP_SHAPE, UP_COUT = (4, 256, 32, 32), 256   # the transposed convolution of the WGRAD_FILL_T cases: x in [-2, 2], dout in [-3, 3]
+UP_X_MAX, UP_G_MAX = 2, 3
+
+
+def unit_operands(seed, layer, device="cpu"):
+    """x, g uniform in {-1, 0, 1} (drawn on the CPU generator) and dw = conv_weight_grad of a UNIT_* layer."""
+    cin, cout, (B, H, W), k, dil = layer
+    assert B * H * W < R.SUM_LIMIT
+    gen = torch.Generator().manual_seed(seed)
+    x = torch.randint(-1, 2, (B, cin, H, W), generator=gen, dtype=torch.int64).to(device)
+    g = torch.randint(-1, 2, (B, cout, H, W), generator=gen, dtype=torch.int64).to(device)
+    return SimpleNamespace(x=x, g=g, dw=conv_weight_grad(x, g, k, dil))
 
 
 # ---- address probes ---------------------------------------------------------------------------------------------------------
