@@ -681,6 +681,51 @@ int insar_split_finish(const int32_t* labels, const int32_t* height, const uint8
                        int32_t H, int32_t W, int32_t max_regions, int64_t max_pairs, int32_t max_rounds, void* scratch, void* table,
                        int32_t* labels_out, void* stream);
 
+/* ---- sieving class maps (build-side addition; the reference has no post-processing): csrc/sieve.hip ------------------------
+ * Regions of a class map below a per-class area threshold are absorbed by their largest neighbour, whatever its class. The
+ * input regions are the connected components over ALL classes: the caller runs the insar_regions_* phases (min_area 1, no
+ * conf) on the remapped map that insar_sieve_remap leaves at offset 0 of the scratch, which gives the label map (ids 1..N by
+ * ascending smallest pixel index; void pixels 0) and the InsarRegion table (area, root).
+ *   adjacency: every horizontally or vertically adjacent pixel pair whose labels a != b are both in 1..max_label counts once
+ *              under (min(a, b), max(a, b)): the number of pixel edges two regions share. Always 4-adjacency.
+ *   rounds:    pieces start as the regions; id, class = those of the root region, area = the sum over the members,
+ *              key(u) = (area[u], -id[u]). Per synchronous round every piece u with area[u] < thresholds[cls[u]] and a
+ *              neighbouring piece takes best(u), the neighbouring piece with the greatest key, and merges into it unless
+ *              best(best(u)) == u and key(u) > key(best(u)); pointers are compressed, areas added into the roots.
+ *   output:    out[p] = cls[root[label[p]]] for labelled pixels, mask[p] elsewhere.
+ * Integers only: bitwise reproducible. One call per phase on one stream; no work-group waits on another. Every argument is
+ * checked before the device is touched. 1 <= max_regions <= 2^30, 1 <= max_pairs <= 2^24, 1 <= max_rounds <= 4096.
+ *   scratch: insar_sieve_scratch_bytes(...) bytes, 16-byte aligned: the remapped map uint8 [H*W] at offset 0, the control
+ *            words, int32 root / next / area / class [1 + max_regions] (the roots directly behind the control words), uint64
+ *            best word [1 + max_regions], the pair list (a 16-byte header {int32 n_pairs, overflow, 0, 0} at `pairs_offset`,
+ *            then max_pairs records {int32 a, int32 b, int64 edges}) and the pair table (2^k >= 2 max_pairs slots of 16
+ *            bytes). Nothing in it has to survive between calls or be cleared by the caller. n_pairs is the TRUE number of
+ *            pairs, which may exceed max_pairs; overflow is non-zero iff the pair table overflowed. The control words are
+ *            int32 [8 + max_rounds] at `ctrl_offset`: 0 / 1 the header's n_pairs / overflow and 2 the TRUE number of regions
+ *            N (after the first rounds call), 3 pixels of class 255 where there is no void value (they have no code left in the
+ *            remapped map; the result is then meaningless), 4 changed pixels and 5 absorbed regions (after apply), 8 + r
+ *            the merges of round r. */
+/* host only: bytes of the scratch and where the control words and the pair list lie in it. */
+int insar_sieve_scratch_bytes(int32_t H, int32_t W, int32_t max_regions, int64_t max_pairs, int32_t max_rounds,
+                              int64_t* scratch_bytes, int64_t* ctrl_offset, int64_t* ctrl_bytes, int64_t* pairs_offset);
+/* 1 launch (2 with void_value -1): the remapped map (class c -> c + 1 below void_value or without one, c above it, void -> 0)
+ * and zeroed control words. mask uint8 [H][W]; void_value -1 (none) or 0..255. */
+int insar_sieve_remap(const uint8_t* mask, int32_t H, int32_t W, int32_t void_value, int32_t max_regions, int64_t max_pairs,
+                      int32_t max_rounds, void* scratch, void* stream);
+/* 3 launches: clear, pairs (the adjacency table of labels int32 [H][W]; labels <= 0 or > max_label are no region), compact
+ * (the pair list and its header). Stands alone: it needs nothing of the other phases. */
+int insar_sieve_pairs(const int32_t* labels, int32_t H, int32_t W, int32_t max_label, int32_t max_regions, int64_t max_pairs,
+                      int32_t max_rounds, void* scratch, void* stream);
+/* 3 launches per round (best neighbour, decide, compress), over the pair list and the region table only, plus 1 (the piece
+ * state of every region from `table`, an InsarRegion table, and the classes mask[root]) when first_round is 0: rounds
+ * first_round .. first_round + n_rounds - 1 <= max_rounds - 1. A round after the fixed point changes nothing. thresholds:
+ * int32 [256] in device memory; 0: regions of that class are never absorbed. */
+int insar_sieve_rounds(const void* table, const uint8_t* mask, const int32_t* thresholds, int32_t H, int32_t W, int32_t first_round,
+                       int32_t n_rounds, int32_t max_regions, int64_t max_pairs, int32_t max_rounds, void* scratch, void* stream);
+/* 1 launch: out uint8 [H][W], changed uint8 [H][W] (nullable; 1 where out != mask), control words 4 and 5. */
+int insar_sieve_apply(const int32_t* labels, const uint8_t* mask, int32_t H, int32_t W, int32_t max_regions, int64_t max_pairs,
+                      int32_t max_rounds, void* scratch, uint8_t* out, uint8_t* changed /*nullable*/, void* stream);
+
 /* ---- region outlines (build-side addition; the reference has no post-processing): csrc/outline.hip ------------------------
  * The exact pixel-edge ("crack") outline of every region of a label map `labels` int32 [H][W] (row-major; 0 or an id >= 1, as
  * insar_regions_relabel writes it, but any int32 map is legal; H, W >= 1, H * W < 2^29), as ordered, closed rings of lattice

@@ -24,6 +24,7 @@ from .split import SplitScratch, split_regions  # noqa: F401
 from .rasterise import PolygonTable, RasterScratch, from_geojson, labels_from_geojson, pack_polygons, rasterise_polygons  # noqa: F401
 from .warp import WarpSpec, draw_warps, gather_warped, grid_matrix, multilook, warp_raster  # noqa: F401
 from .stack import DetectionStack, StackScratch, follow_sites, site_series  # noqa: F401
+from .sieve import SieveScratch, region_adjacency, sieve_regions  # noqa: F401
 
 __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "ChannelAttentionModule", "MaxPool2d", "CrossEntropyLoss", "DiceLoss", "DiceCELoss", "Adam", "GraphedTrainStep",
            "compute_metrics", "train_model", "validate_model", "save_history", "VOCSegDataset", "SyntheticTiles",
@@ -40,4 +41,5 @@ __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "Cha
            "PolygonTable", "RasterScratch", "pack_polygons", "from_geojson", "rasterise_polygons", "labels_from_geojson",
            "ZonalScratch", "region_stats", "percentile", "SplitScratch", "split_regions",
            "warp_raster", "grid_matrix", "multilook", "WarpSpec", "draw_warps", "gather_warped",
-           "DetectionStack", "StackScratch", "site_series", "follow_sites"]
+           "DetectionStack", "StackScratch", "site_series", "follow_sites",
+           "SieveScratch", "region_adjacency", "sieve_regions"]

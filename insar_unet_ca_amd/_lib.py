@@ -226,6 +226,11 @@ _SIGNATURES = {
     "insar_split_basins": [_P, _P, _I, _I, _L, _I, _P, _P],
     "insar_split_rounds": [_P, _I, _I, _I, _I, _I, _I, _L, _I, _P, _P],
     "insar_split_finish": [_P, _P, _P, _P, _I, _I, _I, _L, _I, _P, _P, _P, _P],
+    "insar_sieve_scratch_bytes": [_I, _I, _I, _L, _I, _P, _P, _P, _P],
+    "insar_sieve_remap": [_P, _I, _I, _I, _I, _L, _I, _P, _P],
+    "insar_sieve_pairs": [_P, _I, _I, _I, _I, _L, _I, _P, _P],
+    "insar_sieve_rounds": [_P, _P, _P, _I, _I, _I, _I, _I, _L, _I, _P, _P],
+    "insar_sieve_apply": [_P, _P, _I, _I, _I, _L, _I, _P, _P, _P, _P],
     "insar_outline_scratch_bytes": [_I, _I, _I, _I, _P, _P],
     "insar_outline_launches": [_I],
     "insar_outline_edges": [_P, _I, _I, _I, _I, _P, _P, _P],

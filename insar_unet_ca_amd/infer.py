@@ -294,7 +294,7 @@ class ScenePredictor:
 
     def detect(self, scene, return_prob: bool = False, outlines: bool = False, skeletons: bool = False,
                max_iterations: int = 32, measure: Optional[dict] = None, simplify: Optional[float] = None, split=None,
-               **region_kwargs) -> dict:
+               sieve=None, **region_kwargs) -> dict:
         """`predict(scene)` followed by `label_regions(out["mask"], out["conf"], **region_kwargs)`: the predict outputs
         unchanged, plus "labels", "regions", "count" and the cleaned class map under "mask_clean". With `outlines=True` also
         "outlines" = `outlines.region_outlines(out["labels"])` with the connectivity the regions were labelled with, and
@@ -311,13 +311,20 @@ class ScenePredictor:
         dict of `split.split_regions` keywords, the regions are cut along the necks of their distance map right after
         `label_regions`: the pieces replace "labels", "regions" and "count" (the table gains parent, peak, peak_y, peak_x and
         saddle), "split_rounds" and "split_converged" are added, "mask_clean" is unchanged, and outlines, skeletons and
-        `measure` run on the pieces. With None nothing of it runs."""
+        `measure` run on the pieces. With None nothing of it runs. With `sieve` = an int, a {class: int} dict or a sequence
+        (`min_area` of `sieve.sieve_regions`), or a dict of its keywords (`connectivity` and `max_regions` default to
+        detect's own), the predicted class map is sieved right after `predict`: small regions are absorbed by their largest
+        neighbour and small holes fill, `label_regions` and everything after it run on the cleaned map, "mask" stays the raw
+        prediction, and "mask_sieved", "sieve_changed_pixels", "sieve_absorbed", "sieve_rounds" and "sieve_converged" are
+        added. "conf" is not rewritten: a filled pixel carries the confidence of the class it had. With None nothing of it
+        runs."""
         if measure is not None and not isinstance(measure, dict):
             raise InsarError(f"measure: a dict of name -> raster or (raster, kwargs), got {type(measure).__name__}")
         out = dict(self.predict(scene, return_prob=return_prob))
         H, W = out["mask"].shape
         max_regions = region_kwargs.get("max_regions", DEFAULT_MAX_REGIONS)
-        reg = label_regions(out["mask"], out["conf"], scratch=self._scratch(RegionScratch, out["mask"].device, H, W, max_regions),
+        class_map = out["mask"] if sieve is None else self._sieve(out, sieve, region_kwargs.get("connectivity", 8), max_regions)
+        reg = label_regions(class_map, out["conf"], scratch=self._scratch(RegionScratch, out["mask"].device, H, W, max_regions),
                             **region_kwargs)
         out.update(labels=reg["labels"], regions=reg["regions"], count=reg["count"], mask_clean=reg["mask"])
         if split is not None and split is not False:
@@ -331,6 +338,33 @@ class ScenePredictor:
         if measure is not None:
             self._measure(out, scene, measure, max_regions)
         return out
+
+    def _sieve(self, out: dict, sieve, connectivity: int, max_regions: int) -> torch.Tensor:
+        """The sieved class map of out["mask"]; the sieve's figures go into `out`."""
+        from .sieve import DEFAULT_MAX_PAIRS, SieveScratch, sieve_regions
+        if isinstance(sieve, dict) and any(isinstance(k, str) for k in sieve):
+            kw = dict(sieve)
+            if "min_area" not in kw:
+                raise InsarError("sieve: a dict of sieve_regions keywords needs 'min_area'")
+        elif isinstance(sieve, (dict, list, tuple, np.ndarray, int, float, np.integer, np.floating)) and not isinstance(sieve, bool):
+            kw = {"min_area": sieve}
+        else:
+            raise InsarError(f"sieve: an int, a {{class: int}} dict or a sequence (min_area), or a dict of sieve_regions keywords, "
+                             f"got {sieve!r}")
+        for name in ("mask", "scratch"):
+            if name in kw:
+                raise InsarError(f"sieve: {name!r} is detect's to give")
+        kw.setdefault("connectivity", connectivity)
+        kw.setdefault("max_regions", max_regions)
+        H, W = out["mask"].shape
+        scratch = self._scratch(SieveScratch, out["mask"].device, H, W, kw["max_regions"], kw.get("max_pairs", DEFAULT_MAX_PAIRS),
+                                kw.get("max_rounds", 64))
+        sv = sieve_regions(out["mask"], scratch=scratch, **kw)
+        out.update(mask_sieved=sv["mask"], sieve_changed_pixels=sv["changed_pixels"], sieve_absorbed=sv["absorbed"],
+                   sieve_rounds=sv["rounds"], sieve_converged=sv["converged"])
+        if "changed" in sv:
+            out["sieve_changed"] = sv["changed"]
+        return sv["mask"]
 
     def _split(self, out: dict, split, max_regions: int) -> None:
         from .split import DEFAULT_MAX_PAIRS, SplitScratch, split_regions
@@ -394,15 +428,15 @@ class ScenePredictor:
         out["regions"]["perimeter"] = perimeters(out["outlines"]["rings"], out["regions"]["id"])
 
     def evaluate(self, scene, gt_mask, *, iou_threshold: float = 0.5, gt_min_area: int = 1, max_pairs: int = DEFAULT_MAX_PAIRS,
-                 boundary_distance: Optional[int] = None, measure: Optional[dict] = None, **region_kwargs) -> dict:
+                 boundary_distance: Optional[int] = None, measure: Optional[dict] = None, sieve=None, **region_kwargs) -> dict:
         """`detect(scene, **region_kwargs)`, then `label_regions` of the ground-truth class map (`gt_mask` uint8 [H, W], numpy
         or tensor, copied to the device once; 255 = ignore, labelled as background) with the same connectivity and
         `min_area=gt_min_area`, then `score.match_regions` with `void=gt_mask, void_value=255`: the detect outputs unchanged,
         plus "score" (the match result), "gt_labels", "gt_regions" and "gt_count". With `boundary_distance` = d (an integer
         >= 0) the score gains "boundary" = {"distance", "counts", "iou", "mean_iou"}: `distance.boundary_counts` of
         "mask_clean" against `gt_mask` (void 255) at d pixels, and `boundary_iou` of them; with None nothing of it runs.
-        `measure` goes to `detect`."""
-        out = self.detect(scene, measure=measure, **region_kwargs)
+        `measure` and `sieve` go to `detect`: the sieve cleans the prediction only, never the ground truth."""
+        out = self.detect(scene, measure=measure, sieve=sieve, **region_kwargs)
         dev = out["mask"].device
         H, W = out["mask"].shape
         gt = torch.from_numpy(np.ascontiguousarray(gt_mask)) if isinstance(gt_mask, np.ndarray) else gt_mask
@@ -478,7 +512,7 @@ def predict_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw
 
 def detect_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw) -> dict:
     """One-shot ScenePredictor(model, ...).detect(scene, return_prob, ...): tile / overlap / batch / num_classes / tta go to
-    the predictor, `outlines`, `simplify`, `skeletons`, `max_iterations`, `measure` and `split` to `detect`, every other keyword to
+    the predictor, `outlines`, `simplify`, `skeletons`, `max_iterations`, `measure`, `split` and `sieve` to `detect`, every other keyword to
     `label_regions`."""
     pred_kw = {k: kw.pop(k) for k in ("tile", "overlap", "batch", "num_classes", "tta") if k in kw}
     return ScenePredictor(model, **pred_kw).detect(scene, return_prob=return_prob, **kw)
