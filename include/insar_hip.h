@@ -587,6 +587,33 @@ int insar_scene_blend(const float* logits, const int32_t* origins, int32_t n, in
 int insar_scene_finalize(const float* acc, const float* wsum, int32_t K, int32_t H, int32_t W, float* prob /*nullable*/,
                          uint8_t* mask, float* conf, void* stream);
 
+/* ---- scenes with no-data: csrc/scene_valid.hip ------------------------------------------------------------------------------
+ * A pixel of the scene is VALID iff its byte of the plane `valid` (uint8 [H][W], nullable: every pixel counts as observed) is
+ * non-zero, its value is not `nodata` (looked at only with has_nodata != 0; an exact compare, of the byte for a uint8 scene,
+ * where nodata must be an integer in 0 .. 255, of the float for a float32 one) and, in a float32 scene, it is finite: NaN and
+ * +-inf are never valid, so a NaN `nodata` means "the non-finite pixels only". All three validate before they launch; the
+ * scene and the plane are read at any alignment. */
+/* counts [n] int32 <- the number of valid pixels of each T x T tile of the table `origins` (T a multiple of 16, at most 32768).
+ * One work-group per tile, one plain store per tile, no atomics; an entry that is not inside the scene counts 0. 1 launch. */
+int insar_scene_census(const void* scene, int32_t dtype /*INSAR_SCENE_**/, int32_t H, int32_t W, const uint8_t* valid /*nullable*/,
+                       int32_t has_nodata, float nodata, const int32_t* origins, int32_t n, int32_t T, int32_t* counts /*[n]*/,
+                       void* stream);
+/* insar_scene_gather with the invalid pixels replaced: out [n][1][T][T] fp32 (16-byte aligned). A valid pixel of a uint8
+ * scene gets insar_scene_gather's transform (has_norm must be 0), one of a float32 scene x = (v - offset) * scale with
+ * has_norm != 0 (a subtraction, then a multiplication, in fp32: two roundings; offset finite, scale finite and not 0), else v.
+ * An invalid pixel gives `fill` (finite), whatever its value: no arithmetic is done on it. With valid = null, has_nodata = 0
+ * and has_norm = 0 the output equals insar_scene_gather's bit for bit on a scene of finite values. 1 launch. */
+int insar_scene_gather_valid(const void* scene, int32_t dtype, int32_t H, int32_t W, const uint8_t* valid /*nullable*/,
+                             int32_t has_nodata, float nodata, float fill, int32_t has_norm, float offset, float scale,
+                             const int32_t* origins, int32_t n, int32_t T, float* out /*[n][1][T][T]*/, void* stream);
+/* insar_scene_finalize with a per-pixel mask: at a pixel that is valid (the rule above, evaluated again from `scene` and
+ * `valid`) and covered (wsum > 0) prob, mask and conf are insar_scene_finalize's, bit for bit, and valid_out [H][W] uint8 is 1;
+ * at every other pixel prob = 0, mask = 0, conf = 0 and valid_out = 0, by a select: a NaN in acc does not get through and
+ * nothing is divided by a wsum of 0. 1 launch. */
+int insar_scene_finalize_valid(const float* acc, const float* wsum, int32_t K, int32_t H, int32_t W, const void* scene,
+                               int32_t dtype, const uint8_t* valid /*nullable*/, int32_t has_nodata, float nodata,
+                               float* prob /*nullable*/, uint8_t* mask, float* conf, uint8_t* valid_out, void* stream);
+
 /* ---- regions of a class map (build-side addition; the reference has no post-processing): csrc/regions.hip --------------
  * Connected regions of a class map `mask` uint8 [H][W] (row-major, H * W < 2^31, no tile-multiple requirement). A pixel is
  * foreground if mask != 0 and, when `conf` fp32 [H][W] is given, conf >= min_conf; two foreground pixels are connected if

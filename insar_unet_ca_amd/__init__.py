@@ -10,7 +10,8 @@ from .spatial import SpatialAttention, UNet as UNetSpatialAttention  # noqa: F40
 from .optim import Adam, AdamW, LRSchedule, split_decay_groups  # noqa: F401
 from .graph import GraphedTrainStep  # noqa: F401
 from .train import compute_metrics, save_history, train_model, validate_model  # noqa: F401
-from .infer import ScenePredictor, detect_scene, evaluate_scene, gather_tiles, plan_tiles, predict_scene, stitch_logits, window_1d  # noqa: F401
+from .infer import (ScenePredictor, detect_scene, evaluate_scene, gather_tiles, plan_tiles, predict_scene, select_tiles,  # noqa: F401
+                    stitch_logits, tile_census, window_1d)
 from .regions import label_regions  # noqa: F401
 from .score import DetectionScore, match_from_overlaps, match_regions, region_overlaps  # noqa: F401
 from .augment import Augment  # noqa: F401
@@ -30,7 +31,7 @@ __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "Cha
            "compute_metrics", "train_model", "validate_model", "save_history", "VOCSegDataset", "SyntheticTiles",
            "ShardedSampler", "DevicePrefetcher", "make_loader", "reference_transforms", "InsarError", "LIB_PATH",
            "SpatialAttention", "UNetSpatialAttention", "FCN_SingleChannel", "FCN_SingleChannel_SE",
-           "ScenePredictor", "predict_scene", "stitch_logits", "plan_tiles", "window_1d", "gather_tiles",
+           "ScenePredictor", "predict_scene", "stitch_logits", "plan_tiles", "window_1d", "gather_tiles", "tile_census", "select_tiles",
            "FocalLoss", "class_weights", "label_histogram", "label_regions", "detect_scene", "Augment",
            "AdamW", "LRSchedule", "split_decay_groups",
            "region_overlaps", "match_regions", "match_from_overlaps", "DetectionScore", "evaluate_scene",

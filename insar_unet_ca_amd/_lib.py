@@ -216,6 +216,9 @@ _SIGNATURES = {
     "insar_scene_gather": [_P, _I, _I, _I, _P, _I, _I, _P, _P],
     "insar_scene_blend": [_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "insar_scene_finalize": [_P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "insar_scene_census": [_P, _I, _I, _I, _P, _I, _F, _P, _I, _I, _P, _P],
+    "insar_scene_gather_valid": [_P, _I, _I, _I, _P, _I, _F, _F, _I, _F, _F, _P, _I, _I, _P, _P],
+    "insar_scene_finalize_valid": [_P, _P, _I, _I, _I, _P, _I, _P, _I, _F, _P, _P, _P, _P, _P],
     "insar_regions_scratch_bytes": [_I, _I, _I, _P, _P],
     "insar_regions_tiles": [_P, _P, _F, _I, _I, _I, _P, _P],
     "insar_regions_merge": [_P, _I, _I, _I, _P, _P],

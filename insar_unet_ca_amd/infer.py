@@ -10,6 +10,10 @@ The stitch is bitwise reproducible and independent of the batch size: a pixel's 
 index (row-major over the tile grid) by the thread that owns the pixel; no atomics. The nets' own forward is NOT promised
 bitwise equal across batch sizes (kernel selection depends on the GEMM's M), so `predict` as a whole is reproducible for a
 fixed `batch`, and `stitch_logits` for any `chunk`.
+
+Scenes with no-data (`predict(valid=, nodata=, ...)`, csrc/scene_valid.hip: insar_scene_census / _gather_valid /
+_finalize_valid): the valid pixels of every planned tile are counted on the device, only the tiles that hold enough of them are
+run, invalid pixels enter the net as a fill value and leave with mask = conf = prob = 0 (DESIGN.md "Scenes with no-data").
 """
 from __future__ import annotations
 
@@ -18,7 +22,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _scene
 from ._lib import InsarError, call, ptr
 from .augment import D4_INVERSE, apply_table, check_tta, constant_table
 from .distance import DistanceScratch, boundary_counts, boundary_iou
@@ -98,22 +102,112 @@ def _as_scene(scene, device: torch.device) -> torch.Tensor:
     return scene.detach().to(device).contiguous()
 
 
-def gather_tiles(scene: torch.Tensor, origins_dev: torch.Tensor, tile: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """float32 [n, 1, tile, tile] <- the tiles of a device scene [H, W] at the int32 device table `origins_dev` [n, 2]
-    (every tile inside the scene). uint8 scenes are normalised like `data.reference_transforms`, float32 ones copied."""
-    if not scene.is_cuda or not origins_dev.is_cuda:
-        raise InsarError("gather_tiles: scene and origins must be ROCm tensors (no CPU fallback)")
+def _is_number(v) -> bool:
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+
+
+def _check_validity(who: str, H: int, W: int, is_u8: bool, tile: int, valid, nodata, min_valid, fill, norm):
+    """The refusals of the no-data arguments, by name and before anything is copied to a device. Returns
+    (valid as a uint8 [H, W] tensor wherever it lives, or None; nodata as a float, or None; min_valid; fill;
+    (offset, scale) as floats, or None)."""
+    if valid is not None:
+        if isinstance(valid, np.ndarray):
+            if valid.dtype != np.uint8 or valid.shape != (H, W):
+                raise InsarError(f"{who}: valid must be a uint8 [{H}, {W}] numpy array or tensor, got {valid.dtype} {valid.shape}")
+            valid = torch.from_numpy(np.ascontiguousarray(valid))
+        _scene.check_map(who, "valid", valid, (torch.uint8,), shape=(H, W), of="the scene")
+        valid = valid.detach()
+    if nodata is not None:
+        if is_u8:
+            nodata = float(_scene.check_int(who, "nodata", nodata, 0, 255, integral_floats=True,
+                                            expect="an integer in 0..255 for a uint8 scene"))
+        elif not _is_number(nodata):
+            raise InsarError(f"{who}: nodata={nodata!r}: a float for a float32 scene (nan: the non-finite pixels only)")
+        else:
+            nodata = float(nodata)
+    min_valid = _scene.check_int(who, "min_valid", min_valid, 1, tile * tile, integral_floats=False)
+    if not _is_number(fill) or not np.isfinite(fill):
+        raise InsarError(f"{who}: fill={fill!r}: a finite float, the network input of an invalid pixel")
+    if norm is not None:
+        if is_u8:
+            raise InsarError(f"{who}: norm is for float32 scenes: a uint8 scene gets the reference's transform")
+        if not isinstance(norm, (tuple, list)) or len(norm) != 2 or not all(_is_number(v) for v in norm):
+            raise InsarError(f"{who}: norm={norm!r}: a pair (offset, scale) of numbers")
+        offset, scale = float(norm[0]), float(norm[1])
+        if not np.isfinite(offset):
+            raise InsarError(f"{who}: norm: offset={offset!r} is not finite")
+        if not np.isfinite(scale) or scale == 0.0:
+            raise InsarError(f"{who}: norm: scale={scale!r}: finite and not zero")
+        norm = (offset, scale)
+    return valid, nodata, min_valid, float(fill), norm
+
+
+def _check_scene_args(who: str, scene, origins_dev, valid) -> None:
+    if not isinstance(scene, torch.Tensor) or not isinstance(origins_dev, torch.Tensor) or not scene.is_cuda or not origins_dev.is_cuda:
+        raise InsarError(f"{who}: scene and origins must be ROCm tensors (no CPU fallback)")
     if scene.dim() != 2 or scene.dtype not in (torch.uint8, torch.float32) or not scene.is_contiguous():
-        raise InsarError("gather_tiles: scene must be a contiguous 2-D uint8 or float32 tensor")
+        raise InsarError(f"{who}: scene must be a contiguous 2-D uint8 or float32 tensor")
     if origins_dev.dtype != torch.int32 or origins_dev.dim() != 2 or origins_dev.shape[1] != 2 or not origins_dev.is_contiguous():
-        raise InsarError("gather_tiles: origins must be a contiguous int32 [n, 2] tensor")
+        raise InsarError(f"{who}: origins must be a contiguous int32 [n, 2] tensor")
+    if valid is not None:
+        _scene.check_map(who, "valid", valid, (torch.uint8,), shape=tuple(scene.shape), of="the scene")
+        _scene.check_on_device(who, "valid", valid, like=scene)
+
+
+def _scene_code(scene: torch.Tensor) -> int:
+    return _lib.SCENE_U8 if scene.dtype == torch.uint8 else _lib.SCENE_F32
+
+
+def gather_tiles(scene: torch.Tensor, origins_dev: torch.Tensor, tile: int, out: Optional[torch.Tensor] = None, *, valid=None,
+                 nodata=None, fill: float = 0.0, norm=None) -> torch.Tensor:
+    """float32 [n, 1, tile, tile] <- the tiles of a device scene [H, W] at the int32 device table `origins_dev` [n, 2]
+    (every tile inside the scene). uint8 scenes are normalised like `data.reference_transforms`, float32 ones copied, or
+    taken through x = (v - offset) * scale with `norm` = (offset, scale). With `valid` (a uint8 [H, W] device map, 0 = not
+    observed) or `nodata` every invalid pixel (see `ScenePredictor.predict`) comes out as `fill`. With all four at their
+    defaults this is insar_scene_gather; otherwise insar_scene_gather_valid."""
+    _check_scene_args("gather_tiles", scene, origins_dev, valid)
+    plain = valid is None and nodata is None and norm is None and type(fill) is float and fill == 0.0
+    if not plain:
+        _, nodata, _, fill, norm = _check_validity("gather_tiles", scene.shape[0], scene.shape[1], scene.dtype == torch.uint8, tile,
+                                                   valid, nodata, 1, fill, norm)
+        plain = valid is None and nodata is None and norm is None and fill == 0.0
     n = origins_dev.shape[0]
     if out is None:
         out = torch.empty(n, 1, tile, tile, dtype=torch.float32, device=scene.device)
-    code = _lib.SCENE_U8 if scene.dtype == torch.uint8 else _lib.SCENE_F32
-    call("insar_scene_gather", ptr(scene), code, scene.shape[0], scene.shape[1], ptr(origins_dev), n, tile, ptr(out),
-         _lib.stream_ptr())
+    if plain:
+        call("insar_scene_gather", ptr(scene), _scene_code(scene), scene.shape[0], scene.shape[1], ptr(origins_dev), n, tile,
+             ptr(out), _lib.stream_ptr())
+    else:
+        offset, scale = norm if norm is not None else (0.0, 1.0)
+        call("insar_scene_gather_valid", ptr(scene), _scene_code(scene), scene.shape[0], scene.shape[1], ptr(valid),
+             int(nodata is not None), 0.0 if nodata is None else nodata, fill, int(norm is not None), offset, scale,
+             ptr(origins_dev), n, tile, ptr(out), _lib.stream_ptr())
     return out
+
+
+def tile_census(scene: torch.Tensor, origins_dev: torch.Tensor, tile: int, *, valid=None, nodata=None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 [n] on the device <- the number of valid pixels (see `ScenePredictor.predict`) of each tile of a device scene
+    [H, W] at the int32 device table `origins_dev` [n, 2]. One launch (insar_scene_census), nothing read back."""
+    _check_scene_args("tile_census", scene, origins_dev, valid)
+    _, nodata, _, _, _ = _check_validity("tile_census", scene.shape[0], scene.shape[1], scene.dtype == torch.uint8, tile, valid, nodata,
+                                         1, 0.0, None)
+    n = origins_dev.shape[0]
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=scene.device)
+    call("insar_scene_census", ptr(scene), _scene_code(scene), scene.shape[0], scene.shape[1], ptr(valid), int(nodata is not None),
+         0.0 if nodata is None else nodata, ptr(origins_dev), n, tile, ptr(out), _lib.stream_ptr())
+    return out
+
+
+def select_tiles(counts, min_valid: int = 1) -> np.ndarray:
+    """The indices, ascending, of the tiles whose census is at least `min_valid`: the tiles that are run. Host arithmetic
+    only."""
+    c = np.asarray(counts)
+    if c.ndim != 1 or not np.issubdtype(c.dtype, np.integer):
+        raise InsarError(f"select_tiles: counts must be a 1-D integer array, got {c.dtype} {c.shape}")
+    min_valid = _scene.check_int("select_tiles", "min_valid", min_valid, 1, integral_floats=False)
+    return np.flatnonzero(c >= min_valid)
 
 
 def _blend(logits: torch.Tensor, origins: np.ndarray, origins_dev: torch.Tensor, first: int, K: int, tile: int, overlap: int,
@@ -138,6 +232,20 @@ def _finalize(acc: torch.Tensor, wsum: torch.Tensor, return_prob: bool) -> Dict[
     if return_prob:
         out["prob"] = torch.empty(K, H, W, dtype=torch.float32, device=dev)
     call("insar_scene_finalize", ptr(acc), ptr(wsum), K, H, W, ptr(out.get("prob")), ptr(out["mask"]), ptr(out["conf"]),
+         _lib.stream_ptr())
+    return out
+
+
+def _finalize_valid(acc: torch.Tensor, wsum: torch.Tensor, return_prob: bool, scene: torch.Tensor, valid, nodata) -> Dict[str, torch.Tensor]:
+    """`_finalize` with prob = mask = conf = 0 at the pixels that are invalid or that no tile covered, and "valid"."""
+    K, H, W = acc.shape
+    dev = acc.device
+    out = {"mask": torch.empty(H, W, dtype=torch.uint8, device=dev), "conf": torch.empty(H, W, dtype=torch.float32, device=dev),
+           "valid": torch.empty(H, W, dtype=torch.uint8, device=dev)}
+    if return_prob:
+        out["prob"] = torch.empty(K, H, W, dtype=torch.float32, device=dev)
+    call("insar_scene_finalize_valid", ptr(acc), ptr(wsum), K, H, W, ptr(scene), _scene_code(scene), ptr(valid), int(nodata is not None),
+         0.0 if nodata is None else nodata, ptr(out.get("prob")), ptr(out["mask"]), ptr(out["conf"]), ptr(out["valid"]),
          _lib.stream_ptr())
     return out
 
@@ -209,6 +317,7 @@ class ScenePredictor:
         self._geom: dict = {}            # (H, W, device) -> (origins, origins_dev, buf, acc, wsum)
         self._tiles: dict = {}           # device -> float32 [batch, 1, tile, tile]
         self._tta: dict = {}             # device -> (tables int32 [8, batch, 4], tiles' and logits' transformed copies)
+        self._kept: dict = {}            # (H, W, device) -> (the run tiles' origins int32 [N, 2], the census int32 [N])
         self._cache: dict = {}           # (Scratch class, key, device) -> the scratch of a scene tool
 
     def _buffers(self, H: int, W: int, device: torch.device):
@@ -225,6 +334,7 @@ class ScenePredictor:
         self._geom.clear()
         self._tiles.clear()
         self._tta.clear()
+        self._kept.clear()
         self._cache.clear()
 
     def _scratch(self, cls, device, *key):
@@ -261,11 +371,35 @@ class ScenePredictor:
         apply_table(lg, None, tables[D4_INVERSE[op], :n], out=(lt[:n], None))
         return lt[:n]
 
+    def _kept_buffers(self, H: int, W: int, device: torch.device, N: int):
+        key = (H, W, device)
+        if key not in self._kept:
+            self._kept[key] = (torch.empty(N, 2, dtype=torch.int32, device=device), torch.empty(N, dtype=torch.int32, device=device))
+        return self._kept[key]
+
     @torch.no_grad()
-    def predict(self, scene, return_prob: bool = False) -> Dict[str, torch.Tensor]:
+    def predict(self, scene, return_prob: bool = False, *, valid=None, nodata=None, min_valid: int = 1, fill: float = 0.0,
+                norm=None) -> Dict[str, torch.Tensor]:
+        """The tiled prediction of `scene`. With `valid` (uint8 [H, W], numpy or tensor, copied to the device once; 0 = not
+        observed) or `nodata` the scene has no-data, and a pixel is VALID iff its byte of `valid` is non-zero (None: every
+        one), its value is not `nodata` (an exact compare: an integer in 0..255 for a uint8 scene, a float for a float32 one)
+        and, in a float32 scene, it is finite (nodata=float("nan"): the non-finite pixels only). Then only the tiles of
+        `plan_tiles` that hold at least `min_valid` (1..tile^2) valid pixels are run, in their row-major order; inside them an
+        invalid pixel enters the net as `fill` (finite, in the net's input domain; 0.0 is mid-grey after the reference's
+        normalisation); an invalid pixel, and a valid one that no run tile covers (min_valid > 1 only), has mask = 0, conf = 0
+        and prob = 0, and the result gains "valid" (uint8 [H, W], 1 = valid and covered), "tiles_total", "tiles_run" and
+        "tile_valid" (host int32 [N], the valid pixels of every planned tile). No run tile: no forward, all zero, no error.
+        `norm` = (offset, scale) takes a float32 scene through x = (v - offset) * scale on the way into the tiles (refused
+        for uint8 scenes); alone it selects neither the census nor the masking. With all five at their defaults nothing of
+        this runs."""
         shape = tuple(getattr(scene, "shape", ()))
         if len(shape) == 2:
             _check_geometry(shape[0], shape[1], self.tile, self.overlap)       # refuse before anything is copied
+        masked = valid is not None or nodata is not None
+        if len(shape) == 2:              # anything else is `_as_scene`'s to refuse
+            is_u8 = getattr(scene, "dtype", None) in (np.uint8, torch.uint8)
+            valid, nodata, min_valid, fill, norm = _check_validity("predict", shape[0], shape[1], is_u8, self.tile, valid, nodata,
+                                                                   min_valid, fill, norm)
         try:
             device = next(self.model.parameters()).device
         except StopIteration:
@@ -275,6 +409,19 @@ class ScenePredictor:
         K, T = self.num_classes, self.tile
         origins, o_dev, buf, acc, wsum, tiles = self._buffers(H, W, device)
         N = origins.shape[0]
+        extra = {}
+        if masked:
+            if valid is not None:
+                valid = valid.to(device)
+            kept_dev, counts_dev = self._kept_buffers(H, W, device, N)
+            tile_census(sc, o_dev, T, valid=valid, nodata=nodata, out=counts_dev)
+            tile_valid = counts_dev.cpu().numpy()                          # the one read-back of a masked predict
+            kept = select_tiles(tile_valid, min_valid)
+            extra = {"tiles_total": int(N), "tiles_run": int(kept.size), "tile_valid": tile_valid}
+            origins, o_dev, N = np.ascontiguousarray(origins[kept]), kept_dev, int(kept.size)
+            if N:
+                o_dev[:N].copy_(torch.from_numpy(origins))
+        gather_kw = {} if not masked and norm is None else dict(valid=valid, nodata=nodata, fill=fill, norm=norm)
         tta_bufs = self._tta_buffers(device) if self.tta > 1 else None
         was_training = self.model.training
         self.model.eval()
@@ -282,7 +429,7 @@ class ScenePredictor:
             buf.zero_()
             for i in range(0, N, self.batch):
                 n = min(self.batch, N - i)
-                x = gather_tiles(sc, o_dev[i:i + n], T, out=tiles[:n])
+                x = gather_tiles(sc, o_dev[i:i + n], T, out=tiles[:n], **gather_kw)
                 if self.tta == 1:
                     _blend(self.model(x), origins, o_dev, i, K, T, self.overlap, acc, wsum)
                     continue
@@ -290,11 +437,15 @@ class ScenePredictor:
                     _blend(self._forward_tta(x, op, n, tta_bufs), origins, o_dev, i, K, T, self.overlap, acc, wsum)
         finally:
             self.model.train(was_training)
-        return _finalize(acc, wsum, return_prob)
+        if not masked:
+            return _finalize(acc, wsum, return_prob)
+        out = _finalize_valid(acc, wsum, return_prob, sc, valid, nodata)
+        out.update(extra)
+        return out
 
     def detect(self, scene, return_prob: bool = False, outlines: bool = False, skeletons: bool = False,
                max_iterations: int = 32, measure: Optional[dict] = None, simplify: Optional[float] = None, split=None,
-               sieve=None, **region_kwargs) -> dict:
+               sieve=None, valid=None, nodata=None, min_valid: int = 1, fill: float = 0.0, norm=None, **region_kwargs) -> dict:
         """`predict(scene)` followed by `label_regions(out["mask"], out["conf"], **region_kwargs)`: the predict outputs
         unchanged, plus "labels", "regions", "count" and the cleaned class map under "mask_clean". With `outlines=True` also
         "outlines" = `outlines.region_outlines(out["labels"])` with the connectivity the regions were labelled with, and
@@ -317,10 +468,11 @@ class ScenePredictor:
         neighbour and small holes fill, `label_regions` and everything after it run on the cleaned map, "mask" stays the raw
         prediction, and "mask_sieved", "sieve_changed_pixels", "sieve_absorbed", "sieve_rounds" and "sieve_converged" are
         added. "conf" is not rewritten: a filled pixel carries the confidence of the class it had. With None nothing of it
-        runs."""
+        runs. `valid`, `nodata`, `min_valid`, `fill` and `norm` go to `predict`: an invalid pixel is class 0, hence background
+        for the regions."""
         if measure is not None and not isinstance(measure, dict):
             raise InsarError(f"measure: a dict of name -> raster or (raster, kwargs), got {type(measure).__name__}")
-        out = dict(self.predict(scene, return_prob=return_prob))
+        out = dict(self.predict(scene, return_prob=return_prob, valid=valid, nodata=nodata, min_valid=min_valid, fill=fill, norm=norm))
         H, W = out["mask"].shape
         max_regions = region_kwargs.get("max_regions", DEFAULT_MAX_REGIONS)
         class_map = out["mask"] if sieve is None else self._sieve(out, sieve, region_kwargs.get("connectivity", 8), max_regions)
@@ -428,15 +580,20 @@ class ScenePredictor:
         out["regions"]["perimeter"] = perimeters(out["outlines"]["rings"], out["regions"]["id"])
 
     def evaluate(self, scene, gt_mask, *, iou_threshold: float = 0.5, gt_min_area: int = 1, max_pairs: int = DEFAULT_MAX_PAIRS,
-                 boundary_distance: Optional[int] = None, measure: Optional[dict] = None, sieve=None, **region_kwargs) -> dict:
+                 boundary_distance: Optional[int] = None, measure: Optional[dict] = None, sieve=None, valid=None, nodata=None,
+                 min_valid: int = 1, fill: float = 0.0, norm=None, **region_kwargs) -> dict:
         """`detect(scene, **region_kwargs)`, then `label_regions` of the ground-truth class map (`gt_mask` uint8 [H, W], numpy
         or tensor, copied to the device once; 255 = ignore, labelled as background) with the same connectivity and
         `min_area=gt_min_area`, then `score.match_regions` with `void=gt_mask, void_value=255`: the detect outputs unchanged,
         plus "score" (the match result), "gt_labels", "gt_regions" and "gt_count". With `boundary_distance` = d (an integer
         >= 0) the score gains "boundary" = {"distance", "counts", "iou", "mean_iou"}: `distance.boundary_counts` of
         "mask_clean" against `gt_mask` (void 255) at d pixels, and `boundary_iou` of them; with None nothing of it runs.
-        `measure` and `sieve` go to `detect`: the sieve cleans the prediction only, never the ground truth."""
-        out = self.detect(scene, measure=measure, sieve=sieve, **region_kwargs)
+        `measure` and `sieve` go to `detect`: the sieve cleans the prediction only, never the ground truth. `valid`, `nodata`,
+        `min_valid`, `fill` and `norm` go to `predict`; where its "valid" is 0 the ground truth is set to 255 before anything
+        else, so that a ground-truth object wholly in no-data is no region at all (neither a miss nor a match), and one partly
+        in it is scored on its valid part."""
+        out = self.detect(scene, measure=measure, sieve=sieve, valid=valid, nodata=nodata, min_valid=min_valid, fill=fill, norm=norm,
+                          **region_kwargs)
         dev = out["mask"].device
         H, W = out["mask"].shape
         gt = torch.from_numpy(np.ascontiguousarray(gt_mask)) if isinstance(gt_mask, np.ndarray) else gt_mask
@@ -444,6 +601,8 @@ class ScenePredictor:
             raise InsarError(f"evaluate: gt_mask must be a uint8 [{H}, {W}] numpy array or tensor, got "
                              f"{getattr(gt, 'dtype', type(gt).__name__)} {tuple(getattr(gt, 'shape', ()))}")
         gt = gt.detach().to(dev).contiguous()
+        if "valid" in out:
+            gt = torch.where(out["valid"] == 0, torch.full_like(gt, 255), gt)
         gt_cls = torch.where(gt == 255, torch.zeros_like(gt), gt)
         max_regions = region_kwargs.get("max_regions", DEFAULT_MAX_REGIONS)
         truth = label_regions(gt_cls, None, connectivity=region_kwargs.get("connectivity", 8), min_area=gt_min_area,
@@ -457,13 +616,15 @@ class ScenePredictor:
         out.update(score=score, gt_labels=truth["labels"], gt_regions=truth["regions"], gt_count=truth["count"])
         return out
 
-    def detect_stack(self, scenes, *, valids=None, min_conf: float = 0.0, classes=1, words: Optional[int] = None,
-                     **follow_kwargs) -> dict:
+    def detect_stack(self, scenes, *, valids=None, min_conf: float = 0.0, classes=1, words: Optional[int] = None, nodata=None,
+                     min_valid: int = 1, fill: float = 0.0, norm=None, **follow_kwargs) -> dict:
         """One co-registered scene per date, oldest first: `predict` of each, its mask and confidence pushed into a
         `stack.DetectionStack` (`push(mask, conf=conf, min_conf=min_conf, classes=classes, valid=valids[i])`), then
         `stack.follow_sites(stack, **follow_kwargs)`: its result plus "stack". `valids`: None or one entry per scene, each None
         or a uint8 [H, W] map (numpy or tensor), 0 = not observed at that date. `words`: planes of 64 dates (None: as many as
-        the scenes need). Nothing scene-sized is kept per date beyond the stack's bits: a date's mask and confidence are
+        the scenes need). `nodata`, `min_valid`, `fill` and `norm` go to every date's `predict` (with `nodata`, next to `valids[i]`
+        as its `valid`): the date's "valid" is what is pushed, so that a date's no-data is "not observed", not "observed, no
+        hit", and neither breaks nor extends a run. Nothing scene-sized is kept per date beyond the stack's bits: a date's mask and confidence are
         released before the next scene is predicted."""
         from .stack import MAX_DATES, DetectionStack, follow_sites
         try:
@@ -478,6 +639,9 @@ class ScenePredictor:
             raise InsarError(f"detect_stack: the scenes must share one 2-D shape (co-register them first), got {sorted(shapes)}")
         H, W = next(iter(shapes))
         _check_geometry(H, W, self.tile, self.overlap)
+        for s in scenes:                 # what `predict` would refuse, before the stack is allocated
+            _check_validity("predict", H, W, getattr(s, "dtype", None) in (np.uint8, torch.uint8), self.tile, None, nodata, min_valid,
+                            fill, norm)
         if valids is not None:
             valids = list(valids)
             if len(valids) != n:
@@ -497,7 +661,9 @@ class ScenePredictor:
                 if not isinstance(v, torch.Tensor) or v.dtype != torch.uint8 or tuple(v.shape) != (H, W):
                     raise InsarError(f"detect_stack: valids[{i}] must be a uint8 [{H}, {W}] numpy array or tensor")
                 v = v.detach().to(device).contiguous()
-            out = self.predict(scene)
+            out = self.predict(scene, nodata=nodata, min_valid=min_valid, fill=fill, norm=norm)
+            if "valid" in out:
+                v = out["valid"] if v is None else out["valid"] * (v != 0)
             st.push(out["mask"], conf=out["conf"], min_conf=min_conf, classes=classes, valid=v)
             del out
         res = follow_sites(st, **follow_kwargs)
@@ -506,8 +672,10 @@ class ScenePredictor:
 
 
 def predict_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw) -> Dict[str, torch.Tensor]:
-    """One-shot ScenePredictor(model, **kw).predict(scene, return_prob)."""
-    return ScenePredictor(model, **kw).predict(scene, return_prob=return_prob)
+    """One-shot ScenePredictor(model, ...).predict(scene, return_prob, ...): `valid`, `nodata`, `min_valid`, `fill` and `norm`
+    go to `predict`, every other keyword to the predictor."""
+    run_kw = {k: kw.pop(k) for k in ("valid", "nodata", "min_valid", "fill", "norm") if k in kw}
+    return ScenePredictor(model, **kw).predict(scene, return_prob=return_prob, **run_kw)
 
 
 def detect_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw) -> dict:
