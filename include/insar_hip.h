@@ -753,6 +753,61 @@ int insar_sieve_rounds(const void* table, const uint8_t* mask, const int32_t* th
 int insar_sieve_apply(const int32_t* labels, const uint8_t* mask, int32_t H, int32_t W, int32_t max_regions, int64_t max_pairs,
                       int32_t max_rounds, void* scratch, uint8_t* out, uint8_t* changed /*nullable*/, void* stream);
 
+/* ---- hysteresis thresholds (build-side addition; the reference has no post-processing): csrc/hysteresis.hip ----------------
+ * A site is a connected component of {score >= low} that holds at least min_seeds pixels with score >= high.
+ *   candidates: score fp32 [planes][H][W] (row-major, H * W < 2^31), plane p belonging to class p + 1 (a background plane is
+ *               not passed: it never takes part); thresholds fp32 [512] in device memory, low[c] at word c and high[c] at word
+ *               256 + c, low[c] <= high[c] both finite, or low[c] = NaN for a class that is not selected. A pixel is a
+ *               candidate of class c if score[c] >= low[c] in a float32 compare (NaN compares false) and its byte of `valid`
+ *               (uint8 [H][W], nullable) is non-zero. Of several classes the greatest score wins, ties go to the smallest
+ *               class. cand uint8 [H][W] is the class or 0, conf fp32 [H][W] the class's score, 0 where there is no candidate.
+ *   regions:    the caller runs the five insar_regions_* phases on cand / conf with min_conf = -inf: the components of the
+ *               candidate map of area >= min_area, numbered 1..N by ascending root, their InsarRegion table over the whole
+ *               low-threshold extent, the label map and mask_out.
+ *   seeds:      a labelled pixel is a seed if conf >= high[cand]. Per label the number of seeds and the peak key
+ *               (ordered_u32(conf) << 32) | (0xFFFFFFFF - index), where ordered_u32 flips all bits of a negative float32 and
+ *               the sign bit of any other: its maximum is the exact maximum of conf at the first pixel, in row-major order,
+ *               that reaches it.
+ *   keep:       a region is kept if n_seed >= min_seeds; kept regions are renumbered 1..N' in the same order and copied, with
+ *               their seed fields, into a second, compact table.
+ *   apply:      labels = remap[labels]; mask = cand where the new label is not 0, else 0.
+ * Integers only behind the compares (agent-scope integer atomics, no float atomics): bitwise reproducible. One call per phase
+ * on one stream, 12 launches in all with the seven of the regions phases, whatever the map holds; no work-group waits on
+ * another. Every argument is checked before the device is touched.
+ *   scratch: insar_hyst_scratch_bytes(...) bytes, 16-byte aligned: the seed table {int64 n_seed, uint64 peak_key}
+ *            [1 + max_regions], then remap int32 [1 + max_regions]. Nothing in it has to survive between calls or be cleared
+ *            by the caller.
+ *   table:   InsarHystRegion [1 + max_regions], 16-byte aligned, NOT the InsarRegion table. Record 0 is the header: area = N',
+ *            the number of kept regions, sum_y = N, the TRUE number of components of area >= min_area, which may exceed
+ *            max_regions (the result is then meaningless); records 1..N' are the kept regions. */
+typedef struct InsarHystRegion {
+  int64_t area;            /* the fields of InsarRegion, over the whole low-threshold extent (header record: N') */
+  int64_t sum_y, sum_x;    /* (header record: sum_y = N) */
+  int64_t sum_conf;
+  int32_t y0, x0, y1, x1;
+  int32_t root;
+  int32_t cls;
+  int32_t _pad[2];
+  int64_t n_seed;          /* pixels with conf >= high[cls] */
+  uint64_t peak_key;       /* (ordered_u32(peak) << 32) | (0xFFFFFFFF - index of the first pixel that reaches the peak) */
+} InsarHystRegion;
+/* host only: bytes of the scratch (seed table and remap) and of the compact table for max_regions regions */
+int insar_hyst_scratch_bytes(int32_t H, int32_t W, int32_t max_regions, int64_t* scratch_bytes, int64_t* table_bytes);
+/* 1 launch: cand and conf from the score planes. 1 <= planes <= 255. 16-byte loads and stores wherever a quad lies inside the
+ * map and its plane offset keeps the alignment; guarded scalars elsewhere. */
+int insar_hyst_classify(const float* score, int32_t planes, int32_t H, int32_t W, const float* thresholds,
+                        const uint8_t* valid /*nullable*/, uint8_t* cand, float* conf, void* stream);
+/* 2 launches: the seed table cleared, then filled from labels (as insar_regions_relabel wrote them; ids above max_regions
+ * are never an index), cand and conf. */
+int insar_hyst_seeds(const int32_t* labels, const uint8_t* cand, const float* conf, const float* thresholds, int32_t H, int32_t W,
+                     int32_t max_regions, void* scratch, void* stream);
+/* 1 launch, one work-group: remap and the compact table from `regions` (the InsarRegion table) and the seed table.
+ * min_seeds >= 1. */
+int insar_hyst_keep(const void* regions, int64_t min_seeds, int32_t max_regions, void* scratch, void* table, void* stream);
+/* 1 launch: labels renumbered in place, mask uint8 [H][W] written. */
+int insar_hyst_apply(const uint8_t* cand, int32_t H, int32_t W, int32_t max_regions, const void* scratch, int32_t* labels,
+                     uint8_t* mask, void* stream);
+
 /* ---- region outlines (build-side addition; the reference has no post-processing): csrc/outline.hip ------------------------
  * The exact pixel-edge ("crack") outline of every region of a label map `labels` int32 [H][W] (row-major; 0 or an id >= 1, as
  * insar_regions_relabel writes it, but any int32 map is legal; H, W >= 1, H * W < 2^29), as ordered, closed rings of lattice

@@ -26,6 +26,7 @@ from .rasterise import PolygonTable, RasterScratch, from_geojson, labels_from_ge
 from .warp import WarpSpec, draw_warps, gather_warped, grid_matrix, multilook, warp_raster  # noqa: F401
 from .stack import DetectionStack, StackScratch, follow_sites, site_series  # noqa: F401
 from .sieve import SieveScratch, region_adjacency, sieve_regions  # noqa: F401
+from .hysteresis import HysteresisScratch, hysteresis_regions  # noqa: F401
 
 __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "ChannelAttentionModule", "MaxPool2d", "CrossEntropyLoss", "DiceLoss", "DiceCELoss", "Adam", "GraphedTrainStep",
            "compute_metrics", "train_model", "validate_model", "save_history", "VOCSegDataset", "SyntheticTiles",
@@ -44,3 +45,4 @@ __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "Cha
            "warp_raster", "grid_matrix", "multilook", "WarpSpec", "draw_warps", "gather_warped",
            "DetectionStack", "StackScratch", "site_series", "follow_sites",
            "SieveScratch", "region_adjacency", "sieve_regions"]
+__all__ += ["HysteresisScratch", "hysteresis_regions"]

@@ -234,6 +234,11 @@ _SIGNATURES = {
     "insar_sieve_pairs": [_P, _I, _I, _I, _I, _L, _I, _P, _P],
     "insar_sieve_rounds": [_P, _P, _P, _I, _I, _I, _I, _I, _L, _I, _P, _P],
     "insar_sieve_apply": [_P, _P, _I, _I, _I, _L, _I, _P, _P, _P, _P],
+    "insar_hyst_scratch_bytes": [_I, _I, _I, _P, _P],
+    "insar_hyst_classify": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "insar_hyst_seeds": [_P, _P, _P, _P, _I, _I, _I, _P, _P],
+    "insar_hyst_keep": [_P, _L, _I, _P, _P, _P],
+    "insar_hyst_apply": [_P, _I, _I, _I, _P, _P, _P, _P],
     "insar_outline_scratch_bytes": [_I, _I, _I, _I, _P, _P],
     "insar_outline_launches": [_I],
     "insar_outline_edges": [_P, _I, _I, _I, _I, _P, _P, _P],

@@ -445,7 +445,8 @@ class ScenePredictor:
 
     def detect(self, scene, return_prob: bool = False, outlines: bool = False, skeletons: bool = False,
                max_iterations: int = 32, measure: Optional[dict] = None, simplify: Optional[float] = None, split=None,
-               sieve=None, valid=None, nodata=None, min_valid: int = 1, fill: float = 0.0, norm=None, **region_kwargs) -> dict:
+               sieve=None, valid=None, nodata=None, min_valid: int = 1, fill: float = 0.0, norm=None, hysteresis=None,
+               **region_kwargs) -> dict:
         """`predict(scene)` followed by `label_regions(out["mask"], out["conf"], **region_kwargs)`: the predict outputs
         unchanged, plus "labels", "regions", "count" and the cleaned class map under "mask_clean". With `outlines=True` also
         "outlines" = `outlines.region_outlines(out["labels"])` with the connectivity the regions were labelled with, and
@@ -469,16 +470,29 @@ class ScenePredictor:
         prediction, and "mask_sieved", "sieve_changed_pixels", "sieve_absorbed", "sieve_rounds" and "sieve_converged" are
         added. "conf" is not rewritten: a filled pixel carries the confidence of the class it had. With None nothing of it
         runs. `valid`, `nodata`, `min_valid`, `fill` and `norm` go to `predict`: an invalid pixel is class 0, hence background
-        for the regions."""
+        for the regions. With `hysteresis` = (low, high) or a dict of `hysteresis.hysteresis_regions` keywords, the sites are
+        grown from confident seeds instead: `predict` computes the class probabilities ("prob" is in the result only if
+        `return_prob`), `hysteresis_regions(prob, low, high, valid=out.get("valid"), ...)` with detect's `connectivity`,
+        `min_area` and `max_regions` replaces the `label_regions` call, "labels", "regions" (which gain n_seed, peak, peak_y and
+        peak_x) and "count" come from it, "mask_clean" is its mask, "conf_hysteresis" its candidate plane,
+        "hysteresis_candidates" the components before the seed rule, and "mask" and "conf" stay the raw prediction. `min_conf`
+        and `sieve` are refused next to it: the two thresholds replace the one, and a sieved arg-max map and a low-threshold
+        map are different maps. With None nothing of it runs."""
         if measure is not None and not isinstance(measure, dict):
             raise InsarError(f"measure: a dict of name -> raster or (raster, kwargs), got {type(measure).__name__}")
-        out = dict(self.predict(scene, return_prob=return_prob, valid=valid, nodata=nodata, min_valid=min_valid, fill=fill, norm=norm))
+        if hysteresis is not None:
+            hyst_kw = self._hysteresis_kwargs(hysteresis, sieve, region_kwargs)
+        out = dict(self.predict(scene, return_prob=return_prob or hysteresis is not None, valid=valid, nodata=nodata,
+                                min_valid=min_valid, fill=fill, norm=norm))
         H, W = out["mask"].shape
         max_regions = region_kwargs.get("max_regions", DEFAULT_MAX_REGIONS)
-        class_map = out["mask"] if sieve is None else self._sieve(out, sieve, region_kwargs.get("connectivity", 8), max_regions)
-        reg = label_regions(class_map, out["conf"], scratch=self._scratch(RegionScratch, out["mask"].device, H, W, max_regions),
-                            **region_kwargs)
-        out.update(labels=reg["labels"], regions=reg["regions"], count=reg["count"], mask_clean=reg["mask"])
+        if hysteresis is not None:
+            self._grow(out, hyst_kw, return_prob)
+        else:
+            class_map = out["mask"] if sieve is None else self._sieve(out, sieve, region_kwargs.get("connectivity", 8), max_regions)
+            reg = label_regions(class_map, out["conf"], scratch=self._scratch(RegionScratch, out["mask"].device, H, W, max_regions),
+                                **region_kwargs)
+            out.update(labels=reg["labels"], regions=reg["regions"], count=reg["count"], mask_clean=reg["mask"])
         if split is not None and split is not False:
             self._split(out, split, max_regions)
         if simplify is not None and not outlines:
@@ -490,6 +504,41 @@ class ScenePredictor:
         if measure is not None:
             self._measure(out, scene, measure, max_regions)
         return out
+
+    @staticmethod
+    def _hysteresis_kwargs(hysteresis, sieve, region_kwargs: dict) -> dict:
+        """The keywords of `hysteresis_regions` from detect's `hysteresis` and region keywords; refused before `predict` runs."""
+        if isinstance(hysteresis, dict):
+            kw = dict(hysteresis)
+            if "low" not in kw or "high" not in kw:
+                raise InsarError("hysteresis: a dict of hysteresis_regions keywords needs 'low' and 'high'")
+        elif isinstance(hysteresis, (tuple, list)) and len(hysteresis) == 2:
+            kw = {"low": hysteresis[0], "high": hysteresis[1]}
+        else:
+            raise InsarError(f"hysteresis: (low, high) or a dict of hysteresis_regions keywords, got {hysteresis!r}")
+        for name in ("score", "valid", "scratch"):
+            if name in kw:
+                raise InsarError(f"hysteresis: {name!r} is detect's to give")
+        if "min_conf" in region_kwargs:
+            raise InsarError("detect: min_conf next to hysteresis: the two thresholds replace it (low is the cut on the extent)")
+        if sieve is not None:
+            raise InsarError("detect: sieve next to hysteresis: a sieved arg-max map and a low-threshold map are different maps, "
+                             "and their combination is not defined")
+        for name, v in region_kwargs.items():
+            if name not in ("connectivity", "min_area", "max_regions"):
+                raise InsarError(f"detect: {name!r} next to hysteresis: connectivity, min_area and max_regions are handed to it")
+            kw.setdefault(name, v)
+        return kw
+
+    def _grow(self, out: dict, kw: dict, return_prob: bool) -> None:
+        """`hysteresis_regions` of out["prob"] in place of `label_regions`; its results go into `out`."""
+        from .hysteresis import HysteresisScratch, hysteresis_regions
+        prob = out["prob"] if return_prob else out.pop("prob")
+        _, H, W = prob.shape
+        scratch = self._scratch(HysteresisScratch, prob.device, H, W, kw.get("max_regions", DEFAULT_MAX_REGIONS))
+        hy = hysteresis_regions(prob, kw.pop("low"), kw.pop("high"), valid=out.get("valid"), scratch=scratch, **kw)
+        out.update(labels=hy["labels"], regions=hy["regions"], count=hy["count"], mask_clean=hy["mask"],
+                   conf_hysteresis=hy["conf"], hysteresis_candidates=hy["candidates"])
 
     def _sieve(self, out: dict, sieve, connectivity: int, max_regions: int) -> torch.Tensor:
         """The sieved class map of out["mask"]; the sieve's figures go into `out`."""
@@ -535,7 +584,8 @@ class ScenePredictor:
         H, W = out["labels"].shape
         scratch = self._scratch(SplitScratch, out["labels"].device, H, W, kw["max_regions"], kw.get("max_pairs", DEFAULT_MAX_PAIRS),
                                 kw.get("max_rounds", 64))
-        sp = split_regions(out["labels"], mask=out["mask_clean"], conf=out["conf"], scratch=scratch, **kw)
+        # with hysteresis the labels reach below the arg-max boundary: their confidence is the candidate plane
+        sp = split_regions(out["labels"], mask=out["mask_clean"], conf=out.get("conf_hysteresis", out["conf"]), scratch=scratch, **kw)
         out.update(labels=sp["labels"], regions=sp["regions"], count=sp["count"], split_rounds=sp["rounds"],
                    split_converged=sp["converged"])
 
@@ -581,19 +631,19 @@ class ScenePredictor:
 
     def evaluate(self, scene, gt_mask, *, iou_threshold: float = 0.5, gt_min_area: int = 1, max_pairs: int = DEFAULT_MAX_PAIRS,
                  boundary_distance: Optional[int] = None, measure: Optional[dict] = None, sieve=None, valid=None, nodata=None,
-                 min_valid: int = 1, fill: float = 0.0, norm=None, **region_kwargs) -> dict:
+                 min_valid: int = 1, fill: float = 0.0, norm=None, hysteresis=None, **region_kwargs) -> dict:
         """`detect(scene, **region_kwargs)`, then `label_regions` of the ground-truth class map (`gt_mask` uint8 [H, W], numpy
         or tensor, copied to the device once; 255 = ignore, labelled as background) with the same connectivity and
         `min_area=gt_min_area`, then `score.match_regions` with `void=gt_mask, void_value=255`: the detect outputs unchanged,
         plus "score" (the match result), "gt_labels", "gt_regions" and "gt_count". With `boundary_distance` = d (an integer
         >= 0) the score gains "boundary" = {"distance", "counts", "iou", "mean_iou"}: `distance.boundary_counts` of
         "mask_clean" against `gt_mask` (void 255) at d pixels, and `boundary_iou` of them; with None nothing of it runs.
-        `measure` and `sieve` go to `detect`: the sieve cleans the prediction only, never the ground truth. `valid`, `nodata`,
+        `measure`, `sieve` and `hysteresis` go to `detect`: they shape the prediction only, never the ground truth. `valid`, `nodata`,
         `min_valid`, `fill` and `norm` go to `predict`; where its "valid" is 0 the ground truth is set to 255 before anything
         else, so that a ground-truth object wholly in no-data is no region at all (neither a miss nor a match), and one partly
         in it is scored on its valid part."""
         out = self.detect(scene, measure=measure, sieve=sieve, valid=valid, nodata=nodata, min_valid=min_valid, fill=fill, norm=norm,
-                          **region_kwargs)
+                          hysteresis=hysteresis, **region_kwargs)
         dev = out["mask"].device
         H, W = out["mask"].shape
         gt = torch.from_numpy(np.ascontiguousarray(gt_mask)) if isinstance(gt_mask, np.ndarray) else gt_mask
@@ -680,8 +730,8 @@ def predict_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw
 
 def detect_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw) -> dict:
     """One-shot ScenePredictor(model, ...).detect(scene, return_prob, ...): tile / overlap / batch / num_classes / tta go to
-    the predictor, `outlines`, `simplify`, `skeletons`, `max_iterations`, `measure`, `split` and `sieve` to `detect`, every other keyword to
-    `label_regions`."""
+    the predictor, `outlines`, `simplify`, `skeletons`, `max_iterations`, `measure`, `split`, `sieve` and `hysteresis` to `detect`, every other
+    keyword to `label_regions`."""
     pred_kw = {k: kw.pop(k) for k in ("tile", "overlap", "batch", "num_classes", "tta") if k in kw}
     return ScenePredictor(model, **pred_kw).detect(scene, return_prob=return_prob, **kw)
 
