@@ -861,6 +861,63 @@ int insar_outline_rings(const int32_t* labels, int32_t H, int32_t W, int32_t n_e
 int insar_outline_write(int32_t H, int32_t W, int32_t n_edges, int32_t corners_only, int32_t max_rings, int32_t max_vertices,
                         int32_t max_edges, void* scratch, void* table, int32_t* vertices, void* stream);
 
+/* ---- contour lines (build-side addition; the reference has no post-processing): csrc/contour.hip ---------------------------
+ * The iso-lines of a raster [H][W] (row-major; float32, uint8 or int32, INSAR_ZONAL_*; 1 <= H, W <= 2^22) at n_levels levels
+ * (1 .. 32, n_levels * H * W < 2^30) as ordered polylines of sub-pixel vertices: marching squares in exact integers.
+ *   q:         per pixel, by the rule of insar_zonal_accumulate: integer rasters q = v, float32 q = rint(clamp((double)v * scale,
+ *              +-(2^31 - 1))) to nearest even. A pixel that is not finite, equals `nodata` in the raster's own type (has_nodata) or
+ *              has valid[p] == 0 (valid: uint8 [H][W], nullable) is INVALID. levels_q: HOST int32 [n_levels], strictly increasing.
+ *   node:      the centre of pixel (y, x), at (y + 1/2, x + 1/2) in the frame of the region outlines; every coordinate is an int32
+ *              in 1/256 pixel: (256 y + 128, 256 x + 128). A node is ABOVE level l iff q >= levels_q[l].
+ *   crossing:  lattice edge o = 0 joins node p = y * W + x to its right neighbour, o = 1 to the node below. It is crossed at l iff
+ *              both ends are valid and exactly one is above, and it is a crossing iff one of the two cells (2 x 2 nodes) it bounds
+ *              has four valid nodes (otherwise no segment ends on it and it is not counted). id (l * H * W + p) * 2 + o. Position,
+ *              from the below end: s = floor(((q_l - q_below) * 512 + d) / (2 d)), d = q_above - q_below, in int64, clamped to
+ *              1 .. 255; the offset from p is s if p is the below end, else 256 - s. No vertex lies on a node.
+ *   segments:  a cell with four valid nodes emits the marching-squares segments of its above-mask, directed with the above side on
+ *              the right (the handedness of the region outlines: the ring round a peak has positive area2); the saddle masks join
+ *              the above corners iff the four q sum to >= 4 q_l in int64. A crossing starts at most one segment and ends at most one.
+ *   lines:     the components: closed rings (leader = smallest crossing id) and open lines (leader = the head, the crossing no
+ *              segment ends on; they end on the raster border or beside a cell with an invalid node). Lines are numbered in
+ *              ascending leader order, so level by level; vertices are ranked from the leader; every crossing is kept (V = E).
+ *   vertices:  int32 [n_crossings][2] as (Y, X), 8-byte aligned, line after line.
+ *   table:     InsarContourLine [4 + max_lines], 16-byte aligned. Records 0 .. 3 are the header, 48 int32 slots: slot 2 = the
+ *              TRUE number of lines (it may exceed max_lines), 3 = E, 5 = V, 16 + l = the crossings of level l; record 4 + r is line r.
+ *   scratch:   insar_contour_scratch_bytes(...) bytes, 16-byte aligned; nothing in it has to survive between calls or be cleared.
+ * Call edges, lead, rank, lines, write in this order on one stream with the same H, W, n_levels and max_vertices; read E from the
+ * header after `edges` and pass it on as n_crossings (lead .. write refuse n_crossings > max_vertices). 11 + 2 ceil(log2 E)
+ * launches in all, a function of E alone; one launch per step, no work-group waits on another, integers only behind the
+ * quantisation (bitwise reproducible). No kernel writes a crossing slot >= max_vertices or a record > max_lines. Every argument
+ * is checked before the device is touched. */
+typedef struct InsarContourLine {
+  int64_t area2;           /* rings: signed doubled area in 1/256^2 pixel, sum of X_i * Y_{i+1} - X_{i+1} * Y_i; open lines: 0 */
+  int32_t level, leader;   /* level index; the leader's crossing id */
+  int32_t start, count;    /* first vertex and number of vertices in the vertex array */
+  int32_t closed;          /* 1 ring, 0 open line */
+  int32_t y0, x0, y1, x1;  /* half-open box in 1/256 pixel: y0 <= Y < y1, x0 <= X < x1 over the line's vertices */
+  int32_t _pad;
+} InsarContourLine;
+/* host only: bytes of scratch for an H x W raster at n_levels levels with max_vertices crossing slots, and of a table of max_lines */
+int insar_contour_scratch_bytes(int32_t H, int32_t W, int32_t n_levels, int32_t max_lines, int32_t max_vertices,
+                                int64_t* scratch_bytes, int64_t* table_bytes);
+/* host only: the launches of the five calls below for n_crossings crossings: 11 + 2 ceil(log2 n_crossings) (n_crossings < 1: 5) */
+int insar_contour_launches(int32_t n_crossings);
+/* 5 launches (q and valid flag per pixel; crossing masks and counts per level and block; one-work-group scan, the header written;
+ * compact index per mask word; vertex, id, successor and head flag of every crossing below max_vertices). */
+int insar_contour_edges(const void* raster, int32_t elem_type, int32_t H, int32_t W, double scale, int32_t has_nodata, double nodata,
+                        const uint8_t* valid, const int32_t* levels_q, int32_t n_levels, int32_t max_vertices, void* scratch,
+                        void* table, void* stream);
+/* ceil(log2 n_crossings) launches: pointer doubling with a running minimum; tails point at themselves. */
+int insar_contour_lead(int32_t H, int32_t W, int32_t n_levels, int32_t n_crossings, int32_t max_vertices, void* scratch, void* stream);
+/* 1 + ceil(log2 n_crossings) launches: rings cut in front of their leader, heads written at their tails' slots; Wyllie ranking. */
+int insar_contour_rank(int32_t H, int32_t W, int32_t n_levels, int32_t n_crossings, int32_t max_vertices, void* scratch, void* stream);
+/* 3 launches (leaders and line lengths per block; one-work-group scan, the line count to the header; numbers, records initialised) */
+int insar_contour_lines(int32_t H, int32_t W, int32_t n_levels, int32_t n_crossings, int32_t max_lines, int32_t max_vertices,
+                        void* scratch, void* table, void* stream);
+/* 2 launches (vertices scattered into line order; area2 and box per line). vertices: n_crossings slots. */
+int insar_contour_write(int32_t H, int32_t W, int32_t n_levels, int32_t n_crossings, int32_t max_lines, int32_t max_vertices,
+                        void* scratch, void* table, int32_t* vertices, void* stream);
+
 /* ---- outline simplification (build-side addition; the reference has no post-processing): csrc/simplify.hip -------------------
  * Douglas-Peucker over the rings of the region outlines, in exact integers, with the common border of two regions simplified
  * to the same vertices from both sides. A POSITION is an index into the input vertex array; the kept set is a set of positions.

@@ -19,6 +19,7 @@ from .distance import DistanceScratch, boundary_counts, boundary_iou, distance_t
 from .crops import CropIndex, SceneCrops, draw_crops, gather_crops  # noqa: F401
 from .outlines import OutlineScratch, region_outlines, to_geojson, to_polygons  # noqa: F401
 from .simplify import SimplifyScratch, simplify_outlines  # noqa: F401
+from .contours import ContourScratch, contour_lines, contour_polygons, contours_to_geojson, lines_to_coords  # noqa: F401
 from .skeletons import SkeletonScratch, skeleton_table, thin_regions  # noqa: F401
 from .zonal import ZonalScratch, percentile, region_stats  # noqa: F401
 from .split import SplitScratch, split_regions  # noqa: F401
@@ -39,6 +40,7 @@ __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "Cha
            "DistanceScratch", "distance_transform", "void_band", "expand_labels", "boundary_counts", "boundary_iou",
            "CropIndex", "SceneCrops", "draw_crops", "gather_crops",
            "OutlineScratch", "region_outlines", "to_polygons", "to_geojson", "SimplifyScratch", "simplify_outlines",
+           "ContourScratch", "contour_lines", "contour_polygons", "contours_to_geojson", "lines_to_coords",
            "SkeletonScratch", "thin_regions", "skeleton_table",
            "PolygonTable", "RasterScratch", "pack_polygons", "from_geojson", "rasterise_polygons", "labels_from_geojson",
            "ZonalScratch", "region_stats", "percentile", "SplitScratch", "split_regions",

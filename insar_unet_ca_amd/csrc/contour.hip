@@ -1,0 +1,680 @@
+// Contour lines: the iso-lines of a raster [H][W] (float32, uint8 or int32) at up to 32 levels as ordered polylines of sub-pixel
+// vertices in 1/256 pixel, closed rings and open lines, by marching squares in exact integers. Semantics: include/insar_hip.h.
+// A node is a pixel centre, a lattice edge joins a node p to its right (o = 0) or lower (o = 1) neighbour, and a crossing is a
+// lattice edge whose two valid ends lie on different sides of level l and that bounds a cell of four valid nodes; its id is
+// (l * H * W + p) * 2 + o, its COMPACT index k the number of crossings with a smaller id. Every array below is indexed by k;
+// per level the raster has one 2-bit mask per pixel, four pixels to a 32-bit word (the plane padded to whole words), and one
+// compact index per WORD: index(l, p, o) = off4[word] + popcount(mask bits of the word below bit 8 (p & 3) + o).
+// With E crossings and R = ceil(log2 E):
+//
+//   edges   quantise  per pixel: q (zonal.hip's rule) and the valid flag; the only kernel that sees a float
+//           mark      per word of four pixels: which of its eight lattice edges are crossings, level by level (q is loaded once
+//                     for all levels); crossings per level and block of 1024 pixels
+//           scan      one work-group: exclusive prefix sum of the counts in (level, block) order; E and the crossings per level
+//                     go to the table header
+//           offsets   per level and word: the compact index of its first crossing
+//           link      per crossing: vertex, id, successor (the turn rule below) or none, "no predecessor" flag; pair (succ, k),
+//                     a crossing without successor (a tail) pointing at itself
+//   lead    R rounds of pointer doubling on pairs (jump, min): afterwards an element of a ring knows the ring's smallest
+//           crossing, an element of an open line has jumped to its tail (the fixed point), and "my jump target has no successor"
+//           tells the two apart
+//   rank    cut       rings are cut in front of their leader, open lines end at their tail anyway: pair (next, 1) or (-1, 0);
+//                     lead[k] = the ring's leader, or -1 - tail for an open line, whose head writes itself at its tail's slot
+//           R rounds of Wyllie list ranking: d[k] becomes the distance from k to the last crossing of its line
+//   lines   count     leaders (ring minima and heads) and their line lengths per block of 1024 crossings
+//           scan      one work-group: both prefix sums; the number of lines goes to the header
+//           number    per leader: line number and first position; the line's record is initialised
+//   write   scatter   per crossing: position = line start + rank; the vertex goes there (every crossing is kept: V = E)
+//           reduce    over the ordered array, where a line is one contiguous run: area2 of the rings and the box (combined over
+//                     the runs of a wave before the atomics)
+//
+// 11 + 2 R launches, a function of E alone (5 when E = 0). One launch per step and no work-group ever waits on another: every
+// round reads one pair buffer and writes the other. Integers only behind `quantise`; the atomics add int64 / take int32 minima
+// and maxima at agent scope, so their arrival order changes nothing. A round moves 24 bytes per crossing (8 read in index order,
+// 8 gathered, 8 written). Capacity: no kernel writes a crossing slot or a vertex >= max_vertices or a record > max_lines.
+//
+// The turn rule of `link`. The line runs with the above side on its right. Through a crossing it travels in direction d with the
+// above end A of the lattice edge on the right and the below end B on the left; the cell ahead has A' = A + d and B' = B + d. A'
+// below: turn right (leave through A - A'), unless B' is above and the saddle is joined (the four q sum to >= 4 q_l), then turn left
+// (leave through B - B'); A' above: left if B' is above too, else straight on (leave through A' - B').
+#include "scene_common.h"
+#include <limits.h>
+
+#define CT_THREADS 256
+#define CT_NB 1024                        // pixels / crossings per numbering block (256 threads x 4)
+#define CT_SCAN_THREADS 1024
+#define CT_MAX_LEVELS 32
+#define CT_MAX_CROSSINGS (1 << 30)
+#define CT_MAX_SIDE (1 << 22)             // 256 * side + 128 fits an int32
+#define CT_LIMIT 2147483647.0
+#define CT_HDR 4                          // records of the table header: 48 int32 slots
+// int32 slots of the header (InsarContourLine: area2 0-1, level 2, leader 3, start 4, count 5, ...)
+#define CT_HDR_LINES 2
+#define CT_HDR_CROSSINGS 3
+#define CT_HDR_VERTS 5
+#define CT_HDR_LEVELS 16                  // .. 47: crossings per level
+
+static_assert(sizeof(InsarContourLine) == 48, "InsarContourLine is three 16-byte stores");
+static_assert(CT_THREADS == 4 * INSAR_WAVE, "four waves per work-group in ct_block_excl");
+static_assert(CT_HDR_LEVELS + CT_MAX_LEVELS == CT_HDR * (int)sizeof(InsarContourLine) / 4, "the level counts end the header");
+
+struct CtLevels { int q[CT_MAX_LEVELS]; };
+
+// exclusive prefix of v over the work-group's threads; *total is the work-group's sum. wsum: CT_THREADS / INSAR_WAVE ints of LDS.
+__device__ __forceinline__ int ct_block_excl(int v, int* wsum, int* total) {
+  const int lane = threadIdx.x & (INSAR_WAVE - 1), wave = threadIdx.x / INSAR_WAVE;
+  const int incl = wave_incl_scan(v, lane);
+  if (lane == INSAR_WAVE - 1) wsum[wave] = incl;
+  __syncthreads();
+  int off = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < CT_THREADS / INSAR_WAVE; ++w) {
+    if (w < wave) off += wsum[w];
+    tot += wsum[w];
+  }
+  *total = tot;
+  __syncthreads();                                               // wsum is free again
+  return off + incl - v;
+}
+
+// ---------------------------------------------------------------------------------------------
+// edges: quantise / mark / scan / offsets / link
+// ---------------------------------------------------------------------------------------------
+// four raster elements as values the quantiser takes (zonal.hip's ZnRaster, without the clipped count)
+template <typename T> struct CtRaster;
+template <> struct CtRaster<float> {
+  typedef float V;
+  __device__ __forceinline__ static void load(const float* p, int64_t i, int64_t n, bool vec, V* v) { quad_load(p, i, n, vec, 0.0f, v); }
+  __device__ __forceinline__ static bool quantise(V v, double scale, bool has_nodata, double nodata, int* q) {
+    if (!(fabsf(v) <= 3.402823466e38f) || (has_nodata && v == (float)nodata)) return false;
+    double d = (double)v * scale;
+    d = d > CT_LIMIT ? CT_LIMIT : d < -CT_LIMIT ? -CT_LIMIT : d;
+    *q = (int)rint(d);                                           // nearest even; |d| <= 2^31 - 1 fits
+    return true;
+  }
+};
+template <> struct CtRaster<int> {
+  typedef int V;
+  __device__ __forceinline__ static void load(const int* p, int64_t i, int64_t n, bool vec, V* v) { quad_load(p, i, n, vec, 0, v); }
+  __device__ __forceinline__ static bool quantise(V v, double, bool has_nodata, double nodata, int* q) {
+    if (has_nodata && v == (int)nodata) return false;
+    *q = v;
+    return true;
+  }
+};
+template <> struct CtRaster<uint8_t> {
+  typedef int V;
+  __device__ __forceinline__ static void load(const uint8_t* p, int64_t i, int64_t n, bool vec, V* v) { quad_load_u8(p, i, n, vec, 0, v); }
+  __device__ __forceinline__ static bool quantise(V v, double s, bool has_nodata, double nodata, int* q) {
+    return CtRaster<int>::quantise(v, s, has_nodata, nodata, q);
+  }
+};
+
+template <typename T>
+__global__ void __launch_bounds__(CT_THREADS)
+contour_quantise_kernel(const T* __restrict__ raster, const uint8_t* __restrict__ valid, int npix, int rvec, int vvec, int vec,
+                        double scale, int has_nodata, double nodata, int* __restrict__ q, uint8_t* __restrict__ ok) {
+  const int i = (blockIdx.x * CT_THREADS + threadIdx.x) * 4;
+  if (i >= npix) return;
+  typename CtRaster<T>::V v[4];
+  CtRaster<T>::load(raster, i, npix, rvec, v);
+  int use[4] = {1, 1, 1, 1};
+  if (valid) quad_load_u8(valid, i, npix, vvec, 0, use);
+  int out[4];
+  uint32_t ok4 = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    int qq = 0;
+    const bool good = i + j < npix && use[j] != 0 && CtRaster<T>::quantise(v[j], scale, has_nodata != 0, nodata, &qq);
+    out[j] = good ? qq : 0;
+    ok4 |= (uint32_t)good << (8 * j);
+  }
+  quad_store(q, i, npix, vec, out);
+  if (vec) {
+    *reinterpret_cast<uint32_t*>(ok + i) = ok4;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (i + j < npix) ok[i + j] = (uint8_t)((ok4 >> (8 * j)) & 1u);
+  }
+}
+
+__global__ void __launch_bounds__(CT_THREADS)
+contour_mark_kernel(const int* __restrict__ q, const uint8_t* __restrict__ ok, int H, int W, int npix, int nq, int nblk, int L,
+                    CtLevels lv, uint32_t* __restrict__ mask, int* __restrict__ counts) {
+  __shared__ int cnt[CT_MAX_LEVELS];
+  if (threadIdx.x < CT_MAX_LEVELS) cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const int t = blockIdx.x * CT_THREADS + threadIdx.x;
+  if (t < nq) {
+    const int i = 4 * t;
+    int qp[4], qr[4], qb[4];
+    uint32_t e = 0;                                              // bit 2 j + o: lattice edge o of pixel i + j can be a crossing
+    int y = (int)((uint32_t)i / (uint32_t)W), x = i - y * W;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int p = i + j;
+      qp[j] = qr[j] = qb[j] = 0;
+      if (p < npix && ok[p]) {
+        const bool r = x + 1 < W && ok[p + 1], b = y + 1 < H && ok[p + W];
+        qp[j] = q[p];
+        if (r) {                                                 // the cell above or the cell below emits
+          qr[j] = q[p + 1];
+          const bool up = y > 0 && ok[p - W] && ok[p - W + 1], dn = b && ok[p + W + 1];
+          if (up || dn) e |= 1u << (2 * j);
+        }
+        if (b) {                                                 // the cell to the left or the cell to the right emits
+          qb[j] = q[p + W];
+          const bool lf = x > 0 && ok[p - 1] && ok[p + W - 1], rt = r && ok[p + W + 1];
+          if (lf || rt) e |= 2u << (2 * j);
+        }
+      }
+      if (++x == W) { x = 0; ++y; }
+    }
+    for (int l = 0; l < L; ++l) {
+      const int lq = lv.q[l];
+      uint32_t m4 = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool a = qp[j] >= lq;
+        const uint32_t m = (uint32_t)(a != (qr[j] >= lq)) | ((uint32_t)(a != (qb[j] >= lq)) << 1);
+        m4 |= (m & (e >> (2 * j)) & 3u) << (8 * j);
+      }
+      mask[l * nq + t] = m4;
+      if (m4) atomicAdd(&cnt[l], __popc(m4));                    // LDS; an integer sum, whatever the order
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < L) counts[threadIdx.x * nblk + blockIdx.x] = cnt[threadIdx.x];
+}
+
+// One work-group: a[] (and b[], nullable) become their exclusive prefix sums; the totals go to the header's int32 slots. With
+// L > 0 (the first scan of a call: a[] is L levels of nblk / L counts each) the rest of the header is written too: no line yet,
+// V = E, the crossings per level, zero for the levels that are not there.
+__global__ void __launch_bounds__(CT_SCAN_THREADS)
+contour_scan_kernel(int* __restrict__ a, int* __restrict__ b, int nblk, int* __restrict__ hdr, int slot_a, int slot_b, int L) {
+  __shared__ int wa[CT_SCAN_THREADS / INSAR_WAVE], wb[CT_SCAN_THREADS / INSAR_WAVE];
+  int carry_a = 0, carry_b = 0;                                  // every thread keeps the same running totals (< 2^31)
+  for (int base = 0; base < nblk; base += CT_SCAN_THREADS) {
+    const int i = base + threadIdx.x;
+    const int va = i < nblk ? a[i] : 0, vb = (b && i < nblk) ? b[i] : 0;
+    const int ia = wave_incl_scan(va), ib = wave_incl_scan(vb);
+    if ((threadIdx.x & (INSAR_WAVE - 1)) == INSAR_WAVE - 1) { wa[threadIdx.x / INSAR_WAVE] = ia; wb[threadIdx.x / INSAR_WAVE] = ib; }
+    __syncthreads();
+    int oa = 0, ta = 0, ob = 0, tb = 0;
+#pragma unroll
+    for (int w = 0; w < CT_SCAN_THREADS / INSAR_WAVE; ++w) {
+      if (w < (int)(threadIdx.x / INSAR_WAVE)) { oa += wa[w]; ob += wb[w]; }
+      ta += wa[w]; tb += wb[w];
+    }
+    if (i < nblk) {
+      a[i] = carry_a + oa + ia - va;
+      if (b) b[i] = carry_b + ob + ib - vb;
+    }
+    carry_a += ta; carry_b += tb;
+    __syncthreads();                                             // and this work-group's stores to a[] are visible to it
+  }
+  const int t = threadIdx.x;
+  if (L > 0) {
+    if (t < CT_HDR_LEVELS) {
+      hdr[t] = (t == slot_a || t == CT_HDR_VERTS) ? carry_a : 0;
+    } else if (t < CT_HDR_LEVELS + CT_MAX_LEVELS) {
+      const int l = t - CT_HDR_LEVELS, per = nblk / L;
+      hdr[t] = l < L ? (l + 1 < L ? a[(l + 1) * per] : carry_a) - a[l * per] : 0;
+    }
+  } else if (t == slot_a) {
+    hdr[t] = carry_a;
+  } else if (b && t == slot_b) {
+    hdr[t] = carry_b;
+  }
+}
+
+__global__ void __launch_bounds__(CT_THREADS)
+contour_offsets_kernel(const uint32_t* __restrict__ mask, int nq, int nblk, const int* __restrict__ counts, int* __restrict__ off4) {
+  __shared__ int wsum[CT_THREADS / INSAR_WAVE];
+  const int l = blockIdx.y, t = blockIdx.x * CT_THREADS + threadIdx.x;
+  const uint32_t w = t < nq ? mask[l * nq + t] : 0u;
+  int total;
+  const int o = counts[l * nblk + blockIdx.x] + ct_block_excl(__popc(w), wsum, &total);
+  if (t < nq) off4[l * nq + t] = o;
+}
+
+// the compact index of crossing (p, o) of the level whose planes start at word `base`
+__device__ __forceinline__ int ct_index(const uint32_t* __restrict__ mask, const int* __restrict__ off4, int base, int p, int o) {
+  const int w = base + (p >> 2);
+  return off4[w] + __popc(mask[w] & ((1u << (8 * (p & 3) + o)) - 1u));
+}
+
+__global__ void __launch_bounds__(CT_THREADS)
+contour_link_kernel(const int* __restrict__ q, const uint8_t* __restrict__ ok, const uint32_t* __restrict__ mask,
+                    const int* __restrict__ off4, int H, int W, int npix, int nq, CtLevels lv, int cap, int* __restrict__ succ0,
+                    int* __restrict__ eid, int2* __restrict__ vert, uint8_t* __restrict__ head, int2* __restrict__ pair) {
+  const int l = blockIdx.y, t = blockIdx.x * CT_THREADS + threadIdx.x;
+  if (t >= nq) return;
+  const int base = l * nq;
+  const uint32_t m4 = mask[base + t];
+  if (!m4) return;
+  const int lq = lv.q[l];
+  int k = off4[base + t];
+  for (int bit = 0; bit < 32; bit += (bit & 1) ? 7 : 1) {        // bits 8 j and 8 j + 1
+    if (!((m4 >> bit) & 1u)) continue;
+    const int kk = k++;
+    if (kk >= cap) continue;
+    const int p = 4 * t + (bit >> 3), o = bit & 1;
+    const int y = (int)((uint32_t)p / (uint32_t)W), x = p - y * W;
+    const int qp = q[p], qn = q[p + (o ? W : 1)];
+    const bool ap = qp >= lq;
+    // the position, measured from the below end: s = floor(((q_l - q_below) * 512 + d) / (2 d)), 1 .. 255
+    const long long qa = ap ? qp : qn, qb = ap ? qn : qp, d = qa - qb;
+    long long s = (((long long)lq - qb) * 512 + d) / (2 * d);
+    s = s < 1 ? 1 : s > 255 ? 255 : s;
+    const int offp = ap ? 256 - (int)s : (int)s;
+    // travel direction d, the above end A on its right, the below end B on its left
+    int dy = 0, dx = 0, Ay = y, Ax = x, By = y, Bx = x;
+    if (o == 0) {
+      if (ap) { dy = 1; Bx = x + 1; } else { dy = -1; Ax = x + 1; }
+    } else {
+      if (ap) { dx = -1; By = y + 1; } else { dx = 1; Ay = y + 1; }
+    }
+    const int nAy = Ay + dy, nAx = Ax + dx, nBy = By + dy, nBx = Bx + dx;      // the cell ahead
+    const int pAy = Ay - dy, pAx = Ax - dx, pBy = By - dy, pBx = Bx - dx;      // the cell behind
+    const bool ahead = (unsigned)nAy < (unsigned)H && (unsigned)nAx < (unsigned)W && ok[nAy * W + nAx] && ok[nBy * W + nBx];
+    const bool behind = (unsigned)pAy < (unsigned)H && (unsigned)pAx < (unsigned)W && ok[pAy * W + pAx] && ok[pBy * W + pBx];
+    int k2 = -1;
+    if (ahead) {
+      const int qA2 = q[nAy * W + nAx], qB2 = q[nBy * W + nBx];
+      const bool aA = qA2 >= lq, aB = qB2 >= lq;
+      int uy, ux, vy, vx;
+      bool left;
+      if (!aA) left = aB && (long long)qa + qb + qA2 + qB2 >= 4 * (long long)lq;   // a saddle is joined through its centre
+      else left = aB;
+      if (!aA && !left) { uy = Ay; ux = Ax; vy = nAy; vx = nAx; }              // right
+      else if (left) { uy = By; ux = Bx; vy = nBy; vx = nBx; }                 // left
+      else { uy = nAy; ux = nAx; vy = nBy; vx = nBx; }                         // straight on
+      const int o2 = uy == vy ? 0 : 1;
+      const int p2 = min(uy, vy) * W + min(ux, vx);
+      k2 = ct_index(mask, off4, base, p2, o2);
+      if (k2 >= cap) k2 = -1;                                    // more crossings than slots: the caller reads E and stops
+    }
+    succ0[kk] = k2;
+    eid[kk] = (l * npix + p) * 2 + o;
+    vert[kk] = make_int2(256 * y + 128 + (o ? offp : 0), 256 * x + 128 + (o ? 0 : offp));
+    head[kk] = (uint8_t)!behind;
+    pair[kk] = make_int2(k2 < 0 ? kk : k2, kk);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// lead / rank: one round per launch, from one pair buffer into the other
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(CT_THREADS)
+contour_lead_round_kernel(const int2* __restrict__ in, int2* __restrict__ out, int n) {
+  const int k = blockIdx.x * CT_THREADS + threadIdx.x;
+  if (k >= n) return;
+  const int2 a = in[k];
+  const int2 b = in[a.x];
+  out[k] = make_int2(b.x, min(a.y, b.y));
+}
+
+__global__ void __launch_bounds__(CT_THREADS)
+contour_cut_kernel(const int2* __restrict__ in, const int* __restrict__ succ0, const uint8_t* __restrict__ head,
+                   int* __restrict__ lead, int* __restrict__ headof, int2* __restrict__ out, int n) {
+  const int k = blockIdx.x * CT_THREADS + threadIdx.x;
+  if (k >= n) return;
+  const int2 a = in[k];
+  const int s = succ0[k];
+  if (succ0[a.x] < 0) {                                          // the jump target is a tail: an open line
+    lead[k] = -1 - a.x;
+    if (head[k]) headof[a.x] = k;                                // one head per line: the only writer of this slot
+    out[k] = s < 0 ? make_int2(-1, 0) : make_int2(s, 1);
+  } else {
+    lead[k] = a.y;
+    out[k] = s == a.y ? make_int2(-1, 0) : make_int2(s, 1);      // the successor of a ring's last crossing is its leader
+  }
+}
+
+__global__ void __launch_bounds__(CT_THREADS)
+contour_rank_round_kernel(const int2* __restrict__ in, int2* __restrict__ out, int n) {
+  const int k = blockIdx.x * CT_THREADS + threadIdx.x;
+  if (k >= n) return;
+  int2 a = in[k];
+  if (a.x >= 0) {
+    const int2 b = in[a.x];
+    a = make_int2(b.x, a.y + b.y);
+  }
+  out[k] = a;
+}
+
+// ---------------------------------------------------------------------------------------------
+// lines: count / scan / number
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool ct_is_leader(const int* __restrict__ lead, const uint8_t* __restrict__ head, int k) {
+  return lead[k] == k || head[k];                                // a ring's smallest crossing, or the head of an open line
+}
+
+__global__ void __launch_bounds__(CT_THREADS)
+contour_line_count_kernel(const int* __restrict__ lead, const uint8_t* __restrict__ head, const int2* __restrict__ dist, int n,
+                          int* __restrict__ lcnt, int* __restrict__ llen) {
+  __shared__ int wsum[CT_THREADS / INSAR_WAVE];
+  const int k0 = blockIdx.x * CT_NB + threadIdx.x * 4;
+  int c = 0, l = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int k = k0 + j;
+    if (k < n && ct_is_leader(lead, head, k)) { ++c; l += dist[k].y + 1; }
+  }
+  int tc, tl;
+  ct_block_excl(c, wsum, &tc);
+  ct_block_excl(l, wsum, &tl);
+  if (threadIdx.x == 0) { lcnt[blockIdx.x] = tc; llen[blockIdx.x] = tl; }
+}
+
+__global__ void __launch_bounds__(CT_THREADS)
+contour_line_number_kernel(const int* __restrict__ lead, const uint8_t* __restrict__ head, const int2* __restrict__ dist,
+                           const int* __restrict__ eid, int n, int npix2, const int* __restrict__ lcnt, const int* __restrict__ llen,
+                           int2* __restrict__ info, InsarContourLine* __restrict__ lines, int max_lines) {
+  __shared__ int wsum[CT_THREADS / INSAR_WAVE];
+  const int k0 = blockIdx.x * CT_NB + threadIdx.x * 4;
+  bool is[4];
+  int len[4], c = 0, l = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int k = k0 + j;
+    is[j] = k < n && ct_is_leader(lead, head, k);
+    len[j] = is[j] ? dist[k].y + 1 : 0;
+    c += is[j]; l += len[j];
+  }
+  int tc, tl;
+  int r = lcnt[blockIdx.x] + ct_block_excl(c, wsum, &tc);
+  int st = llen[blockIdx.x] + ct_block_excl(l, wsum, &tl);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (!is[j]) continue;
+    const int k = k0 + j;
+    info[k] = make_int2(r, st);
+    if (r < max_lines) {                                         // area2 0, an empty box
+      const int e = eid[k];
+      int4* t4 = reinterpret_cast<int4*>(lines + CT_HDR + r);
+      t4[0] = make_int4(0, 0, (int)((uint32_t)e / (uint32_t)npix2), e);
+      t4[1] = make_int4(st, len[j], lead[k] >= 0, INT_MAX);
+      t4[2] = make_int4(INT_MAX, 0, 0, 0);
+    }
+    ++r; st += len[j];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// write: scatter / reduce
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(CT_THREADS)
+contour_scatter_kernel(const int* __restrict__ lead, const int* __restrict__ headof, const int2* __restrict__ dist,
+                       const int2* __restrict__ info, const int2* __restrict__ vert, int n, int* __restrict__ ometa,
+                       int2* __restrict__ vertices) {
+  const int k = blockIdx.x * CT_THREADS + threadIdx.x;
+  if (k >= n) return;
+  const int l = lead[k];
+  const int m = l >= 0 ? l : headof[-1 - l];
+  if ((unsigned)m >= (unsigned)n) return;                        // cannot happen; never leave the arrays
+  const int2 li = info[m];
+  const int pos = li.y + dist[m].y - dist[k].y;
+  if ((unsigned)pos >= (unsigned)n) return;
+  ometa[pos] = li.x;
+  vertices[pos] = vert[k];
+}
+
+__global__ void __launch_bounds__(CT_THREADS)
+contour_reduce_kernel(const int2* __restrict__ vertices, const int* __restrict__ ometa, int n,
+                      InsarContourLine* __restrict__ lines, int max_lines) {
+  const int i = blockIdx.x * CT_THREADS + threadIdx.x;
+  int key = -1, vy = 0, vx = 0;
+  long long a2 = 0;
+  if (i < n) {
+    const int r = ometa[i];
+    if (r < max_lines) {
+      const int2 v = vertices[i];
+      key = r; vy = v.x; vx = v.y;
+      const InsarContourLine* ln = lines + CT_HDR + r;           // closed and start were written by `number` and stay
+      if (ln->closed) {
+        const int nxt = (i + 1 < n && ometa[i + 1] == r) ? i + 1 : ln->start;
+        const int2 w = vertices[(unsigned)nxt < (unsigned)n ? nxt : i];
+        a2 = (long long)vx * w.x - (long long)w.y * vy;          // x_i * y_{i+1} - x_{i+1} * y_i
+      }
+    }
+  }
+  const WaveRuns runs = wave_runs(key);
+  const long long ta = wave_run_reduce(runs, a2, WaveAdd());
+  const int y0 = wave_run_reduce(runs, vy, WaveMin()), y1 = wave_run_reduce(runs, vy + 1, WaveMax());
+  const int x0 = wave_run_reduce(runs, vx, WaveMin()), x1 = wave_run_reduce(runs, vx + 1, WaveMax());
+  if (runs.head && key >= 0) {
+    InsarContourLine* r = lines + CT_HDR + key;
+    if (ta) atomicAdd(reinterpret_cast<unsigned long long*>(&r->area2), (unsigned long long)ta);
+    // the box only tightens: a stale read can cost a redundant atomic, never lose an update
+    if (y0 < __hip_atomic_load(&r->y0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&r->y0, y0);
+    if (x0 < __hip_atomic_load(&r->x0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&r->x0, x0);
+    if (y1 > __hip_atomic_load(&r->y1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&r->y1, y1);
+    if (x1 > __hip_atomic_load(&r->x1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&r->x1, x1);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side: scratch layout and the entry points
+// ---------------------------------------------------------------------------------------------
+struct CtLayout {
+  int npix, nq, nblk, L, cap, eblk;
+  int64_t q, ok, mask, off4, counts, succ0, eid, vert, head, lead, headof, p0, p1, ometa, lcnt, llen, bytes;
+};
+
+static int contour_layout(const char* who, int32_t H, int32_t W, int32_t n_levels, int32_t max_vertices, CtLayout* L) {
+  if (H < 1 || W < 1 || H > CT_MAX_SIDE || W > CT_MAX_SIDE) INSAR_FAIL(INSAR_E_SHAPE, "%s: raster %d x %d: H, W in 1 .. 2^22", who, H, W);
+  if (n_levels < 1 || n_levels > CT_MAX_LEVELS) INSAR_FAIL(INSAR_E_SHAPE, "%s: n_levels %d outside 1 .. %d", who, n_levels, CT_MAX_LEVELS);
+  const int64_t npix = (int64_t)H * W;
+  if (npix * n_levels >= ((int64_t)1 << 30))
+    INSAR_FAIL(INSAR_E_SHAPE, "%s: n_levels * H * W = %d * %d * %d is 2^30 or more", who, n_levels, H, W);
+  if (max_vertices < 1 || max_vertices > CT_MAX_CROSSINGS)
+    INSAR_FAIL(INSAR_E_SHAPE, "%s: max_vertices %d outside 1 .. 2^30", who, max_vertices);
+  L->npix = (int)npix;
+  L->nq = (int)((npix + 3) / 4);
+  L->nblk = (L->nq + CT_THREADS - 1) / CT_THREADS;
+  L->L = n_levels;
+  L->cap = max_vertices;
+  L->eblk = (max_vertices + CT_NB - 1) / CT_NB;
+  int64_t at = 0;
+  auto take = [&at](int64_t bytes) { const int64_t o = at; at += (bytes + 15) & ~(int64_t)15; return o; };
+  const int64_t cap = max_vertices, words = (int64_t)n_levels * L->nq;
+  L->q = take(npix * 4);       L->ok = take(npix);         L->mask = take(words * 4);   L->off4 = take(words * 4);
+  L->counts = take((int64_t)n_levels * L->nblk * 4);
+  L->succ0 = take(cap * 4);    L->eid = take(cap * 4);     L->vert = take(cap * 8);     L->head = take(cap);
+  L->lead = take(cap * 4);     L->headof = take(cap * 4);  L->p0 = take(cap * 8);       L->p1 = take(cap * 8);
+  L->ometa = take(cap * 4);
+  L->lcnt = take((int64_t)L->eblk * 4);  L->llen = take((int64_t)L->eblk * 4);
+  L->bytes = at;
+  return INSAR_OK;
+}
+static int contour_check_buf(const char* who, const void* p, const char* what) {
+  if (!p) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer (%s)", who, what);
+  if (!insar_aligned16(p)) INSAR_FAIL(INSAR_E_ALIGN, "%s: %s not 16-byte aligned", who, what);
+  return INSAR_OK;
+}
+static int contour_check_lines(const char* who, const void* table, int32_t max_lines) {
+  if (max_lines < 1 || max_lines > CT_MAX_CROSSINGS) INSAR_FAIL(INSAR_E_SHAPE, "%s: max_lines %d outside 1 .. 2^30", who, max_lines);
+  return contour_check_buf(who, table, "table");
+}
+static int contour_check_count(const char* who, int32_t n, const CtLayout& L) {
+  if (n < 0 || n > L.cap) INSAR_FAIL(INSAR_E_SHAPE, "%s: n_crossings %d outside 0 .. max_vertices=%d", who, n, L.cap);
+  return INSAR_OK;
+}
+static inline int contour_rounds(int n) {                        // ceil(log2 n)
+  int r = 0;
+  while (((int64_t)1 << r) < n) ++r;
+  return r;
+}
+template <typename T>
+static inline T* ct_at(void* scratch, int64_t off) { return reinterpret_cast<T*>((char*)scratch + off); }
+static inline unsigned ct_grid(int n, int per) { return (unsigned)((n + per - 1) / per); }
+
+extern "C" int insar_contour_scratch_bytes(int32_t H, int32_t W, int32_t n_levels, int32_t max_lines, int32_t max_vertices,
+                                           int64_t* scratch_bytes, int64_t* table_bytes) {
+  const char* who = "insar_contour_scratch_bytes";
+  if (!scratch_bytes || !table_bytes) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer", who);
+  CtLayout L;
+  if (int rc = contour_layout(who, H, W, n_levels, max_vertices, &L)) return rc;
+  if (max_lines < 1 || max_lines > CT_MAX_CROSSINGS) INSAR_FAIL(INSAR_E_SHAPE, "%s: max_lines %d outside 1 .. 2^30", who, max_lines);
+  *scratch_bytes = L.bytes;
+  *table_bytes = (int64_t)sizeof(InsarContourLine) * ((int64_t)max_lines + CT_HDR);
+  return INSAR_OK;
+}
+
+extern "C" int insar_contour_launches(int32_t n_crossings) {
+  return n_crossings < 1 ? 5 : 11 + 2 * contour_rounds(n_crossings);
+}
+
+template <typename T>
+static void contour_launch_quantise(const void* raster, const uint8_t* valid, const CtLayout& L, double scale, int32_t has_nodata,
+                                    double nodata, void* scratch, hipStream_t s) {
+  const int vec = L.npix % 4 == 0;
+  const int rvec = vec && insar_aligned16(raster), vvec = vec && valid && ((((uintptr_t)valid) & 3u) == 0);
+  hipLaunchKernelGGL(contour_quantise_kernel<T>, dim3(ct_grid(L.nq, CT_THREADS)), dim3(CT_THREADS), 0, s, (const T*)raster, valid,
+                     L.npix, rvec, vvec, vec, scale, has_nodata, nodata, ct_at<int>(scratch, L.q), ct_at<uint8_t>(scratch, L.ok));
+}
+
+extern "C" int insar_contour_edges(const void* raster, int32_t elem_type, int32_t H, int32_t W, double scale, int32_t has_nodata,
+                                   double nodata, const uint8_t* valid, const int32_t* levels_q, int32_t n_levels,
+                                   int32_t max_vertices, void* scratch, void* table, void* stream) {
+  const char* who = "insar_contour_edges";
+  if (!raster || !levels_q) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer", who);
+  CtLayout L;
+  if (int rc = contour_layout(who, H, W, n_levels, max_vertices, &L)) return rc;
+  if (elem_type != INSAR_ZONAL_F32 && elem_type != INSAR_ZONAL_U8 && elem_type != INSAR_ZONAL_I32)
+    INSAR_FAIL(INSAR_E_DTYPE, "%s: elem_type %d (INSAR_ZONAL_F32, _U8 or _I32)", who, elem_type);
+  if (!(scale > 0.0) || !(scale <= 1.7976931348623157e308)) INSAR_FAIL(INSAR_E_ARG, "%s: scale must be positive and finite", who);
+  if (has_nodata && nodata != nodata) INSAR_FAIL(INSAR_E_ARG, "%s: nodata is NaN", who);
+  CtLevels lv;
+  for (int l = 0; l < CT_MAX_LEVELS; ++l) lv.q[l] = l < n_levels ? levels_q[l] : INT_MAX;
+  for (int l = 1; l < n_levels; ++l)
+    if (lv.q[l] <= lv.q[l - 1]) INSAR_FAIL(INSAR_E_ARG, "%s: levels_q[%d] = %d is not above levels_q[%d] = %d", who, l, lv.q[l], l - 1, lv.q[l - 1]);
+  if (int rc = contour_check_buf(who, scratch, "scratch")) return rc;
+  if (int rc = contour_check_buf(who, table, "table")) return rc;
+  if (elem_type != INSAR_ZONAL_U8 && (((uintptr_t)raster) & 3u)) INSAR_FAIL(INSAR_E_ALIGN, "%s: raster not 4-byte aligned", who);
+  hipStream_t s = (hipStream_t)stream;
+  if (elem_type == INSAR_ZONAL_F32) contour_launch_quantise<float>(raster, valid, L, scale, has_nodata, nodata, scratch, s);
+  else if (elem_type == INSAR_ZONAL_I32) contour_launch_quantise<int>(raster, valid, L, scale, has_nodata, nodata, scratch, s);
+  else contour_launch_quantise<uint8_t>(raster, valid, L, scale, has_nodata, nodata, scratch, s);
+  INSAR_CHECK_LAUNCH(who);
+  const int* q = ct_at<int>(scratch, L.q);
+  const uint8_t* ok = ct_at<uint8_t>(scratch, L.ok);
+  uint32_t* mask = ct_at<uint32_t>(scratch, L.mask);
+  int *off4 = ct_at<int>(scratch, L.off4), *counts = ct_at<int>(scratch, L.counts);
+  hipLaunchKernelGGL(contour_mark_kernel, dim3((unsigned)L.nblk), dim3(CT_THREADS), 0, s, q, ok, H, W, L.npix, L.nq, L.nblk, L.L, lv,
+                     mask, counts);
+  INSAR_CHECK_LAUNCH(who);
+  hipLaunchKernelGGL(contour_scan_kernel, dim3(1), dim3(CT_SCAN_THREADS), 0, s, counts, (int*)nullptr, L.L * L.nblk, (int*)table,
+                     CT_HDR_CROSSINGS, -1, L.L);
+  INSAR_CHECK_LAUNCH(who);
+  hipLaunchKernelGGL(contour_offsets_kernel, dim3((unsigned)L.nblk, (unsigned)L.L), dim3(CT_THREADS), 0, s, (const uint32_t*)mask,
+                     L.nq, L.nblk, (const int*)counts, off4);
+  INSAR_CHECK_LAUNCH(who);
+  hipLaunchKernelGGL(contour_link_kernel, dim3((unsigned)L.nblk, (unsigned)L.L), dim3(CT_THREADS), 0, s, q, ok, (const uint32_t*)mask,
+                     (const int*)off4, H, W, L.npix, L.nq, lv, L.cap, ct_at<int>(scratch, L.succ0), ct_at<int>(scratch, L.eid),
+                     ct_at<int2>(scratch, L.vert), ct_at<uint8_t>(scratch, L.head), ct_at<int2>(scratch, L.p0));
+  INSAR_CHECK_LAUNCH(who);
+  return INSAR_OK;
+}
+
+// The pair buffers: `link` fills p0; round r of `lead` reads p[r & 1] and writes the other; `cut` reads p[R & 1] and writes
+// the other; round r of `rank` goes on from there, so the final distances are in p1 whatever R is, and p0 is free for `lines`.
+extern "C" int insar_contour_lead(int32_t H, int32_t W, int32_t n_levels, int32_t n_crossings, int32_t max_vertices, void* scratch,
+                                  void* stream) {
+  const char* who = "insar_contour_lead";
+  CtLayout L;
+  if (int rc = contour_layout(who, H, W, n_levels, max_vertices, &L)) return rc;
+  if (int rc = contour_check_count(who, n_crossings, L)) return rc;
+  if (int rc = contour_check_buf(who, scratch, "scratch")) return rc;
+  if (n_crossings == 0) return INSAR_OK;
+  int2* p[2] = {ct_at<int2>(scratch, L.p0), ct_at<int2>(scratch, L.p1)};
+  const int rounds = contour_rounds(n_crossings);
+  for (int r = 0; r < rounds; ++r) {
+    hipLaunchKernelGGL(contour_lead_round_kernel, dim3(ct_grid(n_crossings, CT_THREADS)), dim3(CT_THREADS), 0, (hipStream_t)stream,
+                       (const int2*)p[r & 1], p[(r & 1) ^ 1], n_crossings);
+    INSAR_CHECK_LAUNCH(who);
+  }
+  return INSAR_OK;
+}
+
+extern "C" int insar_contour_rank(int32_t H, int32_t W, int32_t n_levels, int32_t n_crossings, int32_t max_vertices, void* scratch,
+                                  void* stream) {
+  const char* who = "insar_contour_rank";
+  CtLayout L;
+  if (int rc = contour_layout(who, H, W, n_levels, max_vertices, &L)) return rc;
+  if (int rc = contour_check_count(who, n_crossings, L)) return rc;
+  if (int rc = contour_check_buf(who, scratch, "scratch")) return rc;
+  if (n_crossings == 0) return INSAR_OK;
+  int2* p[2] = {ct_at<int2>(scratch, L.p0), ct_at<int2>(scratch, L.p1)};
+  const int rounds = contour_rounds(n_crossings);
+  int cur = rounds & 1;
+  const unsigned grid = ct_grid(n_crossings, CT_THREADS);
+  hipLaunchKernelGGL(contour_cut_kernel, dim3(grid), dim3(CT_THREADS), 0, (hipStream_t)stream, (const int2*)p[cur],
+                     (const int*)ct_at<int>(scratch, L.succ0), (const uint8_t*)ct_at<uint8_t>(scratch, L.head),
+                     ct_at<int>(scratch, L.lead), ct_at<int>(scratch, L.headof), p[cur ^ 1], n_crossings);
+  INSAR_CHECK_LAUNCH(who);
+  cur ^= 1;
+  for (int r = 0; r < rounds; ++r, cur ^= 1) {
+    hipLaunchKernelGGL(contour_rank_round_kernel, dim3(grid), dim3(CT_THREADS), 0, (hipStream_t)stream, (const int2*)p[cur],
+                       p[cur ^ 1], n_crossings);
+    INSAR_CHECK_LAUNCH(who);
+  }
+  return INSAR_OK;
+}
+
+extern "C" int insar_contour_lines(int32_t H, int32_t W, int32_t n_levels, int32_t n_crossings, int32_t max_lines,
+                                   int32_t max_vertices, void* scratch, void* table, void* stream) {
+  const char* who = "insar_contour_lines";
+  CtLayout L;
+  if (int rc = contour_layout(who, H, W, n_levels, max_vertices, &L)) return rc;
+  if (int rc = contour_check_count(who, n_crossings, L)) return rc;
+  if (int rc = contour_check_lines(who, table, max_lines)) return rc;
+  if (int rc = contour_check_buf(who, scratch, "scratch")) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int nblk = (int)ct_grid(n_crossings, CT_NB);
+  int *lead = ct_at<int>(scratch, L.lead), *lcnt = ct_at<int>(scratch, L.lcnt), *llen = ct_at<int>(scratch, L.llen);
+  const uint8_t* head = ct_at<uint8_t>(scratch, L.head);
+  const int2* dist = ct_at<int2>(scratch, L.p1);
+  if (nblk > 0) {
+    hipLaunchKernelGGL(contour_line_count_kernel, dim3((unsigned)nblk), dim3(CT_THREADS), 0, s, (const int*)lead, head, dist,
+                       n_crossings, lcnt, llen);
+    INSAR_CHECK_LAUNCH(who);
+  }
+  hipLaunchKernelGGL(contour_scan_kernel, dim3(1), dim3(CT_SCAN_THREADS), 0, s, lcnt, llen, nblk, (int*)table, CT_HDR_LINES, -1, 0);
+  INSAR_CHECK_LAUNCH(who);
+  if (nblk > 0) {
+    hipLaunchKernelGGL(contour_line_number_kernel, dim3((unsigned)nblk), dim3(CT_THREADS), 0, s, (const int*)lead, head, dist,
+                       (const int*)ct_at<int>(scratch, L.eid), n_crossings, 2 * L.npix, (const int*)lcnt, (const int*)llen,
+                       ct_at<int2>(scratch, L.p0), (InsarContourLine*)table, max_lines);
+    INSAR_CHECK_LAUNCH(who);
+  }
+  return INSAR_OK;
+}
+
+extern "C" int insar_contour_write(int32_t H, int32_t W, int32_t n_levels, int32_t n_crossings, int32_t max_lines,
+                                   int32_t max_vertices, void* scratch, void* table, int32_t* vertices, void* stream) {
+  const char* who = "insar_contour_write";
+  CtLayout L;
+  if (int rc = contour_layout(who, H, W, n_levels, max_vertices, &L)) return rc;
+  if (int rc = contour_check_count(who, n_crossings, L)) return rc;
+  if (int rc = contour_check_lines(who, table, max_lines)) return rc;
+  if (!vertices) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer (vertices)", who);
+  if (((uintptr_t)vertices) & 7u) INSAR_FAIL(INSAR_E_ALIGN, "%s: vertices not 8-byte aligned", who);
+  if (int rc = contour_check_buf(who, scratch, "scratch")) return rc;
+  if (n_crossings == 0) return INSAR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned grid = ct_grid(n_crossings, CT_THREADS);
+  int* ometa = ct_at<int>(scratch, L.ometa);
+  hipLaunchKernelGGL(contour_scatter_kernel, dim3(grid), dim3(CT_THREADS), 0, s, (const int*)ct_at<int>(scratch, L.lead),
+                     (const int*)ct_at<int>(scratch, L.headof), (const int2*)ct_at<int2>(scratch, L.p1),
+                     (const int2*)ct_at<int2>(scratch, L.p0), (const int2*)ct_at<int2>(scratch, L.vert), n_crossings, ometa,
+                     reinterpret_cast<int2*>(vertices));
+  INSAR_CHECK_LAUNCH(who);
+  hipLaunchKernelGGL(contour_reduce_kernel, dim3(grid), dim3(CT_THREADS), 0, s, (const int2*)reinterpret_cast<int2*>(vertices),
+                     (const int*)ometa, n_crossings, (InsarContourLine*)table, max_lines);
+  INSAR_CHECK_LAUNCH(who);
+  return INSAR_OK;
+}

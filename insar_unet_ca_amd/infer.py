@@ -446,7 +446,7 @@ class ScenePredictor:
     def detect(self, scene, return_prob: bool = False, outlines: bool = False, skeletons: bool = False,
                max_iterations: int = 32, measure: Optional[dict] = None, simplify: Optional[float] = None, split=None,
                sieve=None, valid=None, nodata=None, min_valid: int = 1, fill: float = 0.0, norm=None, hysteresis=None,
-               **region_kwargs) -> dict:
+               contours: Optional[dict] = None, **region_kwargs) -> dict:
         """`predict(scene)` followed by `label_regions(out["mask"], out["conf"], **region_kwargs)`: the predict outputs
         unchanged, plus "labels", "regions", "count" and the cleaned class map under "mask_clean". With `outlines=True` also
         "outlines" = `outlines.region_outlines(out["labels"])` with the connectivity the regions were labelled with, and
@@ -477,13 +477,26 @@ class ScenePredictor:
         peak_x) and "count" come from it, "mask_clean" is its mask, "conf_hysteresis" its candidate plane,
         "hysteresis_candidates" the components before the seed rule, and "mask" and "conf" stay the raw prediction. `min_conf`
         and `sieve` are refused next to it: the two thresholds replace the one, and a sieved arg-max map and a low-threshold
-        map are different maps. With None nothing of it runs."""
+        map are different maps. With None nothing of it runs. With `contours` = a dict of `contours.contour_lines` keywords
+        (`levels` is needed) plus `raster` (None) and `plane` (1), also "contours" = `contour_lines(raster, levels, ...)`:
+        `raster` None contours probability plane `plane` (`predict` then computes the probabilities; "prob" is in the result
+        only if `return_prob`), else a float32, uint8 or int32 [H, W] raster on the scene grid, numpy or tensor (a host raster
+        is copied once); the "valid" plane of a masked predict is handed on, so that lines end beside no-data. With None
+        nothing of it runs."""
         if measure is not None and not isinstance(measure, dict):
             raise InsarError(f"measure: a dict of name -> raster or (raster, kwargs), got {type(measure).__name__}")
         if hysteresis is not None:
             hyst_kw = self._hysteresis_kwargs(hysteresis, sieve, region_kwargs)
-        out = dict(self.predict(scene, return_prob=return_prob or hysteresis is not None, valid=valid, nodata=nodata,
+        need_prob = hysteresis is not None
+        if contours is not None:
+            contour_kw = self._contour_kwargs(contours)
+            need_prob = need_prob or contour_kw["raster"] is None
+        out = dict(self.predict(scene, return_prob=return_prob or need_prob, valid=valid, nodata=nodata,
                                 min_valid=min_valid, fill=fill, norm=norm))
+        if contours is not None:
+            self._contour(out, contour_kw)                                   # before `_grow` takes "prob" out
+            if need_prob and hysteresis is None and not return_prob:
+                del out["prob"]
         H, W = out["mask"].shape
         max_regions = region_kwargs.get("max_regions", DEFAULT_MAX_REGIONS)
         if hysteresis is not None:
@@ -504,6 +517,43 @@ class ScenePredictor:
         if measure is not None:
             self._measure(out, scene, measure, max_regions)
         return out
+
+    @staticmethod
+    def _contour_kwargs(contours) -> dict:
+        """The keywords of `contour_lines` plus "raster" and "plane" from detect's `contours`; refused before `predict` runs."""
+        if not isinstance(contours, dict) or "levels" not in contours:
+            raise InsarError(f"contours: a dict of contour_lines keywords with 'levels' (and 'raster', 'plane'), got {contours!r}")
+        kw = dict(contours)
+        for name in ("valid", "scratch"):
+            if name in kw:
+                raise InsarError(f"contours: {name!r} is detect's to give")
+        kw.setdefault("raster", None)
+        kw.setdefault("plane", 1)
+        return kw
+
+    def _contour(self, out: dict, kw: dict) -> None:
+        """`contour_lines` of a probability plane or of the caller's raster, with the valid plane of a masked predict."""
+        from .contours import DEFAULT_MAX_LINES, DEFAULT_MAX_VERTICES, ContourScratch, contour_lines
+        kw = dict(kw)
+        raster, plane = kw.pop("raster"), kw.pop("plane")
+        dev = out["mask"].device
+        if raster is None:
+            K = out["prob"].shape[0]
+            plane = _scene.check_int("contours", "plane", plane, 0, K - 1, integral_floats=False)
+            raster = out["prob"][plane]
+        else:
+            if isinstance(raster, np.ndarray):
+                raster = torch.from_numpy(np.ascontiguousarray(raster))
+            if not isinstance(raster, torch.Tensor):
+                raise InsarError(f"contours: raster must be a numpy array or a torch tensor, got {type(raster).__name__}")
+            raster = raster.detach().to(dev).contiguous()
+        levels = kw.pop("levels")
+        n_levels = len(levels) if isinstance(levels, (list, tuple, np.ndarray)) else 1
+        scratch = None
+        if raster.dim() == 2:
+            scratch = self._scratch(ContourScratch, dev, raster.shape[0], raster.shape[1], n_levels,
+                                    kw.get("max_lines", DEFAULT_MAX_LINES), kw.get("max_vertices", DEFAULT_MAX_VERTICES))
+        out["contours"] = contour_lines(raster, levels, valid=out.get("valid"), scratch=scratch, **kw)
 
     @staticmethod
     def _hysteresis_kwargs(hysteresis, sieve, region_kwargs: dict) -> dict:
@@ -730,8 +780,8 @@ def predict_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw
 
 def detect_scene(model: torch.nn.Module, scene, return_prob: bool = False, **kw) -> dict:
     """One-shot ScenePredictor(model, ...).detect(scene, return_prob, ...): tile / overlap / batch / num_classes / tta go to
-    the predictor, `outlines`, `simplify`, `skeletons`, `max_iterations`, `measure`, `split`, `sieve` and `hysteresis` to `detect`, every other
-    keyword to `label_regions`."""
+    the predictor, `outlines`, `simplify`, `skeletons`, `max_iterations`, `measure`, `split`, `sieve`, `hysteresis` and `contours` to
+    `detect`, every other keyword to `label_regions`."""
     pred_kw = {k: kw.pop(k) for k in ("tile", "overlap", "batch", "num_classes", "tta") if k in kw}
     return ScenePredictor(model, **pred_kw).detect(scene, return_prob=return_prob, **kw)
 
