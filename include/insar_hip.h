@@ -1097,6 +1097,49 @@ int insar_zonal_accumulate(const int32_t* labels, const void* raster, int32_t el
                            double scale, int32_t has_nodata, double nodata, int32_t bins, int64_t q_lo, int64_t q_hi,
                            int32_t max_regions, void* table, void* stream);
 
+/* ---- filtering rasters: NaN-aware smoothing, rank filters and slope (build-side addition; the reference has no
+ * post-processing): csrc/focal.hip -------------------------------------------------------------------------------------------
+ * Neighbourhood operations on a raster [planes][H][W] (row-major; INSAR_ZONAL_F32 / _U8 / _I32; H, W >= 1, H * W < 2^31, 1 <=
+ * planes <= 65535; the planes are independent and go on the grid's z dimension). A pixel is VALID iff it lies inside the raster,
+ * valid[y][x] != 0 (valid: uint8 [H][W], shared by the planes, nullable), it does not equal `nodata` in the raster's own type
+ * (has_nodata; NaN is refused) and, in a float32 raster, it is finite. Outside the raster is invalid: there is no padding mode.
+ * keep_invalid != 0: an output whose CENTRE pixel is invalid is invalid; 0: it is filled from its neighbours. An invalid output
+ * is the quiet NaN 0x7fc00000 in float32 and `fill` in integer outputs (uint8: 0..255). out: the raster's layout (gradient:
+ * float32 [planes][2][H][W]), never the raster itself; out_valid (nullable): uint8 [planes][H][W], 1 where the output is valid.
+ * One launch per call on `stream`, no atomics, no work-group waits on another, nothing read back and no copy: the taps and
+ * scalars are kernel arguments. Every output is bitwise defined (tests/focal_ref.py restates all of it). Every argument is
+ * checked before the device is touched (INSAR_E_ARG, INSAR_E_SHAPE, INSAR_E_DTYPE, INSAR_E_ALIGN). */
+enum { INSAR_FOCAL_MIN = 0, INSAR_FOCAL_MAX = 1, INSAR_FOCAL_MEDIAN = 2 };
+/* host only: the rows and columns of outputs one work-group of the smoothing and min / max kernels computes at `radius` 0..15 */
+int insar_focal_tile(int32_t radius, int32_t* rows, int32_t* cols);
+/* Separable normalised convolution in exact integers. taps: HOST int32 [2 radius + 1], each >= 0, 1 <= sum S <= 4096, 0 <= radius
+ * <= 15; tap i multiplies the pixel at offset i - radius (correlation, nothing is flipped); the same taps serve rows and columns.
+ *   q:      integer rasters q = v; float32 q = rint(clamp((double)v * scale, +-(2^31 - 1))) to nearest even, the rule of
+ *           insar_zonal_accumulate; m = 1 for a valid pixel, else 0.
+ *   rows:   A[y][x] = sum_i k[i] m[y][x+i] q[y][x+i], Wr[y][x] = sum_i k[i] m[y][x+i]
+ *   cols:   N = sum_j k[j] A[y+j][x], D = sum_j k[j] Wr[y+j][x]            (int64: |A| < 2^43, |N| < 2^55, D <= S^2)
+ *   valid:  D >= threshold (1 <= threshold <= S^2; the host's max(1, ceil(min_coverage S^2))), and the keep_invalid rule
+ *   value:  q_out = floor((2 N + D) / (2 D)), a floor division: ties go towards +infinity for both signs. float32 output
+ *           (float)((double)q_out / scale); integer outputs hold q_out (a convex combination: in range). */
+int insar_focal_smooth(const void* raster, int32_t elem_type, int32_t planes, int32_t H, int32_t W, const int32_t* taps, int32_t radius,
+                       double scale, int32_t has_nodata, double nodata, const uint8_t* valid, int64_t threshold, int32_t keep_invalid,
+                       int32_t fill, void* out, uint8_t* out_valid, void* stream);
+/* op (INSAR_FOCAL_*) over the n valid pixels of the (2 radius + 1)^2 window, on the raw values. float32 values are ordered by the
+ * key u = bits; u & 2^31 ? ~u : u ^ 2^31 (-0.0 directly below 0.0) and the output is the exact bit pattern of the chosen pixel;
+ * integers use their own order. min, max: 1 <= radius <= 15. median: 1 <= radius <= 3, the LOWER median, element (n - 1) / 2 of
+ * the sorted values; nothing is averaged. The output is valid iff n >= min_count (1 .. (2 radius + 1)^2), and the keep_invalid rule. */
+int insar_focal_rank(const void* raster, int32_t elem_type, int32_t planes, int32_t H, int32_t W, int32_t op, int32_t radius,
+                     int32_t has_nodata, double nodata, const uint8_t* valid, int32_t min_count, int32_t keep_invalid, int32_t fill,
+                     void* out, uint8_t* out_valid, void* stream);
+/* Slope of a float32 raster: out[p][0] = gy, out[p][1] = gx, float32 operations in this order, no fused multiply-add. Along x,
+ * with v- , v0, v+ the pixels at x - 1, x, x + 1 (and unless keep_invalid refuses an invalid centre): both neighbours valid
+ * (v+ - v-) * hx2; else centre and x + 1 valid (v+ - v0) * hx1; else centre and x - 1 valid (v0 - v-) * hx1; else NaN. y likewise
+ * with hy1, hy2. h1 = (float)(1 / spacing), h2 = (float)(1 / (2 spacing)), computed by the host: positive and finite. out_valid
+ * marks the pixels where BOTH components are valid. */
+int insar_focal_gradient(const float* raster, int32_t planes, int32_t H, int32_t W, float hy1, float hy2, float hx1, float hx2,
+                         int32_t has_nodata, double nodata, const uint8_t* valid, int32_t keep_invalid, float* out, uint8_t* out_valid,
+                         void* stream);
+
 /* ---- distance transform (build-side addition; the reference has no post-processing): csrc/distance.hip --------------------
  * The exact squared Euclidean distance from every pixel of a map m [B][H][W] (row-major; uint8 with INSAR_DIST_U8, int32 with
  * INSAR_DIST_I32; B, H, W >= 1, H, W <= 32767, B * H * W < 2^31, no tile-multiple requirement) to the nearest SITE of the same

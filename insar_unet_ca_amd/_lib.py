@@ -25,6 +25,7 @@ RASTER_U8, RASTER_I32 = 0, 1
 ZONAL_F32, ZONAL_U8, ZONAL_I32 = 0, 1, 2
 WARP_U8, WARP_I32, WARP_F32 = 0, 1, 2
 WARP_NEAREST, WARP_BILINEAR = 0, 1
+FOCAL_MIN, FOCAL_MAX, FOCAL_MEDIAN = 0, 1, 2
 IGEMM_OOB_ZERO = 1
 IGEMM_PINGPONG = 2
 
@@ -274,6 +275,10 @@ _SIGNATURES = {
     "insar_zonal_scratch_bytes": [_I, _I, _I, _P],
     "insar_zonal_clear": [_P, _I, _I, _I, _P],
     "insar_zonal_accumulate": [_P, _P, _I, _I, _I, _I, C.c_double, _I, C.c_double, _I, _L, _L, _I, _P, _P],
+    "insar_focal_tile": [_I, _P, _P],
+    "insar_focal_smooth": [_P, _I, _I, _I, _I, _P, _I, C.c_double, _I, C.c_double, _P, _L, _I, _I, _P, _P, _P],
+    "insar_focal_rank": [_P, _I, _I, _I, _I, _I, _I, _I, C.c_double, _P, _I, _I, _I, _P, _P, _P],
+    "insar_focal_gradient": [_P, _I, _I, _I, _F, _F, _F, _F, _I, C.c_double, _P, _I, _P, _P, _P],
     "insar_dist_scratch_bytes": [_I, _I, _I, _P],
     "insar_dist_transform": [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "insar_dist_boundary_counts": [_P, _P, _P, _P, _I, _I, _L, _I, _I, _P, _P],

@@ -481,8 +481,10 @@ class ScenePredictor:
         (`levels` is needed) plus `raster` (None) and `plane` (1), also "contours" = `contour_lines(raster, levels, ...)`:
         `raster` None contours probability plane `plane` (`predict` then computes the probabilities; "prob" is in the result
         only if `return_prob`), else a float32, uint8 or int32 [H, W] raster on the scene grid, numpy or tensor (a host raster
-        is copied once); the "valid" plane of a masked predict is handed on, so that lines end beside no-data. With None
-        nothing of it runs."""
+        is copied once); the "valid" plane of a masked predict is handed on, so that lines end beside no-data. With `smooth` =
+        a Gaussian sigma in pixels (0 < sigma <= 5) in that dict the contoured raster first goes through
+        `focal.smooth_raster(raster, gaussian_taps(sigma), valid=, return_valid=True)` and that valid plane goes to
+        `contour_lines`; without it not one operation changes. With None nothing of it runs."""
         if measure is not None and not isinstance(measure, dict):
             raise InsarError(f"measure: a dict of name -> raster or (raster, kwargs), got {type(measure).__name__}")
         if hysteresis is not None:
@@ -529,13 +531,18 @@ class ScenePredictor:
                 raise InsarError(f"contours: {name!r} is detect's to give")
         kw.setdefault("raster", None)
         kw.setdefault("plane", 1)
+        if kw.get("smooth") is not None:
+            sigma = kw["smooth"]
+            if (isinstance(sigma, bool) or not isinstance(sigma, (int, float, np.integer, np.floating))
+                    or not 0 < sigma <= 5):               # NaN compares false
+                raise InsarError(f"contours: smooth={sigma!r}: a Gaussian sigma in pixels, 0 < sigma <= 5")
         return kw
 
     def _contour(self, out: dict, kw: dict) -> None:
         """`contour_lines` of a probability plane or of the caller's raster, with the valid plane of a masked predict."""
         from .contours import DEFAULT_MAX_LINES, DEFAULT_MAX_VERTICES, ContourScratch, contour_lines
         kw = dict(kw)
-        raster, plane = kw.pop("raster"), kw.pop("plane")
+        raster, plane, sigma = kw.pop("raster"), kw.pop("plane"), kw.pop("smooth", None)
         dev = out["mask"].device
         if raster is None:
             K = out["prob"].shape[0]
@@ -553,7 +560,11 @@ class ScenePredictor:
         if raster.dim() == 2:
             scratch = self._scratch(ContourScratch, dev, raster.shape[0], raster.shape[1], n_levels,
                                     kw.get("max_lines", DEFAULT_MAX_LINES), kw.get("max_vertices", DEFAULT_MAX_VERTICES))
-        out["contours"] = contour_lines(raster, levels, valid=out.get("valid"), scratch=scratch, **kw)
+        valid = out.get("valid")
+        if sigma is not None:                                                # the valid plane of the smoothing ends the lines
+            from .focal import gaussian_taps, smooth_raster
+            raster, valid = smooth_raster(raster, gaussian_taps(float(sigma)), valid=valid, return_valid=True)
+        out["contours"] = contour_lines(raster, levels, valid=valid, scratch=scratch, **kw)
 
     @staticmethod
     def _hysteresis_kwargs(hysteresis, sieve, region_kwargs: dict) -> dict:
