@@ -987,6 +987,70 @@ int insar_simplify_finish(const int32_t* vertices, int32_t n_vertices, const voi
                           int32_t max_vertices, int32_t max_rings, void* scratch, void* table, int32_t* out_vertices,
                           int32_t* out_kept, void* stream);
 
+/* ---- contour simplification (build-side addition; the reference has no post-processing): csrc/contour_simplify.hip ----------
+ * Douglas-Peucker over the polylines of the contour lines, open lines and closed rings, in exact integers. A POSITION is an
+ * index into the input vertex array; the kept set is a set of positions; every line is simplified on its own.
+ *   input:     vertices int32 [n_vertices][2] as (Y, X) in 1/256 pixel, line after line, 0 <= Y, X <= 2^30 (the caller's
+ *              promise: every bound below rests on it, and no kernel leaves its buffers if it is broken); `lines`:
+ *              InsarContourLine [1 + n_lines] on the device (record 0 is a header and is not read; of a line start, count and
+ *              closed are read, level and leader are copied), the lines contiguous and in order: start[0] = 0, start[r + 1] =
+ *              start[r] + count[r], the counts adding up to n_vertices; an open line has 2 vertices or more, a ring 3 or more.
+ *   tolerance: eps = the tolerance in 1/256 pixel (0 <= eps <= 262144 = 1024 pixels), eps2 = eps^2 <= 2^36.
+ *   seeds:     an open line keeps its first and its last position. A ring keeps two: seed 1 is the position with the
+ *              lexicographically smallest (Y, X), seed 2 the position with the largest squared distance from it, ties to the
+ *              smallest (Y, X); both break a tie of equal coordinates by the smallest position (the contour lines never repeat a
+ *              coordinate within a line; the rule makes the function total on other input). A ring whose vertices all coincide
+ *              has one seed.
+ *   round:     a segment (a, b) is a pair of consecutive kept positions of a line, cyclically in a ring (a ring with two seeds
+ *              has two segments, one with one seed has the segment (a, a) of every other position). Among the positions strictly
+ *              between them the winner has the largest |cross|, cross = (b - a) x (p - a) in int64, ties to the smallest
+ *              (Y, X), then to the smallest position: one winner per segment. It is kept iff cross^2 > eps2 |b - a|^2, compared
+ *              exactly. Where a and b carry the same coordinates, d^2 = |p - a|^2 takes the place of |cross| and the test is
+ *              d^2 > eps2. Round r is recursion level r of the sequential algorithm; all segments of all lines take part in
+ *              every round. With eps2 = 0 exactly the vertices off their chord survive: collinear vertices are dropped.
+ *   bounds:    differences within +-2^30, products within 2^60, |cross| <= 2^60 and d^2 <= 2^61 in 64 bits; cross^2 <= 2^120
+ *              against eps2 |b - a|^2 <= 2^97 as unsigned 128-bit integers.
+ *   rounds:    as in the outline simplification: rounds 0 .. max_rounds - 1 keep their winners (1 <= max_rounds <= 4095), round
+ *              max_rounds is a probe that only counts them, a round whose predecessor kept nothing returns at once. `rounds` is
+ *              the number of rounds that kept a vertex; `converged` says that the probe found nothing to keep: otherwise the
+ *              result is the sequential result truncated at depth max_rounds.
+ *   output:    out_vertices int32 [n_vertices][2], out_kept int32 [n_vertices]: the kept vertices and their positions, in
+ *              input order, compacted (the first `count` of the header are written). table: InsarContourLine [1 + n_lines],
+ *              16-byte aligned. Record 0: level = n_lines, leader = rounds, start = converged, count = kept vertices, closed =
+ *              n_vertices. Record 1 + r: level and leader of the input line, closed as 0 / 1; start and count in the compacted
+ *              array; area2 the shoelace sum of the kept vertices of a ring (added modulo 2^64: exact wherever it fits an int64,
+ *              as for every ring that does not overlap itself), 0 for an open line; y0 .. x1 the half-open box of the kept
+ *              vertices; _pad = 1 where a ring collapsed (fewer than 3 kept vertices, or area2 == 0), 0 for every open line.
+ *   scratch:   insar_contour_simplify_scratch_bytes(...) bytes, 16-byte aligned; setup clears what it needs. Its first 4096
+ *              int32 are the per-round counters of kept vertices (slot max_rounds: the probe): a host that reads the counter of
+ *              the last round it launched and finds 0 may stop launching rounds.
+ * Guaranteed: every dropped vertex lies within the tolerance of the chord of the segment it ended in; the ends of an open line
+ * stay; the kept set of a larger tolerance is a subset of that of a smaller one when both converged. NOT guaranteed: that two
+ * lines, of different levels or of one, never cross at a large tolerance, nor that a hole stays inside its exterior.
+ * Call setup, rounds (once, or in batches of consecutive rounds), finish in this order on one stream with the same counts and
+ * capacities. 6 + 5 per round + 6 launches; no work-group waits on another, integer atomics only, nothing depends on launch
+ * geometry. Every argument is checked before the device is touched (null pointers, counts against capacities, alignment, eps2,
+ * the round numbers); the line table itself lives on the device and is the caller's promise, and no kernel leaves its buffers
+ * whatever the table holds. */
+/* host only: bytes of scratch and of the output table for these capacities (1 <= max_vertices <= 2^28, 1 <= max_lines <= 2^27) */
+int insar_contour_simplify_scratch_bytes(int32_t max_vertices, int32_t max_lines, int64_t* scratch_bytes, int64_t* table_bytes);
+/* host only: the launches of setup, `rounds` rounds (the probe counts as one) and finish: 12 + 5 rounds */
+int insar_contour_simplify_launches(int32_t rounds);
+/* 6 launches (clear; line of every vertex, open ends kept, smallest key per ring; largest distance and seed 1; its smallest key;
+ * its smallest position; seeds kept). */
+int insar_contour_simplify_setup(const int32_t* vertices, int32_t n_vertices, const void* lines, int32_t n_lines,
+                                 int32_t max_vertices, int32_t max_lines, void* scratch, void* stream);
+/* 5 launches per round (carries of the kept positions over the blocks; |cross| and the segment maximum; ties by key; ties by
+ * position; winners kept) for the rounds first_round .. first_round + n_rounds - 1, all within 0 .. max_rounds; round
+ * max_rounds is the probe. */
+int insar_contour_simplify_rounds(const int32_t* vertices, int32_t n_vertices, const void* lines, int32_t n_lines, int64_t eps2,
+                                  int32_t first_round, int32_t n_rounds, int32_t max_rounds, int32_t max_vertices,
+                                  int32_t max_lines, void* scratch, void* stream);
+/* 6 launches (kept per block; one-work-group scan and the header; scatter; line records; area2 and boxes; collapsed flags) */
+int insar_contour_simplify_finish(const int32_t* vertices, int32_t n_vertices, const void* lines, int32_t n_lines,
+                                  int32_t max_rounds, int32_t max_vertices, int32_t max_lines, void* scratch, void* table,
+                                  int32_t* out_vertices, int32_t* out_kept, void* stream);
+
 /* ---- polygon rasterisation (build-side addition; the reference reads ready-made masks): csrc/raster.hip ---------------------
  * The inverse of the region outlines: an edge table becomes a label map `out` [H][W] (row-major; uint8 with INSAR_RASTER_U8,
  * int32 with INSAR_RASTER_I32; H >= 1, 1 <= W <= 16384, H * W < 2^31) in exact integers, no floating point on the device.

@@ -20,6 +20,7 @@ from .crops import CropIndex, SceneCrops, draw_crops, gather_crops  # noqa: F401
 from .outlines import OutlineScratch, region_outlines, to_geojson, to_polygons  # noqa: F401
 from .simplify import SimplifyScratch, simplify_outlines  # noqa: F401
 from .contours import ContourScratch, contour_lines, contour_polygons, contours_to_geojson, lines_to_coords  # noqa: F401
+from .contours import ContourSimplifyScratch, simplify_contours  # noqa: F401
 from .focal import box_taps, focal_tile, gaussian_taps, gradient_raster, rank_filter, smooth_raster  # noqa: F401
 from .skeletons import SkeletonScratch, skeleton_table, thin_regions  # noqa: F401
 from .zonal import ZonalScratch, percentile, region_stats  # noqa: F401
@@ -42,6 +43,7 @@ __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "Cha
            "CropIndex", "SceneCrops", "draw_crops", "gather_crops",
            "OutlineScratch", "region_outlines", "to_polygons", "to_geojson", "SimplifyScratch", "simplify_outlines",
            "ContourScratch", "contour_lines", "contour_polygons", "contours_to_geojson", "lines_to_coords",
+           "ContourSimplifyScratch", "simplify_contours",
            "smooth_raster", "rank_filter", "gradient_raster", "box_taps", "gaussian_taps", "focal_tile",
            "SkeletonScratch", "thin_regions", "skeleton_table",
            "PolygonTable", "RasterScratch", "pack_polygons", "from_geojson", "rasterise_polygons", "labels_from_geojson",

@@ -254,6 +254,11 @@ _SIGNATURES = {
     "insar_contour_rank": [_I, _I, _I, _I, _I, _P, _P],
     "insar_contour_lines": [_I, _I, _I, _I, _I, _I, _P, _P, _P],
     "insar_contour_write": [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "insar_contour_simplify_scratch_bytes": [_I, _I, _P, _P],
+    "insar_contour_simplify_launches": [_I],
+    "insar_contour_simplify_setup": [_P, _I, _P, _I, _I, _I, _P, _P],
+    "insar_contour_simplify_rounds": [_P, _I, _P, _I, _L, _I, _I, _I, _I, _I, _P, _P],
+    "insar_contour_simplify_finish": [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "insar_simplify_scratch_bytes": [_I, _I, _P, _P],
     "insar_simplify_launches": [_I],
     "insar_simplify_setup": [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P],
@@ -364,7 +369,7 @@ def load():
 _COUNT_ONLY = {"insar_tune_get", "insar_igemm_num_mtiles", "insar_igemm_tile_rows", "insar_igemm_tile_cols", "insar_igemm_tile_cols_dt", "insar_wgrad_tile", "insar_wgrad_tile_pair", "insar_wgrad_conv3_tile", "insar_wgrad_conv3x_tile", "insar_wgrad_conv3y_tile", "insar_wgrad_conv3k_tile", "insar_wgrad_conv3k_slices", "insar_conv3x3_flat_ok", "insar_conv3x3_flat_rows_ok", "insar_conv3x3_flat2_rows_ok", "insar_conv3x3_flat_rows_dil_ok", "insar_conv3x3_flat_num_mtiles", "insar_conv3x3_flat_stat_rows", "insar_conv3x3_c64_ok", "insar_conv3x3_c64_rows", "insar_conv3x3_c64_geometry", "insar_conv3x3_small_wgrad_blocks", "insar_conv3x3_small_wgrad_fused_ok", "insar_conv3x3_small_fwd_rows", "insar_conv1x1_out_bwd_blocks",
                "insar_ce_blocks", "insar_conv7x7s2_fwd_rows", "insar_conv7x7s2_wgrad_blocks", "insar_outline_launches",
                "insar_skeleton_launches", "insar_raster_launches", "insar_raster_band_rows", "insar_simplify_launches",
-               "insar_contour_launches"}
+               "insar_contour_launches", "insar_contour_simplify_launches"}
 
 
 _TAPE = None      # while a launch tape is being recorded (tape.py): the list every launch is appended to

@@ -1,7 +1,9 @@
 """Contour lines: the iso-lines of a device raster at up to 32 levels as ordered polylines of sub-pixel vertices, closed rings
 and open lines (csrc/contour.hip: insar_contour_edges / _lead / _rank / _lines / _write), and the host helpers that turn them
 into coordinates, polygons and GeoJSON. `ScenePredictor.detect(..., contours=dict(levels=...))` contours a probability plane
-or a co-registered raster.
+or a co-registered raster. `simplify_contours` thins the lines on the device (csrc/contour_simplify.hip:
+insar_contour_simplify_setup / _rounds / _finish): Douglas-Peucker in exact integers, open lines and rings alike, and the
+result has the shape of the `contour_lines` dict, so the host helpers take it unchanged.
 
 Semantics (include/insar_hip.h, "contour lines"): marching squares in exact integers. Every pixel becomes an integer q by
 `zonal`'s rule; a node is a pixel centre, at (y + 1/2, x + 1/2) in the frame of `region_outlines`, and every coordinate is an
@@ -23,7 +25,7 @@ import torch
 
 from . import _lib
 from ._lib import InsarError, call, ptr
-from ._scene import Scratch, check_int, check_map, check_on_device, query_bytes, read_back
+from ._scene import Scratch, check_int, check_map, check_on_device, pinned, query_bytes, read_back
 from .zonal import quantise_scalar
 
 DEFAULT_MAX_LINES = 65536
@@ -189,6 +191,182 @@ def contour_lines(raster: torch.Tensor, levels, *, scale: float = 2 ** 16, valid
     return _result(vertices, lines_from_table(raw, n_lines), level_counts, levels_q, scale, is_float)
 
 
+# ---- simplification ------------------------------------------------------------------------------------------------------------
+# A round is one level of the recursion: a line of n vertices that splits evenly is done after log2 n rounds, one that sheds a
+# vertex per level needs as many rounds as vertices; 64 covers contour lines as rasters give them, and `converged` says when
+# it did not.
+DEFAULT_MAX_ROUNDS = 64
+MAX_ROUNDS = 4095
+ROUNDS_PER_READ = 8                      # the host looks at a round's counter once per this many rounds
+MAX_TOLERANCE = 1024.0
+MAX_COORD = 1 << 30                      # the contract of simplify_contours: 0 <= Y, X <= 2^30 (contour_lines stays below it)
+MAX_SIMPLIFY_VERTICES = 1 << 28
+MAX_SIMPLIFY_LINES = 1 << 27
+SIMPLIFIED_FIELDS = LINE_FIELDS + ("input_area2", "collapsed")
+_NEEDED = ("level", "closed", "start", "count", "leader", "area2")
+
+
+def contour_simplify_scratch_bytes(max_vertices: int, max_lines: int):
+    """(scratch bytes, table bytes) of `simplify_contours` for these capacities. Host arithmetic only."""
+    return query_bytes("insar_contour_simplify_scratch_bytes", max_vertices, max_lines, outputs=2)
+
+
+def contour_simplify_launches(rounds: int) -> int:
+    """Kernel launches of one `simplify_contours` call that issues `rounds` rounds (the probe after max_rounds counts as
+    one): 12 + 5 rounds."""
+    return call("insar_contour_simplify_launches", int(rounds))
+
+
+def eps_q(tolerance: float) -> int:
+    """round(256 * tolerance): the tolerance in 1/256 pixel, ties to even."""
+    return int(round(float(tolerance) * SUBPIXEL))
+
+
+class ContourSimplifyScratch(Scratch):
+    """The device buffers of one (max_vertices, max_lines): scratch, the input and the output line table, and the pinned host
+    copies of the tables and of one round counter. Nothing in them has to survive between calls or be cleared. The vertex and
+    index arrays are the caller's: every call returns fresh ones."""
+    KEY, DEVICE_AT = ("max_vertices", "max_lines"), 2
+
+    def __init__(self, max_vertices: int, max_lines: int, device):
+        sb, tb = contour_simplify_scratch_bytes(max_vertices, max_lines)
+        super().__init__((max_vertices, max_lines), device, scratch=sb, table_in=tb, table=tb, host=tb)
+        self.host_in, self.counter = pinned(tb), pinned(4)
+
+
+def check_tolerance(who: str, name: str, tolerance) -> float:
+    """The tolerance of `simplify_contours` in pixels: a finite number in 0 .. 1024, else InsarError."""
+    if isinstance(tolerance, bool) or not isinstance(tolerance, (int, float, np.integer, np.floating)):
+        raise InsarError(f"{who}: {name}={tolerance!r}: a number of pixels")
+    if not math.isfinite(float(tolerance)) or not 0.0 <= float(tolerance) <= MAX_TOLERANCE:
+        raise InsarError(f"{who}: {name}={tolerance!r}: finite, 0 .. {MAX_TOLERANCE:g}")
+    return float(tolerance)
+
+
+def _check_simplify(contours, tolerance, max_rounds, scratch):
+    """Everything `simplify_contours` refuses, none of which needs a device. Returns (vertices, lines, n_lines)."""
+    who = "simplify_contours"
+    if not isinstance(contours, dict) or "vertices" not in contours or "lines" not in contours:
+        raise InsarError(f"{who}: contours must be a dict of the shape contour_lines returns, with 'vertices' and 'lines'")
+    v, ln = contours["vertices"], contours["lines"]
+    if not isinstance(v, torch.Tensor):
+        raise InsarError(f"{who}: contours['vertices'] must be a torch tensor, got {type(v).__name__}")
+    if v.dtype != torch.int32 or v.dim() != 2 or v.shape[1] != 2 or not v.is_contiguous():
+        raise InsarError(f"{who}: contours['vertices'] must be a contiguous int32 tensor [V, 2], got {v.dtype} {tuple(v.shape)}")
+    if not isinstance(ln, dict) or any(f not in ln for f in _NEEDED):
+        raise InsarError(f"{who}: contours['lines'] must hold {', '.join(_NEEDED)}")
+    R = len(ln["start"])
+    if any(np.asarray(ln[f]).shape != (R,) for f in _NEEDED):
+        raise InsarError(f"{who}: the fields of contours['lines'] differ in length")
+    check_tolerance(who, "tolerance", tolerance)
+    check_int(who, "max_rounds", max_rounds, 1, MAX_ROUNDS, integral_floats=False)
+    V = int(v.shape[0])
+    if V > MAX_SIMPLIFY_VERTICES or R > MAX_SIMPLIFY_LINES:
+        raise InsarError(f"{who}: {V} vertices in {R} lines: at most 2^28 and 2^27")
+    start, count = np.asarray(ln["start"], dtype=np.int64), np.asarray(ln["count"], dtype=np.int64)
+    if (start != np.concatenate([[0], np.cumsum(count)[:-1]])).any() or int(count.sum()) != V:
+        raise InsarError(f"{who}: the lines must tile the vertex array: start[0] = 0, start[i + 1] = start[i] + count[i], "
+                         f"counts adding up to {V}")
+    short = np.flatnonzero(count < np.where(np.asarray(ln["closed"], dtype=bool), 3, 2))
+    if len(short):
+        i = int(short[0])
+        raise InsarError(f"{who}: line {i} is {'closed' if ln['closed'][i] else 'open'} and has {int(count[i])} "
+                         f"vertices: an open line needs 2, a closed one 3")
+    if scratch is not None:
+        if not isinstance(scratch, ContourSimplifyScratch):
+            raise InsarError(f"{who}: scratch must be a ContourSimplifyScratch, got {type(scratch).__name__}")
+        if scratch.max_vertices < V or scratch.max_lines < R or scratch.device != v.device:
+            raise InsarError(f"{who}: scratch for {scratch.max_vertices} vertices in {scratch.max_lines} lines on {scratch.device}: "
+                             f"the input has {V} vertices in {R} lines on {v.device}")
+    return v, ln, R
+
+
+def _carried(contours: dict, out: dict) -> dict:
+    for k in ("level_counts", "levels_q", "scale"):
+        if k in contours:
+            out[k] = contours[k]
+    return out
+
+
+def simplify_contours(contours: dict, *, tolerance: float, max_rounds: int = DEFAULT_MAX_ROUNDS,
+                      scratch: Optional[ContourSimplifyScratch] = None) -> dict:
+    """Douglas-Peucker simplification of the lines of `contours` (a dict of the shape `contour_lines` returns) on the device.
+
+        c = contour_lines(smooth_raster(prob[1], gaussian_taps(1.5)), [0.5])
+        s = simplify_contours(c, tolerance=0.5)
+        s["vertices"]   device int32 [V', 2]: the kept vertices in input order, line after line
+        s["kept"]       device int32 [V']: their positions in c["vertices"]
+        s["lines"]      the line table of `contour_lines` with start / count in the compacted array, area2 (exact int64) and the
+                        half-open box recomputed from the kept vertices; level, closed and leader unchanged; `input_area2`,
+                        the input's area2 (its sign still tells a peak from a pit); `collapsed`: a ring with fewer than 3
+                        kept vertices or area2 == 0 (an open line never collapses)
+        s["n_lines"] (unchanged), ["n_vertices"] = V', ["input_n_vertices"], ["rounds"], ["converged"], and level_counts,
+        levels_q, scale as they came
+
+    Only the dict is read, no raster: hand-made polylines are valid input, with coordinates in 0 .. 2^30 (the contract: the
+    host cannot check it without a read-back, and every overflow bound rests on it; `contour_lines` stays below it). Every
+    line is simplified on its own. An open line keeps both ends; a ring starts from its smallest (Y, X) vertex and the vertex
+    farthest from it. Every round keeps, in every segment between two kept vertices, the vertex farthest from the chord if it
+    lies beyond `tolerance`, ties to the smallest (Y, X), then to the smallest position. `tolerance`: pixels, 0 .. 1024,
+    quantised to 1/256; at 0 exactly the collinear vertices go. `max_rounds` (default 64, at most 4095) bounds the recursion
+    depth: if some segment would still split after it, the result is the full result truncated at that depth and
+    `converged` is False. Integers only: every output is bitwise reproducible (tests/contour_simplify_ref.py restates it).
+
+    Guaranteed: every dropped vertex lies within `tolerance` of the chord of the segment it ended in; the ends of open lines
+    stay; kept sets are nested over tolerances. Not guaranteed: lines of different levels, or two lines of one level, may
+    cross at a large tolerance, and a hole may then fall outside its simplified exterior (`contour_polygons` raises as for any
+    such input); `rasterise_polygons` of the polygons gives back {q >= level} bit for bit at tolerance 0 only.
+
+    12 + 5 launches per round on the current stream; the host reads one 4-byte counter per 8 rounds to stop launching once
+    a round kept nothing, then the line table once. `scratch`: a ContourSimplifyScratch with room for the input (else
+    allocated). An empty input returns an empty result. `contours` is not written."""
+    v, ln, R = _check_simplify(contours, tolerance, max_rounds, scratch)
+    V = int(v.shape[0])
+    if V == 0:
+        lines = lines_from_table(np.zeros(HEADER_RECORDS * LINE_DTYPE.itemsize, dtype=np.uint8), 0)
+        lines.update(input_area2=np.zeros(0, dtype=np.int64), collapsed=np.zeros(0, dtype=np.bool_))
+        return _carried(contours, {"vertices": torch.empty(0, 2, dtype=torch.int32, device=v.device),
+                                   "kept": torch.empty(0, dtype=torch.int32, device=v.device), "lines": lines, "n_lines": 0,
+                                   "n_vertices": 0, "input_n_vertices": 0, "rounds": 0, "converged": True})
+    check_on_device("simplify_contours", "vertices", v)
+    if scratch is None:
+        scratch = ContourSimplifyScratch(V, R, v.device)
+    vm, lm = scratch.max_vertices, scratch.max_lines
+    eps2 = eps_q(tolerance) ** 2
+    max_rounds = int(max_rounds)
+    nbytes = LINE_DTYPE.itemsize * (1 + R)
+    tin = scratch.host_in.numpy()[:nbytes].view(LINE_DTYPE)
+    tin[:] = 0
+    for f in ("level", "closed", "start", "count", "leader"):
+        tin[f][1:] = ln[f]
+    out_v = torch.empty(V, 2, dtype=torch.int32, device=v.device)
+    out_k = torch.empty(V, dtype=torch.int32, device=v.device)
+    sp, tp, ip = ptr(scratch.scratch), ptr(scratch.table), ptr(scratch.table_in)
+    with torch.cuda.device(v.device):
+        s = _lib.stream_ptr()
+        scratch.table_in[:nbytes].copy_(scratch.host_in[:nbytes], non_blocking=True)
+        call("insar_contour_simplify_setup", ptr(v), V, ip, R, vm, lm, sp, s)
+        r, total = 0, max_rounds + 1                             # the last round is the probe
+        while r < total:
+            n = min(ROUNDS_PER_READ, total - r)
+            call("insar_contour_simplify_rounds", ptr(v), V, ip, R, eps2, r, n, max_rounds, vm, lm, sp, s)
+            r += n
+            if r < total:
+                if int(read_back(scratch.counter, scratch.scratch[4 * (r - 1):4 * r]).view(np.int32)[0]) == 0:
+                    break
+        call("insar_contour_simplify_finish", ptr(v), V, ip, R, max_rounds, vm, lm, sp, tp, ptr(out_v), ptr(out_k), s)
+        raw = read_back(scratch.host, scratch.table, nbytes).view(LINE_DTYPE)
+    head, rec = raw[0], raw[1:]
+    kept = int(head["count"])
+    lines = {"line": np.arange(R, dtype=np.int32)}
+    for f in LINE_FIELDS[1:]:
+        lines[f] = rec[f].astype(np.bool_) if f == "closed" else rec[f].copy()
+    lines["input_area2"] = np.asarray(ln["area2"]).astype(np.int64)
+    lines["collapsed"] = rec["_pad"] != 0
+    return _carried(contours, {"vertices": out_v[:kept], "kept": out_k[:kept], "lines": lines, "n_lines": R, "n_vertices": kept,
+                               "input_n_vertices": V, "rounds": int(head["leader"]), "converged": bool(head["start"])})
+
+
 # ---- host side: coordinates, polygons, GeoJSON ------------------------------------------------------------------------------------
 def _host_vertices(contours: dict) -> np.ndarray:
     v = contours["vertices"]
@@ -199,11 +377,18 @@ def _level_value(contours: dict, i: int) -> float:
     return float(contours["levels_q"][i]) / float(contours.get("scale", 1.0))
 
 
-def lines_to_coords(contours: dict, transform=None) -> List[dict]:
+def _collapsed(contours: dict):
+    """The `collapsed` flags of a simplified dict, None for a dict that `simplify_contours` did not make."""
+    c = contours["lines"].get("collapsed")
+    return None if c is None else np.asarray(c, dtype=bool)
+
+
+def lines_to_coords(contours: dict, transform=None, drop_collapsed: bool = True) -> List[dict]:
     """One entry per line, in line order: {"level": index, "value": the level in raster units as it was quantised, "closed",
     "xy": float64 [n, 2]}. Without `transform` xy is (x, y) in pixels in the frame of `region_outlines` (vertex / 256, exact);
     with a 2 x 3 affine it is the world coordinate A @ (x, y, 1), the convention of `to_polygons`. Closed lines are not
-    repeated at their end."""
+    repeated at their end. Of a dict `simplify_contours` made, the collapsed rings are left out unless `drop_collapsed` is
+    False; any other dict has none."""
     A = None
     if transform is not None:
         A = np.asarray(transform, dtype=np.float64)
@@ -211,8 +396,11 @@ def lines_to_coords(contours: dict, transform=None) -> List[dict]:
             raise InsarError(f"transform must be a 2 x 3 affine, got shape {A.shape}")
     v = _host_vertices(contours).astype(np.float64) / SUBPIXEL
     ln = contours["lines"]
+    gone = _collapsed(contours) if drop_collapsed else None
     out = []
     for i in range(len(ln["level"])):
+        if gone is not None and gone[i]:
+            continue
         s, n = int(ln["start"][i]), int(ln["count"][i])
         xy = v[s:s + n, ::-1]
         if A is not None:
@@ -222,12 +410,12 @@ def lines_to_coords(contours: dict, transform=None) -> List[dict]:
     return out
 
 
-def contours_to_geojson(contours: dict, transform=None) -> dict:
+def contours_to_geojson(contours: dict, transform=None, drop_collapsed: bool = True) -> dict:
     """A GeoJSON FeatureCollection: one LineString feature per line with the properties "level" (index), "value" and "closed";
-    coordinates are [x, y] lists as `lines_to_coords` gives them, and a closed line repeats its first point.
-    json-serialisable types only."""
+    coordinates are [x, y] lists as `lines_to_coords` gives them (`drop_collapsed` as there), and a closed line repeats its
+    first point. json-serialisable types only."""
     feats = []
-    for e in lines_to_coords(contours, transform):
+    for e in lines_to_coords(contours, transform, drop_collapsed):
         xy = e["xy"]
         if e["closed"]:
             xy = np.concatenate([xy, xy[:1]], axis=0)
@@ -253,7 +441,10 @@ def contour_polygons(contours: dict, level_index: int) -> List[dict]:
     [{"exterior": float64 [n, 2], "holes": [...]}, ...]}] (empty without a ring). Coordinates are (y, x) = vertex / 256, which is
     exact, rings closed by repeating the first vertex; `pack_polygons` takes them as they are. Rings of positive area2 are
     exteriors; every ring of negative area2 goes to the smallest-area exterior that contains its first vertex, by the even-odd
-    rule in integers. A level with an open line is refused: its set is not bounded by rings alone."""
+    rule in integers. A level with an open line is refused: its set is not bounded by rings alone. Of a dict
+    `simplify_contours` made, exteriors and holes are told apart by the sign of `input_area2` (a simplified ring may turn
+    over or lose its area), collapsed rings are skipped, and a collapsed exterior takes its holes with it: a hole that no
+    remaining exterior contains is dropped where its level has a collapsed exterior, and refused as ever where it has none."""
     who = "contour_polygons"
     ln = contours["lines"]
     L = len(contours["levels_q"])
@@ -264,15 +455,23 @@ def contour_polygons(contours: dict, level_index: int) -> List[dict]:
         raise InsarError(f"{who}: level {level_index} has {len(opened)} open line(s) (line {opened[0]} first): the set is bounded "
                          "by the raster border or by no-data there, not by rings")
     v = _host_vertices(contours).astype(np.int64)
+    gone = _collapsed(contours)
+    sign = ln["area2"] if gone is None else ln["input_area2"]
+    lost_exterior = False
+    if gone is not None:
+        lost_exterior = any(gone[i] and sign[i] > 0 for i in idx)
+        idx = [i for i in idx if not gone[i]]
     ring = {int(i): v[int(ln["start"][i]):int(ln["start"][i]) + int(ln["count"][i])] for i in idx}
-    ext = [i for i in ring if ln["area2"][i] > 0]
+    ext = [i for i in ring if sign[i] > 0]
     polys = {i: {"exterior": np.concatenate([ring[i], ring[i][:1]]) / float(SUBPIXEL), "holes": []} for i in ext}
     for i in ring:
-        if ln["area2"][i] >= 0:
+        if sign[i] >= 0:
             continue
         py, px = int(ring[i][0, 0]), int(ring[i][0, 1])
         holding = [e for e in ext if ln["y0"][e] <= py < ln["y1"][e] and ln["x0"][e] <= px < ln["x1"][e] and _inside(ring[e], py, px)]
+        if not holding and lost_exterior:
+            continue
         if not holding:
             raise InsarError(f"{who}: no ring of positive area of level {level_index} contains line {i}")
-        polys[min(holding, key=lambda e: int(ln["area2"][e]))]["holes"].append(np.concatenate([ring[i], ring[i][:1]]) / float(SUBPIXEL))
+        polys[min(holding, key=lambda e: abs(int(ln["area2"][e])))]["holes"].append(np.concatenate([ring[i], ring[i][:1]]) / float(SUBPIXEL))
     return [{"label": 1, "polygons": [polys[i] for i in ext]}] if ext else []

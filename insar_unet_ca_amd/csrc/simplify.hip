@@ -33,10 +33,12 @@
 // everything a kernel reads was written by an earlier launch; within a launch work-groups meet only in relaxed agent-scope
 // integer atomics (max, min, add), whose arrival order changes nothing. No float anywhere.
 #include "scene_common.h"
+#include "block_scan.h"
 #include <limits.h>
 
 #define SM_THREADS 256
 #define SM_WAVES (SM_THREADS / INSAR_WAVE)
+static_assert(SM_THREADS == BLOCK_SCAN_THREADS, "the scans of block_scan.h take one value per thread of the work-group");
 #define SM_MAX_ROUNDS 4095
 #define SM_COUNTERS 4096
 #define SM_MAX_VERTICES (1 << 28)
@@ -80,63 +82,6 @@ __device__ __forceinline__ void sm_note_kept(const SmBuf& b, int i, int r) {
   SM_MAX(&b.lastk[r], i);
   SM_MAX(&b.bmax[i / SM_THREADS], i);
   SM_MIN(&b.bmin[i / SM_THREADS], i);
-}
-
-// inclusive maximum over the threads 0 .. tid of the work-group, and the work-group's maximum; w: SM_WAVES ints of LDS
-__device__ __forceinline__ int sm_prefix_max(int v, int* w, int* total) {
-  const int lane = threadIdx.x & (INSAR_WAVE - 1), wave = threadIdx.x / INSAR_WAVE;
-#pragma unroll
-  for (int d = 1; d < INSAR_WAVE; d <<= 1) {
-    const int o = __shfl_up(v, d, INSAR_WAVE);
-    if (lane >= d) v = o > v ? o : v;
-  }
-  if (lane == INSAR_WAVE - 1) w[wave] = v;
-  __syncthreads();
-  int tot = INT_MIN;
-#pragma unroll
-  for (int k = 0; k < SM_WAVES; ++k) {
-    if (k < wave) v = w[k] > v ? w[k] : v;
-    tot = w[k] > tot ? w[k] : tot;
-  }
-  *total = tot;
-  __syncthreads();
-  return v;
-}
-// inclusive minimum over the threads tid .. SM_THREADS - 1
-__device__ __forceinline__ int sm_suffix_min(int v, int* w, int* total) {
-  const int lane = threadIdx.x & (INSAR_WAVE - 1), wave = threadIdx.x / INSAR_WAVE;
-#pragma unroll
-  for (int d = 1; d < INSAR_WAVE; d <<= 1) {
-    const int o = __shfl_down(v, d, INSAR_WAVE);
-    if (lane + d < INSAR_WAVE) v = o < v ? o : v;
-  }
-  if (lane == 0) w[wave] = v;
-  __syncthreads();
-  int tot = INT_MAX;
-#pragma unroll
-  for (int k = 0; k < SM_WAVES; ++k) {
-    if (k > wave) v = w[k] < v ? w[k] : v;
-    tot = w[k] < tot ? w[k] : tot;
-  }
-  *total = tot;
-  __syncthreads();
-  return v;
-}
-// exclusive prefix sum over the work-group's threads
-__device__ __forceinline__ int sm_prefix_sum(int v, int* w, int* total) {
-  const int lane = threadIdx.x & (INSAR_WAVE - 1), wave = threadIdx.x / INSAR_WAVE;
-  const int incl = wave_incl_scan(v, lane);
-  if (lane == INSAR_WAVE - 1) w[wave] = incl;
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < SM_WAVES; ++k) {
-    if (k < wave) off += w[k];
-    tot += w[k];
-  }
-  *total = tot;
-  __syncthreads();
-  return off + incl - v;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -259,22 +204,7 @@ __global__ void __launch_bounds__(SM_THREADS)
 simplify_carry_kernel(SmBuf b, int nblk, int rd) {
   __shared__ int w[SM_WAVES];
   if (rd > 0 && b.changed[rd - 1] == 0) return;
-  int carry = -1, total;
-  for (int base = 0; base < nblk; base += SM_THREADS) {          // every thread keeps the same running maximum
-    const int j = base + (int)threadIdx.x;
-    const int v = (j >= 1 && j <= nblk) ? b.bmax[j - 1] : -1;
-    const int m = sm_prefix_max(v, w, &total);
-    if (j < nblk) b.cmax[j] = m > carry ? m : carry;
-    carry = total > carry ? total : carry;
-  }
-  carry = INT_MAX;
-  for (int base = ((nblk - 1) / SM_THREADS) * SM_THREADS; base >= 0; base -= SM_THREADS) {
-    const int j = base + (int)threadIdx.x;
-    const int v = j + 1 < nblk ? b.bmin[j + 1] : INT_MAX;
-    const int m = sm_suffix_min(v, w, &total);
-    if (j < nblk) b.cmin[j] = m < carry ? m : carry;
-    carry = total < carry ? total : carry;
-  }
+  block_carry(b.bmax, b.bmin, b.cmax, b.cmin, nblk, w);
 }
 
 __global__ void __launch_bounds__(SM_THREADS)
@@ -286,8 +216,8 @@ simplify_cross_kernel(SmBuf b, const int* __restrict__ verts, int nv, const Insa
   const bool live = i < nv;
   const bool kept = live && b.keep[i];
   int total;
-  int p = sm_prefix_max(kept ? i : -1, w, &total);
-  int q = sm_suffix_min(kept ? i : INT_MAX, w, &total);
+  int p = block_prefix_max(kept ? i : -1, w, &total);
+  int q = block_suffix_min(kept ? i : INT_MAX, w, &total);
   const int cp = b.cmax[blockIdx.x], cq = b.cmin[blockIdx.x];
   p = cp > p ? cp : p;
   q = cq < q ? cq : q;
@@ -369,7 +299,7 @@ simplify_count_kernel(SmBuf b, int nv) {
   __shared__ int w[SM_WAVES];
   const int i = blockIdx.x * SM_THREADS + threadIdx.x;
   int total;
-  sm_prefix_sum(i < nv ? (int)b.keep[i] : 0, w, &total);
+  block_prefix_sum(i < nv ? (int)b.keep[i] : 0, w, &total);
   if (threadIdx.x == 0) b.bsum[blockIdx.x] = total;
 }
 
@@ -384,7 +314,7 @@ simplify_scan_kernel(SmBuf b, int nblk, int nv, int nr, int max_rounds, InsarRin
   for (int base = 0; base < nblk; base += SM_THREADS) {
     const int j = base + (int)threadIdx.x;
     const int v = j < nblk ? b.bsum[j] : 0;
-    const int ex = sm_prefix_sum(v, w, &total);
+    const int ex = block_prefix_sum(v, w, &total);
     if (j < nblk) b.bsum[j] = carry + ex;
     carry += total;
   }
@@ -411,7 +341,7 @@ simplify_scatter_kernel(SmBuf b, const int* __restrict__ verts, int nv, int* __r
   const int i = blockIdx.x * SM_THREADS + threadIdx.x;
   const int k = i < nv ? (int)b.keep[i] : 0;
   int total;
-  const int at = b.bsum[blockIdx.x] + sm_prefix_sum(k, w, &total);
+  const int at = b.bsum[blockIdx.x] + block_prefix_sum(k, w, &total);
   if (i >= nv) return;
   b.pos[i] = at;
   if (i == nv - 1) b.pos[nv] = at + k;

@@ -484,7 +484,9 @@ class ScenePredictor:
         is copied once); the "valid" plane of a masked predict is handed on, so that lines end beside no-data. With `smooth` =
         a Gaussian sigma in pixels (0 < sigma <= 5) in that dict the contoured raster first goes through
         `focal.smooth_raster(raster, gaussian_taps(sigma), valid=, return_valid=True)` and that valid plane goes to
-        `contour_lines`; without it not one operation changes. With None nothing of it runs."""
+        `contour_lines`; without it not one operation changes. With `simplify` = a tolerance in pixels (0 .. 1024) in that
+        dict "contours" is instead `simplify_contours` of those lines; without it not one operation changes either. With None
+        nothing of it runs."""
         if measure is not None and not isinstance(measure, dict):
             raise InsarError(f"measure: a dict of name -> raster or (raster, kwargs), got {type(measure).__name__}")
         if hysteresis is not None:
@@ -536,6 +538,9 @@ class ScenePredictor:
             if (isinstance(sigma, bool) or not isinstance(sigma, (int, float, np.integer, np.floating))
                     or not 0 < sigma <= 5):               # NaN compares false
                 raise InsarError(f"contours: smooth={sigma!r}: a Gaussian sigma in pixels, 0 < sigma <= 5")
+        if kw.get("simplify") is not None:
+            from .contours import check_tolerance
+            check_tolerance("contours", "simplify", kw["simplify"])
         return kw
 
     def _contour(self, out: dict, kw: dict) -> None:
@@ -543,6 +548,7 @@ class ScenePredictor:
         from .contours import DEFAULT_MAX_LINES, DEFAULT_MAX_VERTICES, ContourScratch, contour_lines
         kw = dict(kw)
         raster, plane, sigma = kw.pop("raster"), kw.pop("plane"), kw.pop("smooth", None)
+        tolerance = kw.pop("simplify", None)
         dev = out["mask"].device
         if raster is None:
             K = out["prob"].shape[0]
@@ -565,6 +571,9 @@ class ScenePredictor:
             from .focal import gaussian_taps, smooth_raster
             raster, valid = smooth_raster(raster, gaussian_taps(float(sigma)), valid=valid, return_valid=True)
         out["contours"] = contour_lines(raster, levels, valid=valid, scratch=scratch, **kw)
+        if tolerance is not None:
+            from .contours import simplify_contours
+            out["contours"] = simplify_contours(out["contours"], tolerance=tolerance)
 
     @staticmethod
     def _hysteresis_kwargs(hysteresis, sieve, region_kwargs: dict) -> dict:
