@@ -1,14 +1,13 @@
-// What the two Douglas-Peucker files (simplify.hip, contour_simplify.hip) share: the scans of one value per thread over a
-// work-group of BLOCK_SCAN_THREADS threads, by wave shuffles and one LDS slot per wave. Every thread of the work-group calls
-// them (they synchronise); w is BLOCK_SCAN_WAVES ints of LDS, free again on return.
+// The work-group scans of the scene tools (regions.hip, split.hip, raster.hip, outline.hip, contour.hip, hysteresis.hip,
+// simplify.hip, contour_simplify.hip): one value per thread over a work-group of THREADS threads, by wave shuffles and one LDS
+// slot per wave, and the one-work-group scan of a whole array built on the same steps. Every thread of the work-group calls them
+// (they synchronise); w is THREADS / INSAR_WAVE ints of LDS, free again on return.
 #pragma once
 #include "scene_common.h"
 #include <limits.h>
 
-#define BLOCK_SCAN_THREADS 256
-#define BLOCK_SCAN_WAVES (BLOCK_SCAN_THREADS / INSAR_WAVE)
-
 // inclusive maximum over the threads 0 .. tid of the work-group, and the work-group's maximum
+template <int THREADS>
 __device__ __forceinline__ int block_prefix_max(int v, int* w, int* total) {
   const int lane = threadIdx.x & (INSAR_WAVE - 1), wave = threadIdx.x / INSAR_WAVE;
 #pragma unroll
@@ -20,7 +19,7 @@ __device__ __forceinline__ int block_prefix_max(int v, int* w, int* total) {
   __syncthreads();
   int tot = INT_MIN;
 #pragma unroll
-  for (int k = 0; k < BLOCK_SCAN_WAVES; ++k) {
+  for (int k = 0; k < THREADS / INSAR_WAVE; ++k) {
     if (k < wave) v = w[k] > v ? w[k] : v;
     tot = w[k] > tot ? w[k] : tot;
   }
@@ -28,7 +27,8 @@ __device__ __forceinline__ int block_prefix_max(int v, int* w, int* total) {
   __syncthreads();
   return v;
 }
-// inclusive minimum over the threads tid .. BLOCK_SCAN_THREADS - 1
+// inclusive minimum over the threads tid .. THREADS - 1
+template <int THREADS>
 __device__ __forceinline__ int block_suffix_min(int v, int* w, int* total) {
   const int lane = threadIdx.x & (INSAR_WAVE - 1), wave = threadIdx.x / INSAR_WAVE;
 #pragma unroll
@@ -40,7 +40,7 @@ __device__ __forceinline__ int block_suffix_min(int v, int* w, int* total) {
   __syncthreads();
   int tot = INT_MAX;
 #pragma unroll
-  for (int k = 0; k < BLOCK_SCAN_WAVES; ++k) {
+  for (int k = 0; k < THREADS / INSAR_WAVE; ++k) {
     if (k > wave) v = w[k] < v ? w[k] : v;
     tot = w[k] < tot ? w[k] : tot;
   }
@@ -48,7 +48,8 @@ __device__ __forceinline__ int block_suffix_min(int v, int* w, int* total) {
   __syncthreads();
   return v;
 }
-// exclusive prefix sum over the work-group's threads
+// exclusive prefix sum over the work-group's threads; *total is the work-group's sum
+template <int THREADS>
 __device__ __forceinline__ int block_prefix_sum(int v, int* w, int* total) {
   const int lane = threadIdx.x & (INSAR_WAVE - 1), wave = threadIdx.x / INSAR_WAVE;
   const int incl = wave_incl_scan(v, lane);
@@ -56,7 +57,7 @@ __device__ __forceinline__ int block_prefix_sum(int v, int* w, int* total) {
   __syncthreads();
   int off = 0, tot = 0;
 #pragma unroll
-  for (int k = 0; k < BLOCK_SCAN_WAVES; ++k) {
+  for (int k = 0; k < THREADS / INSAR_WAVE; ++k) {
     if (k < wave) off += w[k];
     tot += w[k];
   }
@@ -65,22 +66,48 @@ __device__ __forceinline__ int block_prefix_sum(int v, int* w, int* total) {
   return off + incl - v;
 }
 
+// One work-group: a[0 .. n) becomes its exclusive prefix sum in place, THREADS elements per pass; returns the total (< 2^31) to
+// every thread. On return the new a[] is visible to the whole work-group. The caller writes its own header from the total.
+template <int THREADS>
+__device__ __forceinline__ int block_scan_array(int* a, int n, int* w) {
+  const int lane = threadIdx.x & (INSAR_WAVE - 1), wave = threadIdx.x / INSAR_WAVE;
+  int carry = 0;                                                 // every thread keeps the same running total
+  for (int base = 0; base < n; base += THREADS) {
+    const int i = base + (int)threadIdx.x;
+    const int v = i < n ? a[i] : 0;
+    const int incl = wave_incl_scan(v, lane);
+    if (lane == INSAR_WAVE - 1) w[wave] = incl;
+    __syncthreads();
+    int off = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < THREADS / INSAR_WAVE; ++k) {
+      if (k < wave) off += w[k];
+      tot += w[k];
+    }
+    if (i < n) a[i] = carry + off + incl - v;
+    carry += tot;
+    __syncthreads();
+  }
+  return carry;
+}
+
 // One work-group: cmax[j] = max of bmax over the blocks before j, cmin[j] = min of bmin over the blocks after j (the last kept
 // position before a block of positions and the first after it, -1 / INT_MAX where there is none).
+template <int THREADS>
 __device__ __forceinline__ void block_carry(const int* bmax, const int* bmin, int* cmax, int* cmin, int nblk, int* w) {
   int carry = -1, total;
-  for (int base = 0; base < nblk; base += BLOCK_SCAN_THREADS) {  // every thread keeps the same running maximum
+  for (int base = 0; base < nblk; base += THREADS) {             // every thread keeps the same running maximum
     const int j = base + (int)threadIdx.x;
     const int v = (j >= 1 && j <= nblk) ? bmax[j - 1] : -1;
-    const int m = block_prefix_max(v, w, &total);
+    const int m = block_prefix_max<THREADS>(v, w, &total);
     if (j < nblk) cmax[j] = m > carry ? m : carry;
     carry = total > carry ? total : carry;
   }
   carry = INT_MAX;
-  for (int base = ((nblk - 1) / BLOCK_SCAN_THREADS) * BLOCK_SCAN_THREADS; base >= 0; base -= BLOCK_SCAN_THREADS) {
+  for (int base = ((nblk - 1) / THREADS) * THREADS; base >= 0; base -= THREADS) {
     const int j = base + (int)threadIdx.x;
     const int v = j + 1 < nblk ? bmin[j + 1] : INT_MAX;
-    const int m = block_suffix_min(v, w, &total);
+    const int m = block_suffix_min<THREADS>(v, w, &total);
     if (j < nblk) cmin[j] = m < carry ? m : carry;
     carry = total < carry ? total : carry;
   }

@@ -38,6 +38,8 @@
 // below: turn right (leave through A - A'), unless B' is above and the saddle is joined (the four q sum to >= 4 q_l), then turn left
 // (leave through B - B'); A' above: left if B' is above too, else straight on (leave through A' - B').
 #include "scene_common.h"
+#include "block_scan.h"
+#include "list_rank.h"
 #include <limits.h>
 
 #define CT_THREADS 256
@@ -55,27 +57,9 @@
 #define CT_HDR_LEVELS 16                  // .. 47: crossings per level
 
 static_assert(sizeof(InsarContourLine) == 48, "InsarContourLine is three 16-byte stores");
-static_assert(CT_THREADS == 4 * INSAR_WAVE, "four waves per work-group in ct_block_excl");
 static_assert(CT_HDR_LEVELS + CT_MAX_LEVELS == CT_HDR * (int)sizeof(InsarContourLine) / 4, "the level counts end the header");
 
 struct CtLevels { int q[CT_MAX_LEVELS]; };
-
-// exclusive prefix of v over the work-group's threads; *total is the work-group's sum. wsum: CT_THREADS / INSAR_WAVE ints of LDS.
-__device__ __forceinline__ int ct_block_excl(int v, int* wsum, int* total) {
-  const int lane = threadIdx.x & (INSAR_WAVE - 1), wave = threadIdx.x / INSAR_WAVE;
-  const int incl = wave_incl_scan(v, lane);
-  if (lane == INSAR_WAVE - 1) wsum[wave] = incl;
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < CT_THREADS / INSAR_WAVE; ++w) {
-    if (w < wave) off += wsum[w];
-    tot += wsum[w];
-  }
-  *total = tot;
-  __syncthreads();                                               // wsum is free again
-  return off + incl - v;
-}
 
 // ---------------------------------------------------------------------------------------------
 // edges: quantise / mark / scan / offsets / link
@@ -193,27 +177,9 @@ contour_mark_kernel(const int* __restrict__ q, const uint8_t* __restrict__ ok, i
 // V = E, the crossings per level, zero for the levels that are not there.
 __global__ void __launch_bounds__(CT_SCAN_THREADS)
 contour_scan_kernel(int* __restrict__ a, int* __restrict__ b, int nblk, int* __restrict__ hdr, int slot_a, int slot_b, int L) {
-  __shared__ int wa[CT_SCAN_THREADS / INSAR_WAVE], wb[CT_SCAN_THREADS / INSAR_WAVE];
-  int carry_a = 0, carry_b = 0;                                  // every thread keeps the same running totals (< 2^31)
-  for (int base = 0; base < nblk; base += CT_SCAN_THREADS) {
-    const int i = base + threadIdx.x;
-    const int va = i < nblk ? a[i] : 0, vb = (b && i < nblk) ? b[i] : 0;
-    const int ia = wave_incl_scan(va), ib = wave_incl_scan(vb);
-    if ((threadIdx.x & (INSAR_WAVE - 1)) == INSAR_WAVE - 1) { wa[threadIdx.x / INSAR_WAVE] = ia; wb[threadIdx.x / INSAR_WAVE] = ib; }
-    __syncthreads();
-    int oa = 0, ta = 0, ob = 0, tb = 0;
-#pragma unroll
-    for (int w = 0; w < CT_SCAN_THREADS / INSAR_WAVE; ++w) {
-      if (w < (int)(threadIdx.x / INSAR_WAVE)) { oa += wa[w]; ob += wb[w]; }
-      ta += wa[w]; tb += wb[w];
-    }
-    if (i < nblk) {
-      a[i] = carry_a + oa + ia - va;
-      if (b) b[i] = carry_b + ob + ib - vb;
-    }
-    carry_a += ta; carry_b += tb;
-    __syncthreads();                                             // and this work-group's stores to a[] are visible to it
-  }
+  __shared__ int w[CT_SCAN_THREADS / INSAR_WAVE];
+  const int carry_a = block_scan_array<CT_SCAN_THREADS>(a, nblk, w);                 // the new a[] is visible to every thread
+  const int carry_b = b ? block_scan_array<CT_SCAN_THREADS>(b, nblk, w) : 0;
   const int t = threadIdx.x;
   if (L > 0) {
     if (t < CT_HDR_LEVELS) {
@@ -235,7 +201,7 @@ contour_offsets_kernel(const uint32_t* __restrict__ mask, int nq, int nblk, cons
   const int l = blockIdx.y, t = blockIdx.x * CT_THREADS + threadIdx.x;
   const uint32_t w = t < nq ? mask[l * nq + t] : 0u;
   int total;
-  const int o = counts[l * nblk + blockIdx.x] + ct_block_excl(__popc(w), wsum, &total);
+  const int o = counts[l * nblk + blockIdx.x] + block_prefix_sum<CT_THREADS>(__popc(w), wsum, &total);
   if (t < nq) off4[l * nq + t] = o;
 }
 
@@ -305,17 +271,8 @@ contour_link_kernel(const int* __restrict__ q, const uint8_t* __restrict__ ok, c
 }
 
 // ---------------------------------------------------------------------------------------------
-// lead / rank: one round per launch, from one pair buffer into the other
+// lead / rank: the rounds are list_rank.h's; `cut` between them
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(CT_THREADS)
-contour_lead_round_kernel(const int2* __restrict__ in, int2* __restrict__ out, int n) {
-  const int k = blockIdx.x * CT_THREADS + threadIdx.x;
-  if (k >= n) return;
-  const int2 a = in[k];
-  const int2 b = in[a.x];
-  out[k] = make_int2(b.x, min(a.y, b.y));
-}
-
 __global__ void __launch_bounds__(CT_THREADS)
 contour_cut_kernel(const int2* __restrict__ in, const int* __restrict__ succ0, const uint8_t* __restrict__ head,
                    int* __restrict__ lead, int* __restrict__ headof, int2* __restrict__ out, int n) {
@@ -331,18 +288,6 @@ contour_cut_kernel(const int2* __restrict__ in, const int* __restrict__ succ0, c
     lead[k] = a.y;
     out[k] = s == a.y ? make_int2(-1, 0) : make_int2(s, 1);      // the successor of a ring's last crossing is its leader
   }
-}
-
-__global__ void __launch_bounds__(CT_THREADS)
-contour_rank_round_kernel(const int2* __restrict__ in, int2* __restrict__ out, int n) {
-  const int k = blockIdx.x * CT_THREADS + threadIdx.x;
-  if (k >= n) return;
-  int2 a = in[k];
-  if (a.x >= 0) {
-    const int2 b = in[a.x];
-    a = make_int2(b.x, a.y + b.y);
-  }
-  out[k] = a;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -364,8 +309,8 @@ contour_line_count_kernel(const int* __restrict__ lead, const uint8_t* __restric
     if (k < n && ct_is_leader(lead, head, k)) { ++c; l += dist[k].y + 1; }
   }
   int tc, tl;
-  ct_block_excl(c, wsum, &tc);
-  ct_block_excl(l, wsum, &tl);
+  block_prefix_sum<CT_THREADS>(c, wsum, &tc);
+  block_prefix_sum<CT_THREADS>(l, wsum, &tl);
   if (threadIdx.x == 0) { lcnt[blockIdx.x] = tc; llen[blockIdx.x] = tl; }
 }
 
@@ -385,8 +330,8 @@ contour_line_number_kernel(const int* __restrict__ lead, const uint8_t* __restri
     c += is[j]; l += len[j];
   }
   int tc, tl;
-  int r = lcnt[blockIdx.x] + ct_block_excl(c, wsum, &tc);
-  int st = llen[blockIdx.x] + ct_block_excl(l, wsum, &tl);
+  int r = lcnt[blockIdx.x] + block_prefix_sum<CT_THREADS>(c, wsum, &tc);
+  int st = llen[blockIdx.x] + block_prefix_sum<CT_THREADS>(l, wsum, &tl);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (!is[j]) continue;
@@ -478,8 +423,7 @@ static int contour_layout(const char* who, int32_t H, int32_t W, int32_t n_level
   L->L = n_levels;
   L->cap = max_vertices;
   L->eblk = (max_vertices + CT_NB - 1) / CT_NB;
-  int64_t at = 0;
-  auto take = [&at](int64_t bytes) { const int64_t o = at; at += (bytes + 15) & ~(int64_t)15; return o; };
+  ScratchTake take;
   const int64_t cap = max_vertices, words = (int64_t)n_levels * L->nq;
   L->q = take(npix * 4);       L->ok = take(npix);         L->mask = take(words * 4);   L->off4 = take(words * 4);
   L->counts = take((int64_t)n_levels * L->nblk * 4);
@@ -487,30 +431,17 @@ static int contour_layout(const char* who, int32_t H, int32_t W, int32_t n_level
   L->lead = take(cap * 4);     L->headof = take(cap * 4);  L->p0 = take(cap * 8);       L->p1 = take(cap * 8);
   L->ometa = take(cap * 4);
   L->lcnt = take((int64_t)L->eblk * 4);  L->llen = take((int64_t)L->eblk * 4);
-  L->bytes = at;
-  return INSAR_OK;
-}
-static int contour_check_buf(const char* who, const void* p, const char* what) {
-  if (!p) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer (%s)", who, what);
-  if (!insar_aligned16(p)) INSAR_FAIL(INSAR_E_ALIGN, "%s: %s not 16-byte aligned", who, what);
+  L->bytes = take.at;
   return INSAR_OK;
 }
 static int contour_check_lines(const char* who, const void* table, int32_t max_lines) {
   if (max_lines < 1 || max_lines > CT_MAX_CROSSINGS) INSAR_FAIL(INSAR_E_SHAPE, "%s: max_lines %d outside 1 .. 2^30", who, max_lines);
-  return contour_check_buf(who, table, "table");
+  return scene_check_buffer(who, "table", table);
 }
 static int contour_check_count(const char* who, int32_t n, const CtLayout& L) {
   if (n < 0 || n > L.cap) INSAR_FAIL(INSAR_E_SHAPE, "%s: n_crossings %d outside 0 .. max_vertices=%d", who, n, L.cap);
   return INSAR_OK;
 }
-static inline int contour_rounds(int n) {                        // ceil(log2 n)
-  int r = 0;
-  while (((int64_t)1 << r) < n) ++r;
-  return r;
-}
-template <typename T>
-static inline T* ct_at(void* scratch, int64_t off) { return reinterpret_cast<T*>((char*)scratch + off); }
-static inline unsigned ct_grid(int n, int per) { return (unsigned)((n + per - 1) / per); }
 
 extern "C" int insar_contour_scratch_bytes(int32_t H, int32_t W, int32_t n_levels, int32_t max_lines, int32_t max_vertices,
                                            int64_t* scratch_bytes, int64_t* table_bytes) {
@@ -525,7 +456,7 @@ extern "C" int insar_contour_scratch_bytes(int32_t H, int32_t W, int32_t n_level
 }
 
 extern "C" int insar_contour_launches(int32_t n_crossings) {
-  return n_crossings < 1 ? 5 : 11 + 2 * contour_rounds(n_crossings);
+  return n_crossings < 1 ? 5 : 11 + 2 * list_rounds(n_crossings);
 }
 
 template <typename T>
@@ -533,8 +464,8 @@ static void contour_launch_quantise(const void* raster, const uint8_t* valid, co
                                     double nodata, void* scratch, hipStream_t s) {
   const int vec = L.npix % 4 == 0;
   const int rvec = vec && insar_aligned16(raster), vvec = vec && valid && ((((uintptr_t)valid) & 3u) == 0);
-  hipLaunchKernelGGL(contour_quantise_kernel<T>, dim3(ct_grid(L.nq, CT_THREADS)), dim3(CT_THREADS), 0, s, (const T*)raster, valid,
-                     L.npix, rvec, vvec, vec, scale, has_nodata, nodata, ct_at<int>(scratch, L.q), ct_at<uint8_t>(scratch, L.ok));
+  hipLaunchKernelGGL(contour_quantise_kernel<T>, dim3(scene_blocks(L.nq, CT_THREADS)), dim3(CT_THREADS), 0, s, (const T*)raster, valid,
+                     L.npix, rvec, vvec, vec, scale, has_nodata, nodata, scratch_at<int>(scratch, L.q), scratch_at<uint8_t>(scratch, L.ok));
 }
 
 extern "C" int insar_contour_edges(const void* raster, int32_t elem_type, int32_t H, int32_t W, double scale, int32_t has_nodata,
@@ -552,18 +483,18 @@ extern "C" int insar_contour_edges(const void* raster, int32_t elem_type, int32_
   for (int l = 0; l < CT_MAX_LEVELS; ++l) lv.q[l] = l < n_levels ? levels_q[l] : INT_MAX;
   for (int l = 1; l < n_levels; ++l)
     if (lv.q[l] <= lv.q[l - 1]) INSAR_FAIL(INSAR_E_ARG, "%s: levels_q[%d] = %d is not above levels_q[%d] = %d", who, l, lv.q[l], l - 1, lv.q[l - 1]);
-  if (int rc = contour_check_buf(who, scratch, "scratch")) return rc;
-  if (int rc = contour_check_buf(who, table, "table")) return rc;
+  if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
+  if (int rc = scene_check_buffer(who, "table", table)) return rc;
   if (elem_type != INSAR_ZONAL_U8 && (((uintptr_t)raster) & 3u)) INSAR_FAIL(INSAR_E_ALIGN, "%s: raster not 4-byte aligned", who);
   hipStream_t s = (hipStream_t)stream;
   if (elem_type == INSAR_ZONAL_F32) contour_launch_quantise<float>(raster, valid, L, scale, has_nodata, nodata, scratch, s);
   else if (elem_type == INSAR_ZONAL_I32) contour_launch_quantise<int>(raster, valid, L, scale, has_nodata, nodata, scratch, s);
   else contour_launch_quantise<uint8_t>(raster, valid, L, scale, has_nodata, nodata, scratch, s);
   INSAR_CHECK_LAUNCH(who);
-  const int* q = ct_at<int>(scratch, L.q);
-  const uint8_t* ok = ct_at<uint8_t>(scratch, L.ok);
-  uint32_t* mask = ct_at<uint32_t>(scratch, L.mask);
-  int *off4 = ct_at<int>(scratch, L.off4), *counts = ct_at<int>(scratch, L.counts);
+  const int* q = scratch_at<int>(scratch, L.q);
+  const uint8_t* ok = scratch_at<uint8_t>(scratch, L.ok);
+  uint32_t* mask = scratch_at<uint32_t>(scratch, L.mask);
+  int *off4 = scratch_at<int>(scratch, L.off4), *counts = scratch_at<int>(scratch, L.counts);
   hipLaunchKernelGGL(contour_mark_kernel, dim3((unsigned)L.nblk), dim3(CT_THREADS), 0, s, q, ok, H, W, L.npix, L.nq, L.nblk, L.L, lv,
                      mask, counts);
   INSAR_CHECK_LAUNCH(who);
@@ -574,30 +505,24 @@ extern "C" int insar_contour_edges(const void* raster, int32_t elem_type, int32_
                      L.nq, L.nblk, (const int*)counts, off4);
   INSAR_CHECK_LAUNCH(who);
   hipLaunchKernelGGL(contour_link_kernel, dim3((unsigned)L.nblk, (unsigned)L.L), dim3(CT_THREADS), 0, s, q, ok, (const uint32_t*)mask,
-                     (const int*)off4, H, W, L.npix, L.nq, lv, L.cap, ct_at<int>(scratch, L.succ0), ct_at<int>(scratch, L.eid),
-                     ct_at<int2>(scratch, L.vert), ct_at<uint8_t>(scratch, L.head), ct_at<int2>(scratch, L.p0));
+                     (const int*)off4, H, W, L.npix, L.nq, lv, L.cap, scratch_at<int>(scratch, L.succ0), scratch_at<int>(scratch, L.eid),
+                     scratch_at<int2>(scratch, L.vert), scratch_at<uint8_t>(scratch, L.head), scratch_at<int2>(scratch, L.p0));
   INSAR_CHECK_LAUNCH(who);
   return INSAR_OK;
 }
 
-// The pair buffers: `link` fills p0; round r of `lead` reads p[r & 1] and writes the other; `cut` reads p[R & 1] and writes
-// the other; round r of `rank` goes on from there, so the final distances are in p1 whatever R is, and p0 is free for `lines`.
+// The pair buffers: `link` fills p0, `lead` runs from there, `cut` reads its result and writes the other buffer, `rank` goes on from
+// there: the final distances are in p1 whatever R is, and p0 is free for `lines` (list_rank.h).
 extern "C" int insar_contour_lead(int32_t H, int32_t W, int32_t n_levels, int32_t n_crossings, int32_t max_vertices, void* scratch,
                                   void* stream) {
   const char* who = "insar_contour_lead";
   CtLayout L;
   if (int rc = contour_layout(who, H, W, n_levels, max_vertices, &L)) return rc;
   if (int rc = contour_check_count(who, n_crossings, L)) return rc;
-  if (int rc = contour_check_buf(who, scratch, "scratch")) return rc;
+  if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   if (n_crossings == 0) return INSAR_OK;
-  int2* p[2] = {ct_at<int2>(scratch, L.p0), ct_at<int2>(scratch, L.p1)};
-  const int rounds = contour_rounds(n_crossings);
-  for (int r = 0; r < rounds; ++r) {
-    hipLaunchKernelGGL(contour_lead_round_kernel, dim3(ct_grid(n_crossings, CT_THREADS)), dim3(CT_THREADS), 0, (hipStream_t)stream,
-                       (const int2*)p[r & 1], p[(r & 1) ^ 1], n_crossings);
-    INSAR_CHECK_LAUNCH(who);
-  }
-  return INSAR_OK;
+  int2* const p[2] = {scratch_at<int2>(scratch, L.p0), scratch_at<int2>(scratch, L.p1)};
+  return list_lead<CT_THREADS>(p, 0, n_crossings, (hipStream_t)stream, who);
 }
 
 extern "C" int insar_contour_rank(int32_t H, int32_t W, int32_t n_levels, int32_t n_crossings, int32_t max_vertices, void* scratch,
@@ -606,23 +531,16 @@ extern "C" int insar_contour_rank(int32_t H, int32_t W, int32_t n_levels, int32_
   CtLayout L;
   if (int rc = contour_layout(who, H, W, n_levels, max_vertices, &L)) return rc;
   if (int rc = contour_check_count(who, n_crossings, L)) return rc;
-  if (int rc = contour_check_buf(who, scratch, "scratch")) return rc;
+  if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   if (n_crossings == 0) return INSAR_OK;
-  int2* p[2] = {ct_at<int2>(scratch, L.p0), ct_at<int2>(scratch, L.p1)};
-  const int rounds = contour_rounds(n_crossings);
-  int cur = rounds & 1;
-  const unsigned grid = ct_grid(n_crossings, CT_THREADS);
-  hipLaunchKernelGGL(contour_cut_kernel, dim3(grid), dim3(CT_THREADS), 0, (hipStream_t)stream, (const int2*)p[cur],
-                     (const int*)ct_at<int>(scratch, L.succ0), (const uint8_t*)ct_at<uint8_t>(scratch, L.head),
-                     ct_at<int>(scratch, L.lead), ct_at<int>(scratch, L.headof), p[cur ^ 1], n_crossings);
+  int2* const p[2] = {scratch_at<int2>(scratch, L.p0), scratch_at<int2>(scratch, L.p1)};
+  const int led = list_rounds(n_crossings) & 1;                  // where `lead` ended
+  hipLaunchKernelGGL(contour_cut_kernel, dim3(scene_blocks(n_crossings, CT_THREADS)), dim3(CT_THREADS), 0, (hipStream_t)stream,
+                     (const int2*)p[led], (const int*)scratch_at<int>(scratch, L.succ0),
+                     (const uint8_t*)scratch_at<uint8_t>(scratch, L.head), scratch_at<int>(scratch, L.lead),
+                     scratch_at<int>(scratch, L.headof), p[led ^ 1], n_crossings);
   INSAR_CHECK_LAUNCH(who);
-  cur ^= 1;
-  for (int r = 0; r < rounds; ++r, cur ^= 1) {
-    hipLaunchKernelGGL(contour_rank_round_kernel, dim3(grid), dim3(CT_THREADS), 0, (hipStream_t)stream, (const int2*)p[cur],
-                       p[cur ^ 1], n_crossings);
-    INSAR_CHECK_LAUNCH(who);
-  }
-  return INSAR_OK;
+  return list_rank<CT_THREADS>(p, led ^ 1, n_crossings, (hipStream_t)stream, who);
 }
 
 extern "C" int insar_contour_lines(int32_t H, int32_t W, int32_t n_levels, int32_t n_crossings, int32_t max_lines,
@@ -632,12 +550,12 @@ extern "C" int insar_contour_lines(int32_t H, int32_t W, int32_t n_levels, int32
   if (int rc = contour_layout(who, H, W, n_levels, max_vertices, &L)) return rc;
   if (int rc = contour_check_count(who, n_crossings, L)) return rc;
   if (int rc = contour_check_lines(who, table, max_lines)) return rc;
-  if (int rc = contour_check_buf(who, scratch, "scratch")) return rc;
+  if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const int nblk = (int)ct_grid(n_crossings, CT_NB);
-  int *lead = ct_at<int>(scratch, L.lead), *lcnt = ct_at<int>(scratch, L.lcnt), *llen = ct_at<int>(scratch, L.llen);
-  const uint8_t* head = ct_at<uint8_t>(scratch, L.head);
-  const int2* dist = ct_at<int2>(scratch, L.p1);
+  const int nblk = (int)scene_blocks(n_crossings, CT_NB);
+  int *lead = scratch_at<int>(scratch, L.lead), *lcnt = scratch_at<int>(scratch, L.lcnt), *llen = scratch_at<int>(scratch, L.llen);
+  const uint8_t* head = scratch_at<uint8_t>(scratch, L.head);
+  const int2* dist = scratch_at<int2>(scratch, L.p1);
   if (nblk > 0) {
     hipLaunchKernelGGL(contour_line_count_kernel, dim3((unsigned)nblk), dim3(CT_THREADS), 0, s, (const int*)lead, head, dist,
                        n_crossings, lcnt, llen);
@@ -647,8 +565,8 @@ extern "C" int insar_contour_lines(int32_t H, int32_t W, int32_t n_levels, int32
   INSAR_CHECK_LAUNCH(who);
   if (nblk > 0) {
     hipLaunchKernelGGL(contour_line_number_kernel, dim3((unsigned)nblk), dim3(CT_THREADS), 0, s, (const int*)lead, head, dist,
-                       (const int*)ct_at<int>(scratch, L.eid), n_crossings, 2 * L.npix, (const int*)lcnt, (const int*)llen,
-                       ct_at<int2>(scratch, L.p0), (InsarContourLine*)table, max_lines);
+                       (const int*)scratch_at<int>(scratch, L.eid), n_crossings, 2 * L.npix, (const int*)lcnt, (const int*)llen,
+                       scratch_at<int2>(scratch, L.p0), (InsarContourLine*)table, max_lines);
     INSAR_CHECK_LAUNCH(who);
   }
   return INSAR_OK;
@@ -663,14 +581,14 @@ extern "C" int insar_contour_write(int32_t H, int32_t W, int32_t n_levels, int32
   if (int rc = contour_check_lines(who, table, max_lines)) return rc;
   if (!vertices) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer (vertices)", who);
   if (((uintptr_t)vertices) & 7u) INSAR_FAIL(INSAR_E_ALIGN, "%s: vertices not 8-byte aligned", who);
-  if (int rc = contour_check_buf(who, scratch, "scratch")) return rc;
+  if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   if (n_crossings == 0) return INSAR_OK;
   hipStream_t s = (hipStream_t)stream;
-  const unsigned grid = ct_grid(n_crossings, CT_THREADS);
-  int* ometa = ct_at<int>(scratch, L.ometa);
-  hipLaunchKernelGGL(contour_scatter_kernel, dim3(grid), dim3(CT_THREADS), 0, s, (const int*)ct_at<int>(scratch, L.lead),
-                     (const int*)ct_at<int>(scratch, L.headof), (const int2*)ct_at<int2>(scratch, L.p1),
-                     (const int2*)ct_at<int2>(scratch, L.p0), (const int2*)ct_at<int2>(scratch, L.vert), n_crossings, ometa,
+  const unsigned grid = scene_blocks(n_crossings, CT_THREADS);
+  int* ometa = scratch_at<int>(scratch, L.ometa);
+  hipLaunchKernelGGL(contour_scatter_kernel, dim3(grid), dim3(CT_THREADS), 0, s, (const int*)scratch_at<int>(scratch, L.lead),
+                     (const int*)scratch_at<int>(scratch, L.headof), (const int2*)scratch_at<int2>(scratch, L.p1),
+                     (const int2*)scratch_at<int2>(scratch, L.p0), (const int2*)scratch_at<int2>(scratch, L.vert), n_crossings, ometa,
                      reinterpret_cast<int2*>(vertices));
   INSAR_CHECK_LAUNCH(who);
   hipLaunchKernelGGL(contour_reduce_kernel, dim3(grid), dim3(CT_THREADS), 0, s, (const int2*)reinterpret_cast<int2*>(vertices),

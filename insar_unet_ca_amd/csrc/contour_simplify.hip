@@ -40,8 +40,8 @@
 #include "block_scan.h"
 #include <limits.h>
 
-#define CS_THREADS BLOCK_SCAN_THREADS
-#define CS_WAVES BLOCK_SCAN_WAVES
+#define CS_THREADS 256
+#define CS_WAVES (CS_THREADS / INSAR_WAVE)
 #define CS_MAX_ROUNDS 4095
 #define CS_COUNTERS 4096
 #define CS_MAX_VERTICES (1 << 28)
@@ -221,7 +221,7 @@ __global__ void __launch_bounds__(CS_THREADS)
 csimplify_carry_kernel(CsBuf b, int nblk, int rd) {
   __shared__ int w[CS_WAVES];
   if (rd > 0 && b.changed[rd - 1] == 0) return;
-  block_carry(b.bmax, b.bmin, b.cmax, b.cmin, nblk, w);
+  block_carry<CS_THREADS>(b.bmax, b.bmin, b.cmax, b.cmin, nblk, w);
 }
 
 __global__ void __launch_bounds__(CS_THREADS)
@@ -233,8 +233,8 @@ csimplify_cross_kernel(CsBuf b, const int* __restrict__ verts, int nv, const Ins
   const bool live = i < nv;
   const bool kept = live && b.keep[i];
   int total;
-  int p = block_prefix_max(kept ? i : -1, w, &total);
-  int q = block_suffix_min(kept ? i : INT_MAX, w, &total);
+  int p = block_prefix_max<CS_THREADS>(kept ? i : -1, w, &total);
+  int q = block_suffix_min<CS_THREADS>(kept ? i : INT_MAX, w, &total);
   const int cp = b.cmax[blockIdx.x], cq = b.cmin[blockIdx.x];
   p = cp > p ? cp : p;
   q = cq < q ? cq : q;
@@ -329,7 +329,7 @@ csimplify_count_kernel(CsBuf b, int nv) {
   __shared__ int w[CS_WAVES];
   const int i = blockIdx.x * CS_THREADS + threadIdx.x;
   int total;
-  block_prefix_sum(i < nv ? (int)b.keep[i] : 0, w, &total);
+  block_prefix_sum<CS_THREADS>(i < nv ? (int)b.keep[i] : 0, w, &total);
   if (threadIdx.x == 0) b.bsum[blockIdx.x] = total;
 }
 
@@ -340,14 +340,7 @@ csimplify_scan_kernel(CsBuf b, int nblk, int nv, int nl, int max_rounds, InsarCo
   __shared__ int w[CS_WAVES];
   __shared__ int rounds;
   if (threadIdx.x == 0) rounds = 0;
-  int carry = 0, total;
-  for (int base = 0; base < nblk; base += CS_THREADS) {
-    const int j = base + (int)threadIdx.x;
-    const int v = j < nblk ? b.bsum[j] : 0;
-    const int ex = block_prefix_sum(v, w, &total);
-    if (j < nblk) b.bsum[j] = carry + ex;
-    carry += total;
-  }
+  const int carry = block_scan_array<CS_THREADS>(b.bsum, nblk, w);
   int mine = 0;
   for (int r = threadIdx.x; r < max_rounds; r += CS_THREADS) mine += b.changed[r] != 0;
   if (mine) atomicAdd(&rounds, mine);
@@ -371,7 +364,7 @@ csimplify_scatter_kernel(CsBuf b, const int* __restrict__ verts, int nv, int* __
   const int i = blockIdx.x * CS_THREADS + threadIdx.x;
   const int k = i < nv ? (int)b.keep[i] : 0;
   int total;
-  const int at = b.bsum[blockIdx.x] + block_prefix_sum(k, w, &total);
+  const int at = b.bsum[blockIdx.x] + block_prefix_sum<CS_THREADS>(k, w, &total);
   if (i >= nv) return;
   b.pos[i] = at;
   if (i == nv - 1) b.pos[nv] = at + k;

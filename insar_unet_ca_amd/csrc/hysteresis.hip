@@ -26,6 +26,7 @@
 // equal labels, and only the first lane of a run touches the table (regions_relabel_kernel's pattern).
 // Reproducibility: integer sums and maxima commute; the arrival order of the atomics changes nothing.
 #include "scene_common.h"
+#include "block_scan.h"
 #include <limits.h>
 
 #define HY_THREADS 256
@@ -40,25 +41,6 @@ static_assert(sizeof(InsarRegion) == 64 && sizeof(InsarHystRegion) == 80, "a kep
 __device__ __forceinline__ uint32_t hy_ordered_u32(float f) {
   const uint32_t u = __float_as_uint(f);
   return (u & 0x80000000u) ? ~u : (u ^ 0x80000000u);
-}
-
-__device__ __forceinline__ void hy_store_f32(float* p, int64_t i, int64_t n, bool vec, const float* v) {
-  if (vec) {
-    *reinterpret_cast<float4*>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (i + j < n) p[i + j] = v[j];
-  }
-}
-__device__ __forceinline__ void hy_store_u8(uint8_t* p, int64_t i, int64_t n, bool vec, const int* v) {
-  if (vec) {
-    *reinterpret_cast<uint32_t*>(p + i) = (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (i + j < n) p[i + j] = (uint8_t)v[j];
-  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -88,8 +70,8 @@ hyst_classify_kernel(const float* __restrict__ score, int planes, int64_t npix, 
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       if (!ok[j] || i + j >= npix) { c[j] = 0; best[j] = 0.f; }
-    hy_store_u8(cand, i, npix, full, c);
-    hy_store_f32(conf, i, npix, full, best);
+    quad_store_u8(cand, i, npix, full, c);
+    quad_store(conf, i, npix, full, best);
   }
 }
 
@@ -168,17 +150,10 @@ hyst_keep_kernel(const InsarRegion* __restrict__ table, const HySeed* __restrict
     s.n_seed = 0; s.peak_key = 0ull;
     if (r <= n) s = seeds[r];
     const int keep = r <= n && s.n_seed >= min_seeds;
-    const int incl = wave_incl_scan(keep);
-    if ((threadIdx.x & (INSAR_WAVE - 1)) == INSAR_WAVE - 1) wsum[threadIdx.x / INSAR_WAVE] = incl;
-    __syncthreads();
-    int woff = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < HY_KEEP_THREADS / INSAR_WAVE; ++w) {
-      if (w < (int)(threadIdx.x / INSAR_WAVE)) woff += wsum[w];
-      total += wsum[w];
-    }
+    int total;
+    const int before = block_prefix_sum<HY_KEEP_THREADS>(keep, wsum, &total);
     if (r <= n) {
-      const int id = keep ? carry + woff + incl : 0;             // 1 <= id <= r: the compact table is never overrun
+      const int id = keep ? carry + before + 1 : 0;              // 1 <= id <= r: the compact table is never overrun
       remap[r] = id;
       if (keep) {
         const int4* src = reinterpret_cast<const int4*>(table + r);
@@ -189,7 +164,6 @@ hyst_keep_kernel(const InsarRegion* __restrict__ table, const HySeed* __restrict
       }
     }
     carry += total;
-    __syncthreads();
   }
   if (threadIdx.x == 0) remap[0] = 0;
   if (threadIdx.x < 5) {                                         // header record: {N', N, 0, ...}
@@ -219,7 +193,7 @@ hyst_apply_kernel(int* __restrict__ labels, const uint8_t* __restrict__ cand, co
       if (!o[j]) c[j] = 0;
     }
     quad_store(labels, i, npix, vec, o);
-    hy_store_u8(mask, i, npix, vec, c);
+    quad_store_u8(mask, i, npix, vec, c);
   }
 }
 
@@ -227,7 +201,6 @@ hyst_apply_kernel(int* __restrict__ labels, const uint8_t* __restrict__ cand, co
 // host side
 // ---------------------------------------------------------------------------------------------
 struct HyLayout { int64_t npix, seed_bytes, off_remap, scratch_bytes, table_bytes; };
-static inline int64_t hy_align16(int64_t b) { return (b + 15) & ~(int64_t)15; }
 
 static int hyst_layout(const char* who, int32_t H, int32_t W, int32_t max_regions, HyLayout* L) {
   if (H < 1 || W < 1) INSAR_FAIL(INSAR_E_SHAPE, "%s: empty scene %d x %d", who, H, W);
@@ -238,21 +211,10 @@ static int hyst_layout(const char* who, int32_t H, int32_t W, int32_t max_region
   L->npix = npix;
   L->seed_bytes = recs * (int64_t)sizeof(HySeed);
   L->off_remap = L->seed_bytes;
-  L->scratch_bytes = L->off_remap + hy_align16(recs * 4);
+  L->scratch_bytes = L->off_remap + insar_align16(recs * 4);
   L->table_bytes = recs * (int64_t)sizeof(InsarHystRegion);
   return INSAR_OK;
 }
-static int hyst_check_buffer(const char* who, const char* what, const void* p) {
-  if (!p) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer (%s)", who, what);
-  if (!insar_aligned16(p)) INSAR_FAIL(INSAR_E_ALIGN, "%s: %s not 16-byte aligned", who, what);
-  return INSAR_OK;
-}
-static int hyst_check_map(const char* who, const char* what, const void* p, unsigned align) {
-  if (!p) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer (%s)", who, what);
-  if (((uintptr_t)p) & (align - 1u)) INSAR_FAIL(INSAR_E_ALIGN, "%s: %s not %u-byte aligned", who, what, align);
-  return INSAR_OK;
-}
-static inline dim3 hy_grid(int64_t items) { return dim3(insar_grid_cap((items + HY_THREADS - 1) / HY_THREADS)); }
 static inline bool hy_aligned4(const void* p) { return (((uintptr_t)p) & 3u) == 0; }
 
 extern "C" int insar_hyst_scratch_bytes(int32_t H, int32_t W, int32_t max_regions, int64_t* scratch_bytes, int64_t* table_bytes) {
@@ -268,15 +230,15 @@ extern "C" int insar_hyst_scratch_bytes(int32_t H, int32_t W, int32_t max_region
 extern "C" int insar_hyst_classify(const float* score, int32_t planes, int32_t H, int32_t W, const float* thresholds,
                                    const uint8_t* valid, uint8_t* cand, float* conf, void* stream) {
   const char* who = "insar_hyst_classify";
-  if (int rc = hyst_check_map(who, "score", score, 4)) return rc;
-  if (int rc = hyst_check_map(who, "thresholds", thresholds, 4)) return rc;
-  if (int rc = hyst_check_map(who, "cand", cand, 1)) return rc;
-  if (int rc = hyst_check_map(who, "conf", conf, 4)) return rc;
+  if (int rc = scene_check_map(who, "score", score, 4)) return rc;
+  if (int rc = scene_check_map(who, "thresholds", thresholds, 4)) return rc;
+  if (int rc = scene_check_map(who, "cand", cand, 1)) return rc;
+  if (int rc = scene_check_map(who, "conf", conf, 4)) return rc;
   HyLayout L;
   if (int rc = hyst_layout(who, H, W, 1, &L)) return rc;
   if (planes < 1 || planes > HY_MAX_PLANES) INSAR_FAIL(INSAR_E_SHAPE, "%s: %d planes outside 1..%d", who, planes, HY_MAX_PLANES);
   const int al = insar_aligned16(score) && insar_aligned16(conf) && hy_aligned4(cand) && hy_aligned4(valid);
-  hipLaunchKernelGGL(hyst_classify_kernel, hy_grid((L.npix + 3) / 4), dim3(HY_THREADS), 0, (hipStream_t)stream, score, (int)planes,
+  hipLaunchKernelGGL(hyst_classify_kernel, scene_grid((L.npix + 3) / 4, HY_THREADS), dim3(HY_THREADS), 0, (hipStream_t)stream, score, (int)planes,
                      L.npix, al, thresholds, valid, cand, conf);
   INSAR_CHECK_LAUNCH(who);
   return INSAR_OK;
@@ -285,19 +247,19 @@ extern "C" int insar_hyst_classify(const float* score, int32_t planes, int32_t H
 extern "C" int insar_hyst_seeds(const int32_t* labels, const uint8_t* cand, const float* conf, const float* thresholds, int32_t H,
                                 int32_t W, int32_t max_regions, void* scratch, void* stream) {
   const char* who = "insar_hyst_seeds";
-  if (int rc = hyst_check_map(who, "labels", labels, 4)) return rc;
-  if (int rc = hyst_check_map(who, "cand", cand, 1)) return rc;
-  if (int rc = hyst_check_map(who, "conf", conf, 4)) return rc;
-  if (int rc = hyst_check_map(who, "thresholds", thresholds, 4)) return rc;
+  if (int rc = scene_check_map(who, "labels", labels, 4)) return rc;
+  if (int rc = scene_check_map(who, "cand", cand, 1)) return rc;
+  if (int rc = scene_check_map(who, "conf", conf, 4)) return rc;
+  if (int rc = scene_check_map(who, "thresholds", thresholds, 4)) return rc;
   HyLayout L;
   if (int rc = hyst_layout(who, H, W, max_regions, &L)) return rc;
-  if (int rc = hyst_check_buffer(who, "scratch", scratch)) return rc;
+  if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int64_t chunks = L.seed_bytes / 16;
-  hipLaunchKernelGGL(hyst_clear_kernel, hy_grid(chunks), dim3(HY_THREADS), 0, s, (int4*)scratch, chunks);
+  hipLaunchKernelGGL(hyst_clear_kernel, scene_grid(chunks, HY_THREADS), dim3(HY_THREADS), 0, s, (int4*)scratch, chunks);
   INSAR_CHECK_LAUNCH(who);
   const int vec = (L.npix % 4 == 0) && insar_aligned16(labels) && insar_aligned16(conf) && hy_aligned4(cand);
-  hipLaunchKernelGGL(hyst_seeds_kernel, hy_grid((L.npix + 3) / 4), dim3(HY_THREADS), 0, s, (const int*)labels, cand, conf, thresholds,
+  hipLaunchKernelGGL(hyst_seeds_kernel, scene_grid((L.npix + 3) / 4, HY_THREADS), dim3(HY_THREADS), 0, s, (const int*)labels, cand, conf, thresholds,
                      L.npix, vec, (int)max_regions, (HySeed*)scratch);
   INSAR_CHECK_LAUNCH(who);
   return INSAR_OK;
@@ -305,12 +267,12 @@ extern "C" int insar_hyst_seeds(const int32_t* labels, const uint8_t* cand, cons
 
 extern "C" int insar_hyst_keep(const void* regions, int64_t min_seeds, int32_t max_regions, void* scratch, void* table, void* stream) {
   const char* who = "insar_hyst_keep";
-  if (int rc = hyst_check_buffer(who, "regions", regions)) return rc;
+  if (int rc = scene_check_buffer(who, "regions", regions)) return rc;
   HyLayout L;
   if (int rc = hyst_layout(who, 1, 1, max_regions, &L)) return rc;
   if (min_seeds < 1) INSAR_FAIL(INSAR_E_ARG, "%s: min_seeds %lld < 1", who, (long long)min_seeds);
-  if (int rc = hyst_check_buffer(who, "scratch", scratch)) return rc;
-  if (int rc = hyst_check_buffer(who, "table", table)) return rc;
+  if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
+  if (int rc = scene_check_buffer(who, "table", table)) return rc;
   if (table == regions) INSAR_FAIL(INSAR_E_ARG, "%s: the compact table must not be the region table", who);
   hipLaunchKernelGGL(hyst_keep_kernel, dim3(1), dim3(HY_KEEP_THREADS), 0, (hipStream_t)stream, (const InsarRegion*)regions,
                      (const HySeed*)scratch, (long long)min_seeds, (int)max_regions, (int*)((char*)scratch + L.off_remap),
@@ -322,14 +284,14 @@ extern "C" int insar_hyst_keep(const void* regions, int64_t min_seeds, int32_t m
 extern "C" int insar_hyst_apply(const uint8_t* cand, int32_t H, int32_t W, int32_t max_regions, const void* scratch, int32_t* labels,
                                 uint8_t* mask, void* stream) {
   const char* who = "insar_hyst_apply";
-  if (int rc = hyst_check_map(who, "cand", cand, 1)) return rc;
-  if (int rc = hyst_check_map(who, "labels", labels, 4)) return rc;
-  if (int rc = hyst_check_map(who, "mask", mask, 1)) return rc;
+  if (int rc = scene_check_map(who, "cand", cand, 1)) return rc;
+  if (int rc = scene_check_map(who, "labels", labels, 4)) return rc;
+  if (int rc = scene_check_map(who, "mask", mask, 1)) return rc;
   HyLayout L;
   if (int rc = hyst_layout(who, H, W, max_regions, &L)) return rc;
-  if (int rc = hyst_check_buffer(who, "scratch", scratch)) return rc;
+  if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   const int vec = (L.npix % 4 == 0) && insar_aligned16(labels) && hy_aligned4(cand) && hy_aligned4(mask);
-  hipLaunchKernelGGL(hyst_apply_kernel, hy_grid((L.npix + 3) / 4), dim3(HY_THREADS), 0, (hipStream_t)stream, (int*)labels, cand,
+  hipLaunchKernelGGL(hyst_apply_kernel, scene_grid((L.npix + 3) / 4, HY_THREADS), dim3(HY_THREADS), 0, (hipStream_t)stream, (int*)labels, cand,
                      (const int*)((const char*)scratch + L.off_remap), L.npix, vec, (int)max_regions, mask);
   INSAR_CHECK_LAUNCH(who);
   return INSAR_OK;

@@ -29,6 +29,8 @@
 // Capacity: no kernel writes an edge slot >= max_edges, a record > max_rings or a vertex >= max_vertices; lead / rank / rings /
 // write take the edge count read back from the header and refuse one above max_edges.
 #include "scene_common.h"
+#include "block_scan.h"
+#include "list_rank.h"
 #include <limits.h>
 
 #define OL_THREADS 256
@@ -38,28 +40,11 @@
 #define OL_MAX_PIX ((int64_t)1 << 29)
 
 static_assert(sizeof(InsarRing) == 48, "InsarRing is three 16-byte stores");
-static_assert(OL_THREADS == 4 * INSAR_WAVE, "four waves per work-group in ol_block_excl");
 // int32 slots of the header record (InsarRing: area2 0-1, label 2, leader 3, start 4, count 5, edges 6, ...)
 #define OL_HDR_RINGS 2
 #define OL_HDR_VERTS 5
 #define OL_HDR_EDGES 6
 
-// exclusive prefix of v over the work-group's threads; *total is the work-group's sum. wsum: OL_THREADS / INSAR_WAVE ints of LDS.
-__device__ __forceinline__ int ol_block_excl(int v, int* wsum, int* total) {
-  const int lane = threadIdx.x & (INSAR_WAVE - 1), wave = threadIdx.x / INSAR_WAVE;
-  const int incl = wave_incl_scan(v, lane);
-  if (lane == INSAR_WAVE - 1) wsum[wave] = incl;
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < OL_THREADS / INSAR_WAVE; ++w) {
-    if (w < wave) off += wsum[w];
-    tot += wsum[w];
-  }
-  *total = tot;
-  __syncthreads();                                               // wsum is free again
-  return off + incl - v;
-}
 __device__ __forceinline__ int ol_below(int mask, int s) { return __popc(mask & ((1 << s) - 1)); }
 
 // ---------------------------------------------------------------------------------------------
@@ -96,7 +81,7 @@ outline_mark_kernel(const int* __restrict__ labels, int H, int W, int npix, int 
     }
   }
   int total;
-  ol_block_excl(__popc(m4), wsum, &total);
+  block_prefix_sum<OL_THREADS>(__popc(m4), wsum, &total);
   if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
@@ -104,27 +89,9 @@ outline_mark_kernel(const int* __restrict__ labels, int H, int W, int npix, int 
 // `clear`: the other slots of the header are zeroed first (the first scan of a call).
 __global__ void __launch_bounds__(OL_SCAN_THREADS)
 outline_scan_kernel(int* __restrict__ a, int* __restrict__ b, int nblk, int* __restrict__ hdr, int slot_a, int slot_b, int clear) {
-  __shared__ int wa[OL_SCAN_THREADS / INSAR_WAVE], wb[OL_SCAN_THREADS / INSAR_WAVE];
-  int carry_a = 0, carry_b = 0;                                  // every thread keeps the same running totals (< 2^31)
-  for (int base = 0; base < nblk; base += OL_SCAN_THREADS) {
-    const int i = base + threadIdx.x;
-    const int va = i < nblk ? a[i] : 0, vb = (b && i < nblk) ? b[i] : 0;
-    const int ia = wave_incl_scan(va), ib = wave_incl_scan(vb);
-    if ((threadIdx.x & (INSAR_WAVE - 1)) == INSAR_WAVE - 1) { wa[threadIdx.x / INSAR_WAVE] = ia; wb[threadIdx.x / INSAR_WAVE] = ib; }
-    __syncthreads();
-    int oa = 0, ta = 0, ob = 0, tb = 0;
-#pragma unroll
-    for (int w = 0; w < OL_SCAN_THREADS / INSAR_WAVE; ++w) {
-      if (w < (int)(threadIdx.x / INSAR_WAVE)) { oa += wa[w]; ob += wb[w]; }
-      ta += wa[w]; tb += wb[w];
-    }
-    if (i < nblk) {
-      a[i] = carry_a + oa + ia - va;
-      if (b) b[i] = carry_b + ob + ib - vb;
-    }
-    carry_a += ta; carry_b += tb;
-    __syncthreads();
-  }
+  __shared__ int w[OL_SCAN_THREADS / INSAR_WAVE];
+  const int carry_a = block_scan_array<OL_SCAN_THREADS>(a, nblk, w);
+  const int carry_b = b ? block_scan_array<OL_SCAN_THREADS>(b, nblk, w) : 0;
   if (threadIdx.x < (int)(sizeof(InsarRing) / 4)) {
     const int t = threadIdx.x;
     if (t == slot_a) hdr[t] = carry_a;
@@ -141,7 +108,7 @@ outline_offsets_kernel(const uint8_t* __restrict__ mask, int npix, int vec, cons
   quad_load_u8(mask, i, npix, vec && i < npix, 0, m);
   const int c = __popc(m[0]) + __popc(m[1]) + __popc(m[2]) + __popc(m[3]);
   int total;
-  int o = counts[blockIdx.x] + ol_block_excl(c, wsum, &total);
+  int o = counts[blockIdx.x] + block_prefix_sum<OL_THREADS>(c, wsum, &total);
   int out[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) { out[j] = o; o += __popc(m[j]); }
@@ -187,17 +154,8 @@ outline_link_kernel(const int* __restrict__ labels, const uint8_t* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------
-// lead / rank: one round per launch, from one pair buffer into the other
+// lead / rank: the rounds are list_rank.h's; `cut` between them
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(OL_THREADS)
-outline_lead_round_kernel(const int2* __restrict__ in, int2* __restrict__ out, int n) {
-  const int k = blockIdx.x * OL_THREADS + threadIdx.x;
-  if (k >= n) return;
-  const int2 a = in[k];
-  const int2 b = in[a.x];
-  out[k] = make_int2(b.x, min(a.y, b.y));
-}
-
 __global__ void __launch_bounds__(OL_THREADS)
 outline_cut_kernel(const int2* __restrict__ in, const int* __restrict__ succ0, int* __restrict__ lead, int2* __restrict__ out, int n) {
   const int k = blockIdx.x * OL_THREADS + threadIdx.x;
@@ -205,18 +163,6 @@ outline_cut_kernel(const int2* __restrict__ in, const int* __restrict__ succ0, i
   const int m = in[k].y, s = succ0[k];
   lead[k] = m;
   out[k] = s == m ? make_int2(-1, 0) : make_int2(s, 1);          // the successor of a ring's last edge is its leader
-}
-
-__global__ void __launch_bounds__(OL_THREADS)
-outline_rank_round_kernel(const int2* __restrict__ in, int2* __restrict__ out, int n) {
-  const int k = blockIdx.x * OL_THREADS + threadIdx.x;
-  if (k >= n) return;
-  int2 a = in[k];
-  if (a.x >= 0) {
-    const int2 b = in[a.x];
-    a = make_int2(b.x, a.y + b.y);
-  }
-  out[k] = a;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -234,8 +180,8 @@ outline_ring_count_kernel(const int* __restrict__ lead, const int2* __restrict__
     if (k < n && lead[k] == k) { ++c; l += dist[k].y + 1; }
   }
   int tc, tl;
-  ol_block_excl(c, wsum, &tc);
-  ol_block_excl(l, wsum, &tl);
+  block_prefix_sum<OL_THREADS>(c, wsum, &tc);
+  block_prefix_sum<OL_THREADS>(l, wsum, &tl);
   if (threadIdx.x == 0) { rcnt[blockIdx.x] = tc; rlen[blockIdx.x] = tl; }
 }
 
@@ -255,8 +201,8 @@ outline_ring_number_kernel(const int* __restrict__ lead, const int2* __restrict_
     c += is[j]; l += len[j];
   }
   int tc, tl;
-  int r = rcnt[blockIdx.x] + ol_block_excl(c, wsum, &tc);
-  int st = rlen[blockIdx.x] + ol_block_excl(l, wsum, &tl);
+  int r = rcnt[blockIdx.x] + block_prefix_sum<OL_THREADS>(c, wsum, &tc);
+  int st = rlen[blockIdx.x] + block_prefix_sum<OL_THREADS>(l, wsum, &tl);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (!is[j]) continue;
@@ -323,7 +269,7 @@ outline_reduce_kernel(const int2* __restrict__ overt, const int* __restrict__ om
     if (x1 > __hip_atomic_load(&r->x1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&r->x1, x1);
   }
   int total;
-  ol_block_excl(flag, wsum, &total);
+  block_prefix_sum<OL_THREADS>(flag, wsum, &total);
   if (threadIdx.x == 0) ccnt[blockIdx.x] = total;
 }
 
@@ -335,7 +281,7 @@ outline_compact_kernel(const int2* __restrict__ overt, const int* __restrict__ o
   const int i = blockIdx.x * OL_THREADS + threadIdx.x;
   const int flag = i < n ? ocorner[i] : 0;
   int total;
-  const int o = ccnt[blockIdx.x] + ol_block_excl(flag, wsum, &total);
+  const int o = ccnt[blockIdx.x] + block_prefix_sum<OL_THREADS>(flag, wsum, &total);
   if (i >= n) return;
   const int key = ometa[i] >> 2;
   if ((i == 0 || (ometa[i - 1] >> 2) != key) && key < max_rings) rings[1 + key].start = o;
@@ -360,15 +306,14 @@ static int outline_layout(const char* who, int32_t H, int32_t W, int32_t max_edg
   L->cap = max_edges;
   L->eblk = (max_edges + OL_NB - 1) / OL_NB;
   L->cblk = (max_edges + OL_THREADS - 1) / OL_THREADS;
-  int64_t at = 0;
-  auto take = [&at](int64_t bytes) { const int64_t o = at; at += (bytes + 15) & ~(int64_t)15; return o; };
+  ScratchTake take;
   const int64_t cap = max_edges;
   L->mask = take(npix);        L->off = take(npix * 4);    L->counts = take((int64_t)L->nblk * 4);
   L->succ0 = take(cap * 4);    L->eid = take(cap * 4);     L->turn = take(cap);
   L->lead = take(cap * 4);     L->p0 = take(cap * 8);      L->p1 = take(cap * 8);
   L->overt = take(cap * 8);    L->ometa = take(cap * 4);   L->ocorner = take(cap);
   L->rcnt = take((int64_t)L->eblk * 4);  L->rlen = take((int64_t)L->eblk * 4);  L->ccnt = take((int64_t)L->cblk * 4);
-  L->bytes = at;
+  L->bytes = take.at;
   return INSAR_OK;
 }
 static int outline_check_buf(const char* who, const void* p, const char* what) {
@@ -384,14 +329,6 @@ static int outline_check_count(const char* who, int32_t n_edges, const OlLayout&
   if (n_edges < 0 || n_edges > L.cap) INSAR_FAIL(INSAR_E_SHAPE, "%s: n_edges %d outside 0 .. max_edges=%d", who, n_edges, L.cap);
   return INSAR_OK;
 }
-static inline int outline_rounds(int n) {                        // ceil(log2 n)
-  int r = 0;
-  while (((int64_t)1 << r) < n) ++r;
-  return r;
-}
-template <typename T>
-static inline T* ol_at(void* scratch, int64_t off) { return reinterpret_cast<T*>((char*)scratch + off); }
-static inline unsigned ol_grid(int n, int per) { return (unsigned)((n + per - 1) / per); }
 
 extern "C" int insar_outline_scratch_bytes(int32_t H, int32_t W, int32_t max_rings, int32_t max_edges, int64_t* scratch_bytes,
                                            int64_t* table_bytes) {
@@ -406,7 +343,7 @@ extern "C" int insar_outline_scratch_bytes(int32_t H, int32_t W, int32_t max_rin
 }
 
 extern "C" int insar_outline_launches(int32_t n_edges) {
-  return n_edges < 1 ? 6 : 12 + 2 * outline_rounds(n_edges);
+  return n_edges < 1 ? 6 : 12 + 2 * list_rounds(n_edges);
 }
 
 extern "C" int insar_outline_edges(const int32_t* labels, int32_t H, int32_t W, int32_t connectivity, int32_t max_edges,
@@ -422,8 +359,8 @@ extern "C" int insar_outline_edges(const int32_t* labels, int32_t H, int32_t W, 
   hipStream_t s = (hipStream_t)stream;
   const int vec = L.npix % 4 == 0;
   const int lvec = vec && insar_aligned16(labels);
-  uint8_t* mask = ol_at<uint8_t>(scratch, L.mask);
-  int *off = ol_at<int>(scratch, L.off), *counts = ol_at<int>(scratch, L.counts);
+  uint8_t* mask = scratch_at<uint8_t>(scratch, L.mask);
+  int *off = scratch_at<int>(scratch, L.off), *counts = scratch_at<int>(scratch, L.counts);
   hipLaunchKernelGGL(outline_mark_kernel, dim3((unsigned)L.nblk), dim3(OL_THREADS), 0, s, labels, H, W, L.npix, lvec, mask, counts);
   INSAR_CHECK_LAUNCH(who);
   hipLaunchKernelGGL(outline_scan_kernel, dim3(1), dim3(OL_SCAN_THREADS), 0, s, counts, (int*)nullptr, L.nblk, (int*)table,
@@ -431,15 +368,15 @@ extern "C" int insar_outline_edges(const int32_t* labels, int32_t H, int32_t W, 
   INSAR_CHECK_LAUNCH(who);
   hipLaunchKernelGGL(outline_offsets_kernel, dim3((unsigned)L.nblk), dim3(OL_THREADS), 0, s, mask, L.npix, vec, counts, off);
   INSAR_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(outline_link_kernel, dim3(ol_grid(L.npix, OL_THREADS)), dim3(OL_THREADS), 0, s, labels, mask, off, H, W,
-                     L.npix, connectivity == 8, L.cap, ol_at<int>(scratch, L.succ0), ol_at<int>(scratch, L.eid),
-                     ol_at<uint8_t>(scratch, L.turn), ol_at<int2>(scratch, L.p0));
+  hipLaunchKernelGGL(outline_link_kernel, dim3(scene_blocks(L.npix, OL_THREADS)), dim3(OL_THREADS), 0, s, labels, mask, off, H, W,
+                     L.npix, connectivity == 8, L.cap, scratch_at<int>(scratch, L.succ0), scratch_at<int>(scratch, L.eid),
+                     scratch_at<uint8_t>(scratch, L.turn), scratch_at<int2>(scratch, L.p0));
   INSAR_CHECK_LAUNCH(who);
   return INSAR_OK;
 }
 
-// The pair buffers: `link` fills p0; round r of `lead` reads p[r & 1] and writes the other; `cut` reads p[L & 1] and writes
-// the other; round r of `rank` goes on from there, so the final distances are in p1 whatever L is, and p0 is free for `rings`.
+// The pair buffers: `link` fills p0, `lead` runs from there, `cut` reads its result and writes the other buffer, `rank` goes on from
+// there: the final distances are in p1 whatever L is, and p0 is free for `rings` (list_rank.h).
 extern "C" int insar_outline_lead(int32_t H, int32_t W, int32_t n_edges, int32_t max_edges, void* scratch, void* stream) {
   const char* who = "insar_outline_lead";
   OlLayout L;
@@ -447,14 +384,8 @@ extern "C" int insar_outline_lead(int32_t H, int32_t W, int32_t n_edges, int32_t
   if (int rc = outline_check_count(who, n_edges, L)) return rc;
   if (int rc = outline_check_buf(who, scratch, "scratch")) return rc;
   if (n_edges == 0) return INSAR_OK;
-  int2* p[2] = {ol_at<int2>(scratch, L.p0), ol_at<int2>(scratch, L.p1)};
-  const int rounds = outline_rounds(n_edges);
-  for (int r = 0; r < rounds; ++r) {
-    hipLaunchKernelGGL(outline_lead_round_kernel, dim3(ol_grid(n_edges, OL_THREADS)), dim3(OL_THREADS), 0, (hipStream_t)stream,
-                       (const int2*)p[r & 1], p[(r & 1) ^ 1], n_edges);
-    INSAR_CHECK_LAUNCH(who);
-  }
-  return INSAR_OK;
+  int2* const p[2] = {scratch_at<int2>(scratch, L.p0), scratch_at<int2>(scratch, L.p1)};
+  return list_lead<OL_THREADS>(p, 0, n_edges, (hipStream_t)stream, who);
 }
 
 extern "C" int insar_outline_rank(int32_t H, int32_t W, int32_t n_edges, int32_t max_edges, void* scratch, void* stream) {
@@ -464,20 +395,13 @@ extern "C" int insar_outline_rank(int32_t H, int32_t W, int32_t n_edges, int32_t
   if (int rc = outline_check_count(who, n_edges, L)) return rc;
   if (int rc = outline_check_buf(who, scratch, "scratch")) return rc;
   if (n_edges == 0) return INSAR_OK;
-  int2* p[2] = {ol_at<int2>(scratch, L.p0), ol_at<int2>(scratch, L.p1)};
-  const int rounds = outline_rounds(n_edges);
-  int cur = rounds & 1;
-  const unsigned grid = ol_grid(n_edges, OL_THREADS);
-  hipLaunchKernelGGL(outline_cut_kernel, dim3(grid), dim3(OL_THREADS), 0, (hipStream_t)stream, (const int2*)p[cur],
-                     (const int*)ol_at<int>(scratch, L.succ0), ol_at<int>(scratch, L.lead), p[cur ^ 1], n_edges);
+  int2* const p[2] = {scratch_at<int2>(scratch, L.p0), scratch_at<int2>(scratch, L.p1)};
+  const int led = list_rounds(n_edges) & 1;                      // where `lead` ended
+  hipLaunchKernelGGL(outline_cut_kernel, dim3(scene_blocks(n_edges, OL_THREADS)), dim3(OL_THREADS), 0, (hipStream_t)stream,
+                     (const int2*)p[led], (const int*)scratch_at<int>(scratch, L.succ0), scratch_at<int>(scratch, L.lead), p[led ^ 1],
+                     n_edges);
   INSAR_CHECK_LAUNCH(who);
-  cur ^= 1;
-  for (int r = 0; r < rounds; ++r, cur ^= 1) {
-    hipLaunchKernelGGL(outline_rank_round_kernel, dim3(grid), dim3(OL_THREADS), 0, (hipStream_t)stream, (const int2*)p[cur],
-                       p[cur ^ 1], n_edges);
-    INSAR_CHECK_LAUNCH(who);
-  }
-  return INSAR_OK;
+  return list_rank<OL_THREADS>(p, led ^ 1, n_edges, (hipStream_t)stream, who);
 }
 
 extern "C" int insar_outline_rings(const int32_t* labels, int32_t H, int32_t W, int32_t n_edges, int32_t max_rings,
@@ -491,9 +415,9 @@ extern "C" int insar_outline_rings(const int32_t* labels, int32_t H, int32_t W, 
   if (int rc = outline_check_buf(who, scratch, "scratch")) return rc;
   if (((uintptr_t)labels) & 3u) INSAR_FAIL(INSAR_E_ALIGN, "%s: labels not 4-byte aligned", who);
   hipStream_t s = (hipStream_t)stream;
-  const int nblk = (int)ol_grid(n_edges, OL_NB);
-  int *lead = ol_at<int>(scratch, L.lead), *rcnt = ol_at<int>(scratch, L.rcnt), *rlen = ol_at<int>(scratch, L.rlen);
-  const int2* dist = ol_at<int2>(scratch, L.p1);
+  const int nblk = (int)scene_blocks(n_edges, OL_NB);
+  int *lead = scratch_at<int>(scratch, L.lead), *rcnt = scratch_at<int>(scratch, L.rcnt), *rlen = scratch_at<int>(scratch, L.rlen);
+  const int2* dist = scratch_at<int2>(scratch, L.p1);
   if (nblk > 0) {
     hipLaunchKernelGGL(outline_ring_count_kernel, dim3((unsigned)nblk), dim3(OL_THREADS), 0, s, (const int*)lead, dist, n_edges,
                        rcnt, rlen);
@@ -503,8 +427,8 @@ extern "C" int insar_outline_rings(const int32_t* labels, int32_t H, int32_t W, 
   INSAR_CHECK_LAUNCH(who);
   if (nblk > 0) {
     hipLaunchKernelGGL(outline_ring_number_kernel, dim3((unsigned)nblk), dim3(OL_THREADS), 0, s, (const int*)lead, dist,
-                       (const int*)ol_at<int>(scratch, L.eid), labels, n_edges, (const int*)rcnt, (const int*)rlen,
-                       ol_at<int2>(scratch, L.p0), (InsarRing*)table, max_rings);
+                       (const int*)scratch_at<int>(scratch, L.eid), labels, n_edges, (const int*)rcnt, (const int*)rlen,
+                       scratch_at<int2>(scratch, L.p0), (InsarRing*)table, max_rings);
     INSAR_CHECK_LAUNCH(who);
   }
   return INSAR_OK;
@@ -523,15 +447,15 @@ extern "C" int insar_outline_write(int32_t H, int32_t W, int32_t n_edges, int32_
   if (((uintptr_t)vertices) & 7u) INSAR_FAIL(INSAR_E_ALIGN, "%s: vertices not 8-byte aligned", who);
   if (int rc = outline_check_buf(who, scratch, "scratch")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const int nblk = (int)ol_grid(n_edges, OL_THREADS);
-  int2* overt = ol_at<int2>(scratch, L.overt);
-  int *ometa = ol_at<int>(scratch, L.ometa), *ccnt = ol_at<int>(scratch, L.ccnt);
-  uint8_t* ocorner = ol_at<uint8_t>(scratch, L.ocorner);
+  const int nblk = (int)scene_blocks(n_edges, OL_THREADS);
+  int2* overt = scratch_at<int2>(scratch, L.overt);
+  int *ometa = scratch_at<int>(scratch, L.ometa), *ccnt = scratch_at<int>(scratch, L.ccnt);
+  uint8_t* ocorner = scratch_at<uint8_t>(scratch, L.ocorner);
   if (nblk > 0) {
-    hipLaunchKernelGGL(outline_scatter_kernel, dim3((unsigned)nblk), dim3(OL_THREADS), 0, s, (const int*)ol_at<int>(scratch, L.lead),
-                       (const int2*)ol_at<int2>(scratch, L.p1), (const int2*)ol_at<int2>(scratch, L.p0),
-                       (const int*)ol_at<int>(scratch, L.succ0), (const int*)ol_at<int>(scratch, L.eid),
-                       (const uint8_t*)ol_at<uint8_t>(scratch, L.turn), n_edges, W, corners_only != 0, overt, ometa, ocorner);
+    hipLaunchKernelGGL(outline_scatter_kernel, dim3((unsigned)nblk), dim3(OL_THREADS), 0, s, (const int*)scratch_at<int>(scratch, L.lead),
+                       (const int2*)scratch_at<int2>(scratch, L.p1), (const int2*)scratch_at<int2>(scratch, L.p0),
+                       (const int*)scratch_at<int>(scratch, L.succ0), (const int*)scratch_at<int>(scratch, L.eid),
+                       (const uint8_t*)scratch_at<uint8_t>(scratch, L.turn), n_edges, W, corners_only != 0, overt, ometa, ocorner);
     INSAR_CHECK_LAUNCH(who);
     hipLaunchKernelGGL(outline_reduce_kernel, dim3((unsigned)nblk), dim3(OL_THREADS), 0, s, (const int2*)overt, (const int*)ometa,
                        (const uint8_t*)ocorner, n_edges, (InsarRing*)table, max_rings, ccnt);

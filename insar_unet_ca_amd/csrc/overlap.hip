@@ -139,11 +139,6 @@ static int overlap_capacity(const char* who, int64_t max_pairs, int64_t* capacit
   *capacity = c;
   return INSAR_OK;
 }
-static int overlap_check_buffer(const char* who, const char* what, const void* p) {
-  if (!p) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer (%s)", who, what);
-  if (!insar_aligned16(p)) INSAR_FAIL(INSAR_E_ALIGN, "%s: %s not 16-byte aligned", who, what);
-  return INSAR_OK;
-}
 
 extern "C" int insar_overlap_scratch_bytes(int64_t max_pairs, int64_t* table_bytes, int64_t* out_bytes) {
   const char* who = "insar_overlap_scratch_bytes";
@@ -157,8 +152,8 @@ extern "C" int insar_overlap_scratch_bytes(int64_t max_pairs, int64_t* table_byt
 
 extern "C" int insar_overlap_clear(void* table, void* out, int64_t max_pairs, void* stream) {
   const char* who = "insar_overlap_clear";
-  if (int rc = overlap_check_buffer(who, "table", table)) return rc;
-  if (int rc = overlap_check_buffer(who, "out", out)) return rc;
+  if (int rc = scene_check_buffer(who, "table", table)) return rc;
+  if (int rc = scene_check_buffer(who, "out", out)) return rc;
   int64_t cap;
   if (int rc = overlap_capacity(who, max_pairs, &cap)) return rc;
   const int64_t chunks = 1 + cap;
@@ -176,7 +171,7 @@ extern "C" int insar_overlap_count(const int32_t* pred, const int32_t* gt, const
   const int64_t npix = (int64_t)H * W;
   if (npix >= ((int64_t)1 << 31)) INSAR_FAIL(INSAR_E_SHAPE, "%s: scene %d x %d has 2^31 pixels or more", who, H, W);
   if (voidmap && (void_value < 0 || void_value > 255)) INSAR_FAIL(INSAR_E_ARG, "%s: void_value %d outside 0..255", who, void_value);
-  if (int rc = overlap_check_buffer(who, "table", table)) return rc;
+  if (int rc = scene_check_buffer(who, "table", table)) return rc;
   int64_t cap;
   if (int rc = overlap_capacity(who, max_pairs, &cap)) return rc;
   if ((((uintptr_t)pred) | ((uintptr_t)gt)) & 3u) INSAR_FAIL(INSAR_E_ALIGN, "%s: label map not 4-byte aligned", who);
@@ -191,8 +186,8 @@ extern "C" int insar_overlap_count(const int32_t* pred, const int32_t* gt, const
 
 extern "C" int insar_overlap_compact(const void* table, int64_t max_pairs, void* out, void* stream) {
   const char* who = "insar_overlap_compact";
-  if (int rc = overlap_check_buffer(who, "table", table)) return rc;
-  if (int rc = overlap_check_buffer(who, "out", out)) return rc;
+  if (int rc = scene_check_buffer(who, "table", table)) return rc;
+  if (int rc = scene_check_buffer(who, "out", out)) return rc;
   int64_t cap;
   if (int rc = overlap_capacity(who, max_pairs, &cap)) return rc;
   const OvHeader* hdr = (const OvHeader*)table;

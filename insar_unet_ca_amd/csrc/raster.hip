@@ -16,6 +16,7 @@
 // on the caller's crossing count: no record is written at or past `cap`, fill reads none there and ignores a record whose
 // row or column lies outside its planes.
 #include "scene_common.h"
+#include "block_scan.h"
 
 #define RS_THREADS 256
 #define RS_FILL_THREADS 1024
@@ -108,24 +109,8 @@ raster_count_kernel(const int* __restrict__ edges, int n_edges, int H, int lgR, 
 __global__ void __launch_bounds__(RS_FILL_THREADS)
 raster_scan_kernel(int* __restrict__ cnt, int* __restrict__ cur, int nb) {
   __shared__ int ws[RS_FILL_WAVES];
-  const int lane = threadIdx.x & (INSAR_WAVE - 1), wave = threadIdx.x / INSAR_WAVE;
-  int carry = 0;
-  for (int base = 0; base < nb; base += RS_FILL_THREADS) {                           // base + threadIdx.x < 2^31: nb <= 2^31 - 1024
-    const int i = base + threadIdx.x;
-    const int v = i < nb ? cnt[i] : 0;
-    const int incl = wave_incl_scan(v, lane);
-    if (lane == INSAR_WAVE - 1) ws[wave] = incl;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < RS_FILL_WAVES; ++w) {
-      if (w < wave) off += ws[w];
-      tot += ws[w];
-    }
-    if (i < nb) { const int x = carry + off + incl - v; cnt[i] = x; cur[i] = x; }
-    carry += tot;
-    __syncthreads();
-  }
+  const int carry = block_scan_array<RS_FILL_THREADS>(cnt, nb, ws);                  // base + threadIdx.x < 2^31: nb <= 2^31 - 1024
+  for (int i = threadIdx.x; i < nb; i += RS_FILL_THREADS) cur[i] = cnt[i];           // every thread copies what it wrote itself
   if (threadIdx.x == 0) cnt[nb] = carry;
 }
 
@@ -286,12 +271,11 @@ static int raster_layout(const char* who, int32_t H, int32_t W, int64_t max_cros
   while ((1 << L->lgR) < L->R) ++L->lgR;
   L->nb = (int)(((int64_t)H + L->R - 1) / L->R);
   L->cap = (int)max_crossings;
-  int64_t at = 0;
-  auto take = [&at](int64_t bytes) { const int64_t o = at; at += (bytes + 15) & ~(int64_t)15; return o; };
+  ScratchTake take;
   L->cnt = take(((int64_t)L->nb + 1) * 4);
   L->cur = take((int64_t)L->nb * 4);
   L->rec = take((max_crossings > 0 ? max_crossings : 1) * 8);
-  L->bytes = at;
+  L->bytes = take.at;
   return INSAR_OK;
 }
 

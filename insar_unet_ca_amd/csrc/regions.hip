@@ -19,6 +19,7 @@
 // Reproducibility: integers only (int64 sums, min / max boxes, confidence as sum of llrint(clamp(conf, 0, 1) * 2^30));
 // integer addition commutes, so the atomics' arrival order changes nothing.
 #include "scene_common.h"
+#include "block_scan.h"
 #include <limits.h>
 
 #define RG_THREADS 256
@@ -235,10 +236,9 @@ regions_count_kernel(const int* __restrict__ parent, const int* __restrict__ are
   quad_load(area, i, npix, vec && i < npix, 0, a);
 #pragma unroll
   for (int j = 0; j < 4; ++j) c += (i + j < npix && p[j] == i + j && (int64_t)a[j] >= min_area);
-  c = wave_incl_scan(c);
-  if ((threadIdx.x & (INSAR_WAVE - 1)) == INSAR_WAVE - 1) wsum[threadIdx.x / INSAR_WAVE] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  int total;
+  block_prefix_sum<RG_THREADS>(c, wsum, &total);
+  if (threadIdx.x == 0) counts[blockIdx.x] = total;
   // the table's records (the header is written by the scan): empty sums, an empty box
   int4* t4 = reinterpret_cast<int4*>(table + 1);
   for (int64_t r = blockIdx.x * (int64_t)RG_THREADS + threadIdx.x; r < max_regions; r += (int64_t)gridDim.x * RG_THREADS) {
@@ -252,23 +252,7 @@ regions_count_kernel(const int* __restrict__ parent, const int* __restrict__ are
 __global__ void __launch_bounds__(RG_SCAN_THREADS)
 regions_scan_kernel(int* __restrict__ counts, int nblk, InsarRegion* __restrict__ table) {
   __shared__ int wsum[RG_SCAN_THREADS / INSAR_WAVE];
-  int carry = 0;                                                 // every thread keeps the same running total (< 2^31)
-  for (int base = 0; base < nblk; base += RG_SCAN_THREADS) {
-    const int i = base + threadIdx.x;
-    const int v = i < nblk ? counts[i] : 0;
-    const int incl = wave_incl_scan(v);
-    if ((threadIdx.x & (INSAR_WAVE - 1)) == INSAR_WAVE - 1) wsum[threadIdx.x / INSAR_WAVE] = incl;
-    __syncthreads();
-    int woff = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < RG_SCAN_THREADS / INSAR_WAVE; ++w) {
-      if (w < (int)(threadIdx.x / INSAR_WAVE)) woff += wsum[w];
-      total += wsum[w];
-    }
-    if (i < nblk) counts[i] = carry + woff + incl - v;
-    carry += total;
-    __syncthreads();
-  }
+  const int carry = block_scan_array<RG_SCAN_THREADS>(counts, nblk, wsum);
   if (threadIdx.x < 4) {                                         // header record: {N, 0, ...}
     int4 h = make_int4(0, 0, 0, 0);
     if (threadIdx.x == 0) h.x = carry;
@@ -293,12 +277,8 @@ regions_number_kernel(const int* __restrict__ parent, int* __restrict__ area, co
     keep[j] = root[j] && (int64_t)a[j] >= min_area;
     c += keep[j];
   }
-  const int incl = wave_incl_scan(c);
-  const int wave = threadIdx.x / INSAR_WAVE;
-  if ((threadIdx.x & (INSAR_WAVE - 1)) == INSAR_WAVE - 1) wsum[wave] = incl;
-  __syncthreads();
-  int id = counts[blockIdx.x] + incl - c;
-  for (int w = 0; w < wave; ++w) id += wsum[w];
+  int total;
+  int id = counts[blockIdx.x] + block_prefix_sum<RG_THREADS>(c, wsum, &total);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (!root[j]) continue;                                      // other pixels keep the 0 that `tiles` wrote
@@ -343,13 +323,7 @@ regions_relabel_kernel(const int* __restrict__ parent, const int* __restrict__ i
         sc[j] = conf ? __float2ll_rn(fminf(fmaxf(f[j], 0.f), 1.f) * 1073741824.0f) : 0;
       }
       quad_store(labels, i, npix, vec, id);
-      if (vec) {
-        *reinterpret_cast<uint32_t*>(mask_out + i) = (uint32_t)m[0] | ((uint32_t)m[1] << 8) | ((uint32_t)m[2] << 16) | ((uint32_t)m[3] << 24);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (i + j < npix) mask_out[i + j] = (uint8_t)m[j];
-      }
+      quad_store_u8(mask_out, i, npix, vec, m);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) cnt[j] = id[j] > 0;
@@ -395,9 +369,9 @@ static int regions_layout(const char* who, int32_t H, int32_t W, RgLayout* L) {
   const int64_t npix = (int64_t)H * W;
   if (npix >= ((int64_t)1 << 31)) INSAR_FAIL(INSAR_E_SHAPE, "%s: scene %d x %d has 2^31 pixels or more", who, H, W);
   L->npix = npix;
-  L->seg = (npix * 4 + 15) & ~(int64_t)15;
+  L->seg = insar_align16(npix * 4);
   L->nblk = (npix + RG_NB - 1) / RG_NB;
-  L->bytes = 2 * L->seg + ((L->nblk * 4 + 15) & ~(int64_t)15);
+  L->bytes = 2 * L->seg + insar_align16(L->nblk * 4);
   L->nty = (H + RG_TH - 1) / RG_TH;
   L->ntx = (W + RG_TW - 1) / RG_TW;
   return INSAR_OK;

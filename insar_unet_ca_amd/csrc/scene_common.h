@@ -1,7 +1,8 @@
-// What the scene pipeline (scene.hip, regions.hip, augment.hip, overlap.hip, distance.hip, crops.hip) and the dropout kernel of
-// deeplab.hip share: the counter hash, the guarded four-element access, the wave primitives (runs of equal keys, scan,
-// max) and the image / label quads of the two gather kernels. Each file's kernels, launch geometry and argument checks are
-// its own.
+// What the scene tools (scene.hip, scene_valid.hip, regions.hip, augment.hip, overlap.hip, distance.hip, crops.hip, outline.hip,
+// skeleton.hip, raster.hip, zonal.hip, simplify.hip, contour_simplify.hip, split.hip, warp.hip, stack.hip, sieve.hip,
+// hysteresis.hip, contour.hip), the focal loss of focal.hip and the dropout kernel of deeplab.hip share: the counter hash, the guarded four-element access,
+// the wave primitives (runs of equal keys, scan, max), the image / label quads of the two gather kernels and the host side's
+// small change (scratch layout, grids, pointer checks). Each file's kernels, launch geometry and argument checks are its own.
 #pragma once
 #include "common.h"
 
@@ -55,6 +56,25 @@ __device__ __forceinline__ void quad_store(int* p, int64_t i, int64_t n, bool ve
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       if (i + j < n) p[i + j] = v[j];
+  }
+}
+
+__device__ __forceinline__ void quad_store(float* p, int64_t i, int64_t n, bool vec, const float* v) {
+  if (vec) {
+    *reinterpret_cast<float4*>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (i + j < n) p[i + j] = v[j];
+  }
+}
+__device__ __forceinline__ void quad_store_u8(uint8_t* p, int64_t i, int64_t n, bool vec, const int* v) {
+  if (vec) {
+    *reinterpret_cast<uint32_t*>(p + i) = (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (i + j < n) p[i + j] = (uint8_t)v[j];
   }
 }
 
@@ -145,4 +165,28 @@ __device__ __forceinline__ void quad_store_i64(int64_t* p, const int64_t* v) {  
 __device__ __forceinline__ void labels4_store_i64(int64_t* p, uint32_t u) {
   const int64_t v[4] = {(int64_t)(u & 0xffu), (int64_t)((u >> 8) & 0xffu), (int64_t)((u >> 16) & 0xffu), (int64_t)(u >> 24)};
   quad_store_i64(p, v);
+}
+
+// ---- host side: scratch layout, grids, pointer checks --------------------------------------------------------------------------
+static inline int64_t insar_align16(int64_t b) { return (b + 15) & ~(int64_t)15; }
+// bump allocator of a scratch layout: take(bytes) is the offset of the next 16-byte aligned piece, `at` the bytes taken so far
+struct ScratchTake {
+  int64_t at = 0;
+  int64_t operator()(int64_t bytes) { const int64_t o = at; at += insar_align16(bytes); return o; }
+};
+template <typename T>
+static inline T* scratch_at(void* scratch, int64_t off) { return reinterpret_cast<T*>((char*)scratch + off); }
+// work-groups of `per` items: all of them (n < 2^31), or capped for a grid-stride loop
+static inline unsigned scene_blocks(int n, int per) { return (unsigned)((n + per - 1) / per); }
+static inline dim3 scene_grid(int64_t items, int threads) { return dim3(insar_grid_cap((items + threads - 1) / threads)); }
+// a buffer of the library's own layout (16-byte aligned), a map at its element's alignment
+static inline int scene_check_buffer(const char* who, const char* what, const void* p) {
+  if (!p) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer (%s)", who, what);
+  if (!insar_aligned16(p)) INSAR_FAIL(INSAR_E_ALIGN, "%s: %s not 16-byte aligned", who, what);
+  return INSAR_OK;
+}
+static inline int scene_check_map(const char* who, const char* what, const void* p, unsigned align) {
+  if (!p) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer (%s)", who, what);
+  if (((uintptr_t)p) & (align - 1u)) INSAR_FAIL(INSAR_E_ALIGN, "%s: %s not %u-byte aligned", who, what, align);
+  return INSAR_OK;
 }

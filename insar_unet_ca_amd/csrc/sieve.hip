@@ -346,7 +346,6 @@ struct SvLayout {
   int64_t npix, cap, ctrl_words, regions;
   int64_t off_ctrl, off_up, off_nxt, off_area, off_cls, off_best, off_hdr, off_pairs, off_slots, bytes;
 };
-static inline int64_t sv_align16(int64_t b) { return (b + 15) & ~(int64_t)15; }
 
 static int sieve_layout(const char* who, int32_t H, int32_t W, int32_t max_regions, int64_t max_pairs, int32_t max_rounds, SvLayout* L) {
   if (H < 1 || W < 1) INSAR_FAIL(INSAR_E_SHAPE, "%s: empty scene %d x %d", who, H, W);
@@ -361,10 +360,10 @@ static int sieve_layout(const char* who, int32_t H, int32_t W, int32_t max_regio
   int64_t c = 2;
   while (c < 2 * max_pairs) c <<= 1;
   L->cap = c;
-  L->ctrl_words = sv_align16((SV_CTRL_WORDS + (int64_t)max_rounds) * 4) / 4;
+  L->ctrl_words = insar_align16((SV_CTRL_WORDS + (int64_t)max_rounds) * 4) / 4;
   L->regions = (int64_t)max_regions + 1;
-  const int64_t seg = sv_align16(L->regions * 4);
-  L->off_ctrl = sv_align16(npix);                                 // the remapped class map comes first
+  const int64_t seg = insar_align16(L->regions * 4);
+  L->off_ctrl = insar_align16(npix);                                 // the remapped class map comes first
   L->off_up = L->off_ctrl + L->ctrl_words * 4;                    // directly behind the control words: one read-back takes both
   L->off_nxt = L->off_up + seg;
   L->off_area = L->off_nxt + seg;
@@ -376,19 +375,6 @@ static int sieve_layout(const char* who, int32_t H, int32_t W, int32_t max_regio
   L->bytes = L->off_slots + L->cap * (int64_t)sizeof(SvSlot);
   return INSAR_OK;
 }
-static int sieve_check_buffer(const char* who, const char* what, const void* p) {
-  if (!p) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer (%s)", who, what);
-  if (!insar_aligned16(p)) INSAR_FAIL(INSAR_E_ALIGN, "%s: %s not 16-byte aligned", who, what);
-  return INSAR_OK;
-}
-static int sieve_check_map(const char* who, const char* what, const void* p, unsigned align) {
-  if (!p) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer (%s)", who, what);
-  if (((uintptr_t)p) & (align - 1u)) INSAR_FAIL(INSAR_E_ALIGN, "%s: %s not %u-byte aligned", who, what, align);
-  return INSAR_OK;
-}
-template <typename T>
-static inline T* sv_at(void* scratch, int64_t off) { return reinterpret_cast<T*>((char*)scratch + off); }
-static inline dim3 sv_grid(int64_t items) { return dim3(insar_grid_cap((items + SV_THREADS - 1) / SV_THREADS)); }
 
 extern "C" int insar_sieve_scratch_bytes(int32_t H, int32_t W, int32_t max_regions, int64_t max_pairs, int32_t max_rounds,
                                          int64_t* scratch_bytes, int64_t* ctrl_offset, int64_t* ctrl_bytes, int64_t* pairs_offset) {
@@ -406,19 +392,19 @@ extern "C" int insar_sieve_scratch_bytes(int32_t H, int32_t W, int32_t max_regio
 extern "C" int insar_sieve_remap(const uint8_t* mask, int32_t H, int32_t W, int32_t void_value, int32_t max_regions, int64_t max_pairs,
                                  int32_t max_rounds, void* scratch, void* stream) {
   const char* who = "insar_sieve_remap";
-  if (int rc = sieve_check_map(who, "mask", mask, 1)) return rc;
+  if (int rc = scene_check_map(who, "mask", mask, 1)) return rc;
   SvLayout L;
   if (int rc = sieve_layout(who, H, W, max_regions, max_pairs, max_rounds, &L)) return rc;
   if (void_value < -1 || void_value > 255) INSAR_FAIL(INSAR_E_ARG, "%s: void_value %d outside -1..255", who, void_value);
-  if (int rc = sieve_check_buffer(who, "scratch", scratch)) return rc;
+  if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  int* ctrl = sv_at<int>(scratch, L.off_ctrl);
+  int* ctrl = scratch_at<int>(scratch, L.off_ctrl);
   const int vec = (L.npix % 4 == 0) && ((((uintptr_t)mask) & 3u) == 0);
-  hipLaunchKernelGGL(sieve_remap_kernel, sv_grid((L.npix + 3) / 4), dim3(SV_THREADS), 0, s, mask, L.npix, vec, (int)void_value,
-                     sv_at<uint8_t>(scratch, 0), (int4*)ctrl, (int)(L.ctrl_words / 4));
+  hipLaunchKernelGGL(sieve_remap_kernel, scene_grid((L.npix + 3) / 4, SV_THREADS), dim3(SV_THREADS), 0, s, mask, L.npix, vec, (int)void_value,
+                     scratch_at<uint8_t>(scratch, 0), (int4*)ctrl, (int)(L.ctrl_words / 4));
   INSAR_CHECK_LAUNCH(who);
   if (void_value < 0) {
-    hipLaunchKernelGGL(sieve_badcls_kernel, sv_grid(L.npix), dim3(SV_THREADS), 0, s, mask, L.npix, ctrl);
+    hipLaunchKernelGGL(sieve_badcls_kernel, scene_grid(L.npix, SV_THREADS), dim3(SV_THREADS), 0, s, mask, L.npix, ctrl);
     INSAR_CHECK_LAUNCH(who);
   }
   return INSAR_OK;
@@ -427,25 +413,25 @@ extern "C" int insar_sieve_remap(const uint8_t* mask, int32_t H, int32_t W, int3
 extern "C" int insar_sieve_pairs(const int32_t* labels, int32_t H, int32_t W, int32_t max_label, int32_t max_regions,
                                  int64_t max_pairs, int32_t max_rounds, void* scratch, void* stream) {
   const char* who = "insar_sieve_pairs";
-  if (int rc = sieve_check_map(who, "labels", labels, 4)) return rc;
+  if (int rc = scene_check_map(who, "labels", labels, 4)) return rc;
   SvLayout L;
   if (int rc = sieve_layout(who, H, W, max_regions, max_pairs, max_rounds, &L)) return rc;
   if (max_label < 1) INSAR_FAIL(INSAR_E_ARG, "%s: max_label %d < 1", who, max_label);
-  if (int rc = sieve_check_buffer(who, "scratch", scratch)) return rc;
+  if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  int* hdr = sv_at<int>(scratch, L.off_hdr);
-  SvSlot* slots = sv_at<SvSlot>(scratch, L.off_slots);
-  const dim3 block(SV_THREADS), grid = sv_grid((L.npix + 3) / 4);
+  int* hdr = scratch_at<int>(scratch, L.off_hdr);
+  SvSlot* slots = scratch_at<SvSlot>(scratch, L.off_slots);
+  const dim3 block(SV_THREADS), grid = scene_grid((L.npix + 3) / 4, SV_THREADS);
   const unsigned int mask = (unsigned int)(L.cap - 1);
-  hipLaunchKernelGGL(sieve_clear_kernel, sv_grid(L.cap), block, 0, s, (int4*)slots, L.cap, (int4*)hdr);
+  hipLaunchKernelGGL(sieve_clear_kernel, scene_grid(L.cap, SV_THREADS), block, 0, s, (int4*)slots, L.cap, (int4*)hdr);
   INSAR_CHECK_LAUNCH(who);
   if (W % 4 == 0 && insar_aligned16(labels))
     hipLaunchKernelGGL(sieve_pairs_kernel<true>, grid, block, 0, s, (const int*)labels, H, W, max_label, hdr, slots, mask);
   else
     hipLaunchKernelGGL(sieve_pairs_kernel<false>, grid, block, 0, s, (const int*)labels, H, W, max_label, hdr, slots, mask);
   INSAR_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(sieve_compact_kernel, sv_grid(L.cap), block, 0, s, (const SvSlot*)slots, L.cap, max_pairs, hdr,
-                     sv_at<SvPair>(scratch, L.off_pairs));
+  hipLaunchKernelGGL(sieve_compact_kernel, scene_grid(L.cap, SV_THREADS), block, 0, s, (const SvSlot*)slots, L.cap, max_pairs, hdr,
+                     scratch_at<SvPair>(scratch, L.off_pairs));
   INSAR_CHECK_LAUNCH(who);
   return INSAR_OK;
 }
@@ -454,21 +440,21 @@ extern "C" int insar_sieve_rounds(const void* table, const uint8_t* mask, const 
                                   int32_t first_round, int32_t n_rounds, int32_t max_regions, int64_t max_pairs, int32_t max_rounds,
                                   void* scratch, void* stream) {
   const char* who = "insar_sieve_rounds";
-  if (int rc = sieve_check_buffer(who, "table", table)) return rc;
-  if (int rc = sieve_check_map(who, "mask", mask, 1)) return rc;
-  if (int rc = sieve_check_map(who, "thresholds", thresholds, 4)) return rc;
+  if (int rc = scene_check_buffer(who, "table", table)) return rc;
+  if (int rc = scene_check_map(who, "mask", mask, 1)) return rc;
+  if (int rc = scene_check_map(who, "thresholds", thresholds, 4)) return rc;
   SvLayout L;
   if (int rc = sieve_layout(who, H, W, max_regions, max_pairs, max_rounds, &L)) return rc;
-  if (int rc = sieve_check_buffer(who, "scratch", scratch)) return rc;
+  if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   if (first_round < 0 || n_rounds < 1 || (int64_t)first_round + n_rounds > max_rounds)
     INSAR_FAIL(INSAR_E_ARG, "%s: rounds %d..%d outside 0..%d", who, first_round, first_round + n_rounds, max_rounds);
   hipStream_t s = (hipStream_t)stream;
-  int *ctrl = sv_at<int>(scratch, L.off_ctrl), *up = sv_at<int>(scratch, L.off_up), *nxt = sv_at<int>(scratch, L.off_nxt);
-  int *area = sv_at<int>(scratch, L.off_area), *cls = sv_at<int>(scratch, L.off_cls);
-  const int* hdr = sv_at<int>(scratch, L.off_hdr);
-  unsigned long long* best = sv_at<unsigned long long>(scratch, L.off_best);
-  const SvPair* pairs = sv_at<SvPair>(scratch, L.off_pairs);
-  const dim3 block(SV_THREADS), pgrid = sv_grid(max_pairs), rgrid = sv_grid(L.regions);
+  int *ctrl = scratch_at<int>(scratch, L.off_ctrl), *up = scratch_at<int>(scratch, L.off_up), *nxt = scratch_at<int>(scratch, L.off_nxt);
+  int *area = scratch_at<int>(scratch, L.off_area), *cls = scratch_at<int>(scratch, L.off_cls);
+  const int* hdr = scratch_at<int>(scratch, L.off_hdr);
+  unsigned long long* best = scratch_at<unsigned long long>(scratch, L.off_best);
+  const SvPair* pairs = scratch_at<SvPair>(scratch, L.off_pairs);
+  const dim3 block(SV_THREADS), pgrid = scene_grid(max_pairs, SV_THREADS), rgrid = scene_grid(L.regions, SV_THREADS);
   if (first_round == 0) {
     hipLaunchKernelGGL(sieve_init_kernel, rgrid, block, 0, s, (const InsarRegion*)table, mask, hdr, max_regions, ctrl, up, nxt, area,
                        cls, best);
@@ -490,17 +476,17 @@ extern "C" int insar_sieve_rounds(const void* table, const uint8_t* mask, const 
 extern "C" int insar_sieve_apply(const int32_t* labels, const uint8_t* mask, int32_t H, int32_t W, int32_t max_regions,
                                  int64_t max_pairs, int32_t max_rounds, void* scratch, uint8_t* out, uint8_t* changed, void* stream) {
   const char* who = "insar_sieve_apply";
-  if (int rc = sieve_check_map(who, "labels", labels, 4)) return rc;
-  if (int rc = sieve_check_map(who, "mask", mask, 1)) return rc;
-  if (int rc = sieve_check_map(who, "out", out, 1)) return rc;
+  if (int rc = scene_check_map(who, "labels", labels, 4)) return rc;
+  if (int rc = scene_check_map(who, "mask", mask, 1)) return rc;
+  if (int rc = scene_check_map(who, "out", out, 1)) return rc;
   SvLayout L;
   if (int rc = sieve_layout(who, H, W, max_regions, max_pairs, max_rounds, &L)) return rc;
-  if (int rc = sieve_check_buffer(who, "scratch", scratch)) return rc;
+  if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   const int vec = (L.npix % 4 == 0) && insar_aligned16(labels) &&
                   (((((uintptr_t)mask) | ((uintptr_t)out) | ((uintptr_t)changed)) & 3u) == 0);
-  hipLaunchKernelGGL(sieve_apply_kernel, sv_grid((L.npix + 3) / 4), dim3(SV_THREADS), 0, (hipStream_t)stream, (const int*)labels, mask,
-                     L.npix, vec, max_regions, sv_at<int>(scratch, L.off_ctrl), (const int*)sv_at<int>(scratch, L.off_up),
-                     (const int*)sv_at<int>(scratch, L.off_cls), out, changed);
+  hipLaunchKernelGGL(sieve_apply_kernel, scene_grid((L.npix + 3) / 4, SV_THREADS), dim3(SV_THREADS), 0, (hipStream_t)stream, (const int*)labels, mask,
+                     L.npix, vec, max_regions, scratch_at<int>(scratch, L.off_ctrl), (const int*)scratch_at<int>(scratch, L.off_up),
+                     (const int*)scratch_at<int>(scratch, L.off_cls), out, changed);
   INSAR_CHECK_LAUNCH(who);
   return INSAR_OK;
 }

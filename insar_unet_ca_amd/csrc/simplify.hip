@@ -38,7 +38,6 @@
 
 #define SM_THREADS 256
 #define SM_WAVES (SM_THREADS / INSAR_WAVE)
-static_assert(SM_THREADS == BLOCK_SCAN_THREADS, "the scans of block_scan.h take one value per thread of the work-group");
 #define SM_MAX_ROUNDS 4095
 #define SM_COUNTERS 4096
 #define SM_MAX_VERTICES (1 << 28)
@@ -204,7 +203,7 @@ __global__ void __launch_bounds__(SM_THREADS)
 simplify_carry_kernel(SmBuf b, int nblk, int rd) {
   __shared__ int w[SM_WAVES];
   if (rd > 0 && b.changed[rd - 1] == 0) return;
-  block_carry(b.bmax, b.bmin, b.cmax, b.cmin, nblk, w);
+  block_carry<SM_THREADS>(b.bmax, b.bmin, b.cmax, b.cmin, nblk, w);
 }
 
 __global__ void __launch_bounds__(SM_THREADS)
@@ -216,8 +215,8 @@ simplify_cross_kernel(SmBuf b, const int* __restrict__ verts, int nv, const Insa
   const bool live = i < nv;
   const bool kept = live && b.keep[i];
   int total;
-  int p = block_prefix_max(kept ? i : -1, w, &total);
-  int q = block_suffix_min(kept ? i : INT_MAX, w, &total);
+  int p = block_prefix_max<SM_THREADS>(kept ? i : -1, w, &total);
+  int q = block_suffix_min<SM_THREADS>(kept ? i : INT_MAX, w, &total);
   const int cp = b.cmax[blockIdx.x], cq = b.cmin[blockIdx.x];
   p = cp > p ? cp : p;
   q = cq < q ? cq : q;
@@ -299,7 +298,7 @@ simplify_count_kernel(SmBuf b, int nv) {
   __shared__ int w[SM_WAVES];
   const int i = blockIdx.x * SM_THREADS + threadIdx.x;
   int total;
-  block_prefix_sum(i < nv ? (int)b.keep[i] : 0, w, &total);
+  block_prefix_sum<SM_THREADS>(i < nv ? (int)b.keep[i] : 0, w, &total);
   if (threadIdx.x == 0) b.bsum[blockIdx.x] = total;
 }
 
@@ -310,14 +309,7 @@ simplify_scan_kernel(SmBuf b, int nblk, int nv, int nr, int max_rounds, InsarRin
   __shared__ int w[SM_WAVES];
   __shared__ int rounds;
   if (threadIdx.x == 0) rounds = 0;
-  int carry = 0, total;
-  for (int base = 0; base < nblk; base += SM_THREADS) {
-    const int j = base + (int)threadIdx.x;
-    const int v = j < nblk ? b.bsum[j] : 0;
-    const int ex = block_prefix_sum(v, w, &total);
-    if (j < nblk) b.bsum[j] = carry + ex;
-    carry += total;
-  }
+  const int carry = block_scan_array<SM_THREADS>(b.bsum, nblk, w);
   int mine = 0;
   for (int r = threadIdx.x; r < max_rounds; r += SM_THREADS) mine += b.changed[r] != 0;
   if (mine) atomicAdd(&rounds, mine);
@@ -341,7 +333,7 @@ simplify_scatter_kernel(SmBuf b, const int* __restrict__ verts, int nv, int* __r
   const int i = blockIdx.x * SM_THREADS + threadIdx.x;
   const int k = i < nv ? (int)b.keep[i] : 0;
   int total;
-  const int at = b.bsum[blockIdx.x] + block_prefix_sum(k, w, &total);
+  const int at = b.bsum[blockIdx.x] + block_prefix_sum<SM_THREADS>(k, w, &total);
   if (i >= nv) return;
   b.pos[i] = at;
   if (i == nv - 1) b.pos[nv] = at + k;

@@ -25,6 +25,7 @@
 // Reproducibility: max, min and integer sums commute; which slot a pair lands in, and the order of the edge list, depend on
 // arrival order, but every result taken from them is a maximum or minimum under a total order.
 #include "scene_common.h"
+#include "block_scan.h"
 #include <limits.h>
 
 #define SP_THREADS 256
@@ -328,10 +329,9 @@ split_count_kernel(const int* __restrict__ piece, const int* __restrict__ bidx, 
   __shared__ int wsum[SP_THREADS / INSAR_WAVE];
   const int64_t i = (int64_t)blockIdx.x * SP_NB + threadIdx.x * 4;
   bool first[4];
-  int c = wave_incl_scan(sp_block_firsts(piece, bidx, i, npix, first));
-  if ((threadIdx.x & (INSAR_WAVE - 1)) == INSAR_WAVE - 1) wsum[threadIdx.x / INSAR_WAVE] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  int total;
+  block_prefix_sum<SP_THREADS>(sp_block_firsts(piece, bidx, i, npix, first), wsum, &total);
+  if (threadIdx.x == 0) counts[blockIdx.x] = total;
   // the table's records (the header is written by the scan): empty sums, an empty box
   int4* t4 = reinterpret_cast<int4*>(table + 1);
   for (int64_t r = blockIdx.x * (int64_t)SP_THREADS + threadIdx.x; r < max_regions; r += (int64_t)gridDim.x * SP_THREADS) {
@@ -346,23 +346,7 @@ split_count_kernel(const int* __restrict__ piece, const int* __restrict__ bidx, 
 __global__ void __launch_bounds__(SP_SCAN_THREADS)
 split_scan_kernel(int* __restrict__ counts, int nblk, int* __restrict__ ctrl, InsarSplitRegion* __restrict__ table) {
   __shared__ int wsum[SP_SCAN_THREADS / INSAR_WAVE];
-  int carry = 0;                                                   // every thread keeps the same running total (< 2^31)
-  for (int base = 0; base < nblk; base += SP_SCAN_THREADS) {
-    const int i = base + threadIdx.x;
-    const int v = i < nblk ? counts[i] : 0;
-    const int incl = wave_incl_scan(v);
-    if ((threadIdx.x & (INSAR_WAVE - 1)) == INSAR_WAVE - 1) wsum[threadIdx.x / INSAR_WAVE] = incl;
-    __syncthreads();
-    int woff = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < SP_SCAN_THREADS / INSAR_WAVE; ++w) {
-      if (w < (int)(threadIdx.x / INSAR_WAVE)) woff += wsum[w];
-      total += wsum[w];
-    }
-    if (i < nblk) counts[i] = carry + woff + incl - v;
-    carry += total;
-    __syncthreads();
-  }
+  const int carry = block_scan_array<SP_SCAN_THREADS>(counts, nblk, wsum);
   if (threadIdx.x == 0) {                                          // header record: {M, pairs, overflow, bad heights; raw basins}
     InsarSplitRegion hd = {};
     hd.area = carry;
@@ -383,12 +367,8 @@ split_number_kernel(const int* __restrict__ piece, const int* __restrict__ bidx,
   const int64_t i = (int64_t)blockIdx.x * SP_NB + threadIdx.x * 4;
   bool first[4];
   const int c = sp_block_firsts(piece, bidx, i, npix, first);
-  const int incl = wave_incl_scan(c);
-  const int wave = threadIdx.x / INSAR_WAVE;
-  if ((threadIdx.x & (INSAR_WAVE - 1)) == INSAR_WAVE - 1) wsum[wave] = incl;
-  __syncthreads();
-  int id = counts[blockIdx.x] + incl - c;
-  for (int w = 0; w < wave; ++w) id += wsum[w];
+  int total;
+  int id = counts[blockIdx.x] + block_prefix_sum<SP_THREADS>(c, wsum, &total);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (!first[j]) continue;
@@ -446,7 +426,6 @@ struct SpLayout {
   int64_t npix, seg, nblk, cap, ctrl_words;
   int64_t off_up, off_nxt, off_bidx, off_best, off_counts, off_ctrl, off_slots, off_edges, bytes;
 };
-static inline int64_t sp_align16(int64_t b) { return (b + 15) & ~(int64_t)15; }
 
 static int split_layout(const char* who, int32_t H, int32_t W, int64_t max_pairs, int32_t max_rounds, SpLayout* L) {
   if (H < 1 || W < 1) INSAR_FAIL(INSAR_E_SHAPE, "%s: empty scene %d x %d", who, H, W);
@@ -457,26 +436,21 @@ static int split_layout(const char* who, int32_t H, int32_t W, int64_t max_pairs
   if (max_rounds < 1 || max_rounds > SP_MAX_ROUNDS)
     INSAR_FAIL(INSAR_E_SHAPE, "%s: max_rounds %d outside 1..%d", who, max_rounds, SP_MAX_ROUNDS);
   L->npix = npix;
-  L->seg = sp_align16(npix * 4);
+  L->seg = insar_align16(npix * 4);
   L->nblk = (npix + SP_NB - 1) / SP_NB;
   int64_t c = 2;
   while (c < 2 * max_pairs) c <<= 1;
   L->cap = c;
-  L->ctrl_words = sp_align16((SP_CTRL_WORDS + (int64_t)max_rounds) * 4) / 4;
+  L->ctrl_words = insar_align16((SP_CTRL_WORDS + (int64_t)max_rounds) * 4) / 4;
   L->off_up = L->seg;
   L->off_nxt = 2 * L->seg;
   L->off_bidx = 3 * L->seg;
   L->off_best = 4 * L->seg;
   L->off_counts = 6 * L->seg;
-  L->off_ctrl = L->off_counts + sp_align16(L->nblk * 4);
+  L->off_ctrl = L->off_counts + insar_align16(L->nblk * 4);
   L->off_slots = L->off_ctrl + L->ctrl_words * 4;
   L->off_edges = L->off_slots + L->cap * (int64_t)sizeof(SpSlot);
   L->bytes = L->off_edges + max_pairs * (int64_t)sizeof(SpEdge);
-  return INSAR_OK;
-}
-static int split_check_buffer(const char* who, const char* what, const void* p) {
-  if (!p) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer (%s)", who, what);
-  if (!insar_aligned16(p)) INSAR_FAIL(INSAR_E_ALIGN, "%s: %s not 16-byte aligned", who, what);
   return INSAR_OK;
 }
 static int split_check_map(const char* who, const char* what, const void* p) {
@@ -484,9 +458,6 @@ static int split_check_map(const char* who, const char* what, const void* p) {
   if (((uintptr_t)p) & 3u) INSAR_FAIL(INSAR_E_ALIGN, "%s: %s not 4-byte aligned", who, what);
   return INSAR_OK;
 }
-template <typename T>
-static inline T* sp_at(void* scratch, int64_t off) { return reinterpret_cast<T*>((char*)scratch + off); }
-static inline dim3 sp_grid(int64_t items) { return dim3(insar_grid_cap((items + SP_THREADS - 1) / SP_THREADS)); }
 
 extern "C" int insar_split_scratch_bytes(int32_t H, int32_t W, int32_t max_regions, int64_t max_pairs, int32_t max_rounds,
                                          int64_t* scratch_bytes, int64_t* table_bytes, int64_t* ctrl_offset, int64_t* ctrl_bytes) {
@@ -509,25 +480,25 @@ extern "C" int insar_split_basins(const int32_t* labels, const int32_t* height, 
   if (int rc = split_check_map(who, "height", height)) return rc;
   SpLayout L;
   if (int rc = split_layout(who, H, W, max_pairs, max_rounds, &L)) return rc;
-  if (int rc = split_check_buffer(who, "scratch", scratch)) return rc;
+  if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  int *basin = sp_at<int>(scratch, 0), *ctrl = sp_at<int>(scratch, L.off_ctrl);
-  SpSlot* slots = sp_at<SpSlot>(scratch, L.off_slots);
-  hipLaunchKernelGGL(split_clear_kernel, sp_grid(L.cap), dim3(SP_THREADS), 0, s, (int4*)slots, L.cap, (int4*)ctrl,
+  int *basin = scratch_at<int>(scratch, 0), *ctrl = scratch_at<int>(scratch, L.off_ctrl);
+  SpSlot* slots = scratch_at<SpSlot>(scratch, L.off_slots);
+  hipLaunchKernelGGL(split_clear_kernel, scene_grid(L.cap, SP_THREADS), dim3(SP_THREADS), 0, s, (int4*)slots, L.cap, (int4*)ctrl,
                      (int)(L.ctrl_words / 4));
   INSAR_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(split_ascent_kernel, sp_grid(L.npix), dim3(SP_THREADS), 0, s, (const int*)labels, (const int*)height, H, W,
+  hipLaunchKernelGGL(split_ascent_kernel, scene_grid(L.npix, SP_THREADS), dim3(SP_THREADS), 0, s, (const int*)labels, (const int*)height, H, W,
                      basin, ctrl);
   INSAR_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(split_resolve_kernel, sp_grid(L.npix), dim3(SP_THREADS), 0, s, basin, L.npix);
+  hipLaunchKernelGGL(split_resolve_kernel, scene_grid(L.npix, SP_THREADS), dim3(SP_THREADS), 0, s, basin, L.npix);
   INSAR_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(split_saddles_kernel, sp_grid(L.npix), dim3(SP_THREADS), 0, s, (const int*)labels, (const int*)height,
-                     (const int*)basin, H, W, sp_at<int>(scratch, L.off_up), sp_at<int>(scratch, L.off_nxt),
-                     sp_at<int>(scratch, L.off_bidx), sp_at<unsigned long long>(scratch, L.off_best), ctrl, slots,
+  hipLaunchKernelGGL(split_saddles_kernel, scene_grid(L.npix, SP_THREADS), dim3(SP_THREADS), 0, s, (const int*)labels, (const int*)height,
+                     (const int*)basin, H, W, scratch_at<int>(scratch, L.off_up), scratch_at<int>(scratch, L.off_nxt),
+                     scratch_at<int>(scratch, L.off_bidx), scratch_at<unsigned long long>(scratch, L.off_best), ctrl, slots,
                      (unsigned int)(L.cap - 1));
   INSAR_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(split_compact_kernel, sp_grid(L.cap), dim3(SP_THREADS), 0, s, (const SpSlot*)slots, L.cap, max_pairs, ctrl,
-                     sp_at<SpEdge>(scratch, L.off_edges));
+  hipLaunchKernelGGL(split_compact_kernel, scene_grid(L.cap, SP_THREADS), dim3(SP_THREADS), 0, s, (const SpSlot*)slots, L.cap, max_pairs, ctrl,
+                     scratch_at<SpEdge>(scratch, L.off_edges));
   INSAR_CHECK_LAUNCH(who);
   return INSAR_OK;
 }
@@ -539,16 +510,16 @@ extern "C" int insar_split_rounds(const int32_t* height, int32_t H, int32_t W, i
   if (int rc = split_check_map(who, "height", height)) return rc;
   SpLayout L;
   if (int rc = split_layout(who, H, W, max_pairs, max_rounds, &L)) return rc;
-  if (int rc = split_check_buffer(who, "scratch", scratch)) return rc;
+  if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   if (threshold < 0 || threshold > SP_MAX_T) INSAR_FAIL(INSAR_E_ARG, "%s: threshold %d outside 0..%d", who, threshold, SP_MAX_T);
   if (first_round < 0 || n_rounds < 1 || (int64_t)first_round + n_rounds > max_rounds)
     INSAR_FAIL(INSAR_E_ARG, "%s: rounds %d..%d outside 0..%d", who, first_round, first_round + n_rounds, max_rounds);
   hipStream_t s = (hipStream_t)stream;
-  int *up = sp_at<int>(scratch, L.off_up), *nxt = sp_at<int>(scratch, L.off_nxt), *bidx = sp_at<int>(scratch, L.off_bidx);
-  int* ctrl = sp_at<int>(scratch, L.off_ctrl);
-  unsigned long long* best = sp_at<unsigned long long>(scratch, L.off_best);
-  const SpEdge* edges = sp_at<SpEdge>(scratch, L.off_edges);
-  const dim3 grid = sp_grid(max_pairs), block(SP_THREADS);
+  int *up = scratch_at<int>(scratch, L.off_up), *nxt = scratch_at<int>(scratch, L.off_nxt), *bidx = scratch_at<int>(scratch, L.off_bidx);
+  int* ctrl = scratch_at<int>(scratch, L.off_ctrl);
+  unsigned long long* best = scratch_at<unsigned long long>(scratch, L.off_best);
+  const SpEdge* edges = scratch_at<SpEdge>(scratch, L.off_edges);
+  const dim3 grid = scene_grid(max_pairs, SP_THREADS), block(SP_THREADS);
   for (int r = first_round; r < first_round + n_rounds; ++r) {
     hipLaunchKernelGGL(split_best1_kernel, grid, block, 0, s, edges, (const int*)ctrl, max_pairs, (const int*)up, (const int*)height, best);
     INSAR_CHECK_LAUNCH(who);
@@ -575,18 +546,18 @@ extern "C" int insar_split_finish(const int32_t* labels, const int32_t* height, 
   SpLayout L;
   if (int rc = split_layout(who, H, W, max_pairs, max_rounds, &L)) return rc;
   if (max_regions < 1) INSAR_FAIL(INSAR_E_SHAPE, "%s: max_regions %d < 1", who, max_regions);
-  if (int rc = split_check_buffer(who, "scratch", scratch)) return rc;
-  if (int rc = split_check_buffer(who, "table", table)) return rc;
+  if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
+  if (int rc = scene_check_buffer(who, "table", table)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  int *piece = sp_at<int>(scratch, 0), *up = sp_at<int>(scratch, L.off_up), *ids = sp_at<int>(scratch, L.off_nxt);
-  int *bidx = sp_at<int>(scratch, L.off_bidx), *counts = sp_at<int>(scratch, L.off_counts), *ctrl = sp_at<int>(scratch, L.off_ctrl);
-  unsigned long long* best = sp_at<unsigned long long>(scratch, L.off_best);
+  int *piece = scratch_at<int>(scratch, 0), *up = scratch_at<int>(scratch, L.off_up), *ids = scratch_at<int>(scratch, L.off_nxt);
+  int *bidx = scratch_at<int>(scratch, L.off_bidx), *counts = scratch_at<int>(scratch, L.off_counts), *ctrl = scratch_at<int>(scratch, L.off_ctrl);
+  unsigned long long* best = scratch_at<unsigned long long>(scratch, L.off_best);
   InsarSplitRegion* t = (InsarSplitRegion*)table;
   const dim3 block(SP_THREADS);
-  hipLaunchKernelGGL(split_best1_kernel, sp_grid(max_pairs), block, 0, s, (const SpEdge*)sp_at<SpEdge>(scratch, L.off_edges),
+  hipLaunchKernelGGL(split_best1_kernel, scene_grid(max_pairs, SP_THREADS), block, 0, s, (const SpEdge*)scratch_at<SpEdge>(scratch, L.off_edges),
                      (const int*)ctrl, max_pairs, (const int*)up, (const int*)height, best);
   INSAR_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(split_piece_kernel, sp_grid(L.npix), block, 0, s, piece, (const int*)up, bidx, L.npix);
+  hipLaunchKernelGGL(split_piece_kernel, scene_grid(L.npix, SP_THREADS), block, 0, s, piece, (const int*)up, bidx, L.npix);
   INSAR_CHECK_LAUNCH(who);
   hipLaunchKernelGGL(split_count_kernel, dim3((unsigned)L.nblk), block, 0, s, (const int*)piece, (const int*)bidx, L.npix, counts, t,
                      max_regions);
@@ -597,7 +568,7 @@ extern "C" int insar_split_finish(const int32_t* labels, const int32_t* height, 
                      (const unsigned long long*)best, (const int*)labels, (const int*)height, mask, L.npix, (const int*)counts, ids, t,
                      max_regions);
   INSAR_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(split_relabel_kernel, sp_grid(L.npix), block, 0, s, (const int*)piece, (const int*)ids, conf, L.npix, W,
+  hipLaunchKernelGGL(split_relabel_kernel, scene_grid(L.npix, SP_THREADS), block, 0, s, (const int*)piece, (const int*)ids, conf, L.npix, W,
                      labels_out, t, max_regions);
   INSAR_CHECK_LAUNCH(who);
   return INSAR_OK;

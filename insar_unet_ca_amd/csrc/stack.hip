@@ -70,15 +70,6 @@ __device__ __forceinline__ void quad_store_i16(int16_t* p, int64_t i, int64_t n,
       if (i + j < n) p[i + j] = (int16_t)v[j];
   }
 }
-__device__ __forceinline__ void quad_store_u8(uint8_t* p, int64_t i, int64_t n, bool vec, const int* v) {
-  if (vec) {
-    *reinterpret_cast<uint32_t*>(p + i) = (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (i + j < n) p[i + j] = (uint8_t)v[j];
-  }
-}
 // bits lo .. hi - 1 of a word, 0 <= lo < hi <= 64
 __host__ __device__ __forceinline__ sk_u64 sk_bits(int lo, int hi) {
   const sk_u64 m = (hi - lo) >= 64 ? ~0ull : ((1ull << (hi - lo)) - 1ull);

@@ -235,6 +235,35 @@ def test_bitwise_against_the_oracle(dev, name):
         assert np.abs(quantise(m)[0]).max() == (1 << 31) - 1
 
 
+def _isolated_pixels(H, W):
+    """A uint8 raster that is 2 where y and x are both odd and 0 elsewhere, and its contours at level 1 in closed form: one
+    closed line per such pixel through the midpoints of its four lattice edges, from the edge above it clockwise (the pixel on
+    the right), led by that edge's id 2 * (pixel - W) + 1."""
+    m = np.zeros((H, W), dtype=np.uint8)
+    m[1:H - 1:2, 1:W - 1:2] = 2
+    y, x = (a.ravel().astype(np.int32) for a in np.mgrid[1:H - 1:2, 1:W - 1:2])
+    n = y.size
+    four = np.full(n, 4, dtype=np.int32)
+    Y, X = 256 * y + 128, 256 * x + 128
+    lines = {"line": np.arange(n, dtype=np.int32), "level": np.zeros(n, dtype=np.int32), "closed": np.ones(n, dtype=np.bool_),
+             "start": 4 * np.arange(n, dtype=np.int32), "count": four, "leader": 2 * ((y - 1) * W + x) + 1,
+             "area2": np.full(n, 2 * 128 * 256, dtype=np.int64), "y0": Y - 128, "x0": X - 128, "y1": Y + 129, "x1": X + 129}
+    vertices = np.stack([np.stack([Y - 128, X], 1), np.stack([Y, X + 128], 1), np.stack([Y + 128, X], 1), np.stack([Y, X - 128], 1)], 1)
+    return m, {"n_lines": n, "n_vertices": 4 * n, "level_counts": np.array([4 * n]), "levels_q": np.array([1]), "scale": 1.0,
+               "lines": lines, "vertices": np.ascontiguousarray(vertices.reshape(-1, 2), dtype=np.int32)}
+
+
+def test_isolated_pixels_fill_more_than_one_scan_pass(dev):
+    """The two array scans take 1024 blocks per pass. 1058 x 1026 pixels are 1061 blocks of 1024 pixels at the one level, and the
+    270 336 isolated pixels give 1 081 344 crossings in 1056 blocks of 1024: both scans run a second pass and hand their carry to
+    the header (the crossings, the level's count, the lines). The capacities are exact."""
+    import insar_unet_ca_amd as iu
+    m, ref = _isolated_pixels(1058, 1026)
+    assert m.size > 1024 * 1024 and ref["n_vertices"] > 1024 * 1024
+    out = iu.contour_lines(torch.from_numpy(m).to(dev), [1], max_lines=ref["n_lines"], max_vertices=ref["n_vertices"])
+    _compare(out, ref, "isolated pixels")
+
+
 def test_vector_and_scalar_paths_agree(dev):
     """33 x 67 is off the 4-pixel vector width; 32 x 68 is on it, and a view one element into a buffer is misaligned."""
     import insar_unet_ca_amd as iu

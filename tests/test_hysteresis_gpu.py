@@ -115,6 +115,22 @@ def test_negative_scores_keep_their_exact_peak(dev):
     assert out["regions"]["peak_x"].tolist() == [1] and out["regions"]["n_seed"].tolist() == [4]
 
 
+def test_isolated_seeds_fill_three_passes_of_keep(dev):
+    """2500 one-pixel sites: `keep` scans 1024 records per pass, so it runs three passes and carries the kept count from one to
+    the next and into the header. The expected labels are 1..2500 in row-major order; the capacity is exact."""
+    import insar_unet_ca_amd as iu
+    s = np.zeros((100, 100), dtype=np.float32)
+    s[1::2, 1::2] = 1.0
+    out = iu.hysteresis_regions(_t(s, dev), 0.25, 0.75, connectivity=4, min_seeds=1, max_regions=2500)
+    _same(out, ref.hysteresis(s, 0.25, 0.75, connectivity=4, min_seeds=1), "isolated seeds")
+    labels = np.zeros((100, 100), dtype=np.int32)
+    labels[1::2, 1::2] = np.arange(1, 2501, dtype=np.int32).reshape(50, 50)
+    assert out["count"] == out["candidates"] == 2500 and np.array_equal(out["labels"].cpu().numpy(), labels)
+    r = out["regions"]
+    assert np.array_equal(r["id"], np.arange(1, 2501)) and (r["area"] == 1).all() and (r["n_seed"] == 1).all()
+    assert np.array_equal(r["peak_y"], np.nonzero(labels)[0]) and np.array_equal(r["peak_x"], np.nonzero(labels)[1])
+
+
 # ---- the identities ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("conn", [4, 8])
 @pytest.mark.parametrize("H,W,K", [(33, 65, 1), (64, 128, 3), (97, 130, 2)])

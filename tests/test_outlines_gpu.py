@@ -127,6 +127,39 @@ def test_the_hand_made_maps_are_what_they_claim():
     assert (ri["area2"] > 0).sum() == 2 and (ri["area2"] < 0).sum() == 2 and set(ri["label"].tolist()) == {4}
 
 
+# ---- isolated pixels: the one-work-group scans past their first pass ----------------------------------------------------------------
+def _isolated_pixels(H, W):
+    """Label 1 where y and x are both odd, and the outlines of that map in closed form: under connectivity 4 every such pixel is
+    a region of its own, its ring the unit square from its top-left corner clockwise, led by its top edge 4 * pixel."""
+    labels = np.zeros((H, W), dtype=np.int32)
+    labels[1::2, 1::2] = 1
+    y, x = (a.ravel().astype(np.int32) for a in np.mgrid[1:H:2, 1:W:2])
+    n = y.size
+    four = np.full(n, 4, dtype=np.int32)
+    rings = {"ring": np.arange(n, dtype=np.int32), "label": np.ones(n, dtype=np.int32), "start": 4 * np.arange(n, dtype=np.int32),
+             "count": four, "edges": four, "area2": np.full(n, 2, dtype=np.int64), "hole": np.zeros(n, dtype=np.bool_),
+             "y0": y, "x0": x, "y1": y + 2, "x1": x + 2, "leader": 4 * (y * W + x)}      # the box is half-open over the vertices
+    vertices = np.stack([np.stack([y, x], 1), np.stack([y, x + 1], 1), np.stack([y + 1, x + 1], 1), np.stack([y + 1, x], 1)], 1)
+    ref = {"edge_count": 4 * n, "ring_count": n, "vertex_count": 4 * n, "rings": rings,
+           "vertices": np.ascontiguousarray(vertices.reshape(-1, 2), dtype=np.int32)}
+    return labels, ref
+
+
+@pytest.mark.parametrize("H,W", [(384, 768), (1056, 1024)])
+def test_isolated_pixels_fill_more_than_one_scan_pass(dev, H, W):
+    """The array scans of `edges`, `rings` and `write` take 1024 blocks per pass. 384 x 768: 294 912 edges are 1152 blocks of 256
+    positions, so the vertex scan runs a second pass and hands its carry to the header's vertex count. 1056 x 1024: 1056 blocks of
+    1024 pixels and 1 081 344 edges in 1056 blocks of 1024, so the edge scan and the paired ring scan do too. The capacities are
+    exact."""
+    import insar_unet_ca_amd as iu
+    labels, ref = _isolated_pixels(H, W)
+    E, R = ref["edge_count"], ref["ring_count"]
+    assert (E + 255) // 256 > 1024 and ((H * W > 1024 * 1024 and E > 1024 * 1024) or H * W < 1024 * 1024)
+    out = iu.region_outlines(torch.from_numpy(labels).to(dev), connectivity=4, corners_only=True, max_rings=R, max_vertices=E,
+                             max_edges=E)
+    _compare(out, ref, f"isolated pixels {H} x {W}")
+
+
 # ---- maps labelled by label_regions -------------------------------------------------------------------------------------------------
 SPECKLE = {"96x160 at 50 %": (96, 160, 0.5, 11), "70x130 at 30 %": (70, 130, 0.3, 12), "70x130 at 70 %": (70, 130, 0.7, 13)}
 

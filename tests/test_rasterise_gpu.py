@@ -69,6 +69,24 @@ def test_small_and_odd_shapes(dev, shape):
     _check(dev, scene_for(H, W, seed=H * 100 + W), H, W, f"{H}x{W}")
 
 
+def test_more_bands_than_one_scan_pass(dev):
+    """32 800 x 8 is 1025 bands of 32 rows, and the scan of the band counters takes 1024 per pass: the last band gets its slice of
+    the record array from the carry of the first pass. Two rectangles, one through every band and one inside the last."""
+    import insar_unet_ca_amd as iu
+    from insar_unet_ca_amd import rasterise as rs
+    H, W = 32800, 8
+    assert rs.band_rows(W) == 32
+    rect = lambda y0, x0, y1, x1: np.array([[y0, x0], [y0, x1], [y1, x1], [y1, x0]], dtype=np.float64)
+    table = iu.pack_polygons([{"label": 7, "polygons": [{"exterior": rect(3, 1, H - 40, 4), "holes": []}]},
+                              {"label": 9, "polygons": [{"exterior": rect(H - 20, 2, H - 2, 7), "holes": []}]}])
+    want = np.zeros((H, W), dtype=np.int32)
+    want[3:H - 40, 1:4] = 7
+    want[H - 20:H - 2, 2:7] = 9
+    for dt in (torch.uint8, torch.int32):
+        out = iu.rasterise_polygons(table, H, W, dtype=dt, device=dev)
+        assert np.array_equal(out["labels"].cpu().numpy(), want.astype(NP[dt])) and int(out["overlap_pixels"]) == 0
+
+
 def _band_boundaries():
     from insar_unet_ca_amd import rasterise as rs
     rows = [rs.band_rows(W) for W in range(1, 16385)]

@@ -97,6 +97,24 @@ def test_random_labels_with_distance_heights(dev):
     assert np.array_equal(whole, sr.components_by_first_pixel(m))      # label_regions's numbering where nothing is cut
 
 
+def test_numbering_scan_runs_a_second_pass(dev):
+    """1030 x 1024 pixels are 1030 numbering blocks, and the scan of their counts takes 1024 per pass: the pieces of the last six
+    blocks get their ids from the carry of the first pass, and the header its count. One-pixel sites 4099 pixels apart (four rows
+    and three columns, never neighbours) with a given height are a piece each, numbered in row-major order."""
+    H, W = 1030, 1024
+    at = np.arange(5, H * W, 4099)
+    m = np.zeros(H * W, dtype=np.int32)
+    m[at] = 1
+    out = _run(dev, m.reshape(H, W), height=m.reshape(H, W), squared=False, min_depth=0, max_pairs=1024)
+    want = np.zeros(H * W, dtype=np.int32)
+    want[at] = np.arange(1, at.size + 1)
+    assert at[-1] // 1024 >= 1024 and (out["count"], out["raw_basins"]) == (at.size, at.size)
+    assert np.array_equal(out["labels"].cpu().numpy().ravel(), want)
+    r = out["regions"]
+    assert np.array_equal(r["id"], np.arange(1, at.size + 1)) and (r["area"] == 1).all() and (r["parent"] == 1).all()
+    assert np.array_equal(r["peak_y"], at // W) and np.array_equal(r["peak_x"], at % W)
+
+
 @pytest.mark.parametrize("shape", [(1, 1), (1, 200), (200, 1)])
 def test_degenerate_shapes(dev, shape):
     rng = np.random.default_rng(sum(shape))
