@@ -10,7 +10,8 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ._lib import InsarError, call
+from . import _lib
+from ._lib import InsarError, call, ptr
 
 
 def query_bytes(name: str, *args, outputs: int):
@@ -99,6 +100,52 @@ def read_back(host: torch.Tensor, dev: torch.Tensor, nbytes: Optional[int] = Non
     host.copy_(dev, non_blocking=True)
     torch.cuda.current_stream().synchronize()
     return host.numpy()
+
+
+# ---- what simplify.py and contours.py share of Douglas-Peucker (csrc/dp_common.h) ------------------------------------------------
+# A round is one level of the recursion: a record of n vertices that splits evenly is done after log2 n rounds (17 for 10^5
+# vertices), one that sheds a vertex per level, like a spiral arm, needs as many rounds as vertices; 64 covers outlines and
+# contour lines as detection produces them, and `converged` says when it did not.
+DEFAULT_MAX_ROUNDS = 64
+MAX_ROUNDS = 4095
+ROUNDS_PER_READ = 8                      # the host looks at a round's counter once per this many rounds
+MAX_TOLERANCE = 1024.0
+
+
+def check_tolerance(who: str, name: str, tolerance) -> float:
+    """The tolerance of a simplification in pixels: a finite number in 0 .. 1024, else InsarError."""
+    if isinstance(tolerance, bool) or not isinstance(tolerance, (int, float, np.integer, np.floating)):
+        raise InsarError(f"{who}: {name}={tolerance!r}: a number of pixels")
+    if not math.isfinite(float(tolerance)) or not 0.0 <= float(tolerance) <= MAX_TOLERANCE:
+        raise InsarError(f"{who}: {name}={tolerance!r}: finite, 0 .. {MAX_TOLERANCE:g}")
+    return float(tolerance)
+
+
+def simplify_rounds(prefix: str, scratch, v: torch.Tensor, n_records: int, nbytes: int, eps: int, max_rounds: int, setup_extra=()):
+    """One simplification through the entry points `prefix`_setup / _rounds / _finish on the current stream of v's device: the
+    first `nbytes` of the pinned input table `scratch.host_in` (filled by the caller: header + n_records records) go up, setup
+    runs (`setup_extra` between the record count and the capacities), then batches of ROUNDS_PER_READ rounds until the 4-byte
+    counter of a batch's last round reads 0 or the probe after `max_rounds` has run, then finish. Returns (the raw bytes of
+    the output table, header first, a view of `scratch.host`; the compacted vertices; their input positions), the last two
+    device tensors of full length of which the header's count says how much is used."""
+    V = int(v.shape[0])
+    out_v = torch.empty(V, 2, dtype=torch.int32, device=v.device)
+    out_k = torch.empty(V, dtype=torch.int32, device=v.device)
+    head = (ptr(v), V, ptr(scratch.table_in), n_records)
+    caps = (*scratch.key()[:2], ptr(scratch.scratch))            # max_vertices, max records, scratch
+    with torch.cuda.device(v.device):
+        s = _lib.stream_ptr()
+        scratch.table_in[:nbytes].copy_(scratch.host_in[:nbytes], non_blocking=True)
+        call(prefix + "_setup", *head, *setup_extra, *caps, s)
+        r, total = 0, max_rounds + 1                             # the last round is the probe
+        while r < total:
+            n = min(ROUNDS_PER_READ, total - r)
+            call(prefix + "_rounds", *head, eps, r, n, max_rounds, *caps, s)
+            r += n
+            if r < total and int(read_back(scratch.counter, scratch.scratch[4 * (r - 1):4 * r]).view(np.int32)[0]) == 0:
+                break
+        call(prefix + "_finish", *head, max_rounds, *caps, ptr(scratch.table), ptr(out_v), ptr(out_k), s)
+        return read_back(scratch.host, scratch.table, nbytes), out_v, out_k
 
 
 class Scratch:

@@ -25,7 +25,9 @@ import torch
 
 from . import _lib
 from ._lib import InsarError, call, ptr
-from ._scene import Scratch, check_int, check_map, check_on_device, pinned, query_bytes, read_back
+from ._scene import MAX_TOLERANCE, ROUNDS_PER_READ  # noqa: F401  (the tools read them from here)
+from ._scene import (DEFAULT_MAX_ROUNDS, MAX_ROUNDS, Scratch, check_int, check_map, check_on_device, check_tolerance, pinned,
+                     query_bytes, read_back, simplify_rounds)
 from .zonal import quantise_scalar
 
 DEFAULT_MAX_LINES = 65536
@@ -192,13 +194,6 @@ def contour_lines(raster: torch.Tensor, levels, *, scale: float = 2 ** 16, valid
 
 
 # ---- simplification ------------------------------------------------------------------------------------------------------------
-# A round is one level of the recursion: a line of n vertices that splits evenly is done after log2 n rounds, one that sheds a
-# vertex per level needs as many rounds as vertices; 64 covers contour lines as rasters give them, and `converged` says when
-# it did not.
-DEFAULT_MAX_ROUNDS = 64
-MAX_ROUNDS = 4095
-ROUNDS_PER_READ = 8                      # the host looks at a round's counter once per this many rounds
-MAX_TOLERANCE = 1024.0
 MAX_COORD = 1 << 30                      # the contract of simplify_contours: 0 <= Y, X <= 2^30 (contour_lines stays below it)
 MAX_SIMPLIFY_VERTICES = 1 << 28
 MAX_SIMPLIFY_LINES = 1 << 27
@@ -232,15 +227,6 @@ class ContourSimplifyScratch(Scratch):
         sb, tb = contour_simplify_scratch_bytes(max_vertices, max_lines)
         super().__init__((max_vertices, max_lines), device, scratch=sb, table_in=tb, table=tb, host=tb)
         self.host_in, self.counter = pinned(tb), pinned(4)
-
-
-def check_tolerance(who: str, name: str, tolerance) -> float:
-    """The tolerance of `simplify_contours` in pixels: a finite number in 0 .. 1024, else InsarError."""
-    if isinstance(tolerance, bool) or not isinstance(tolerance, (int, float, np.integer, np.floating)):
-        raise InsarError(f"{who}: {name}={tolerance!r}: a number of pixels")
-    if not math.isfinite(float(tolerance)) or not 0.0 <= float(tolerance) <= MAX_TOLERANCE:
-        raise InsarError(f"{who}: {name}={tolerance!r}: finite, 0 .. {MAX_TOLERANCE:g}")
-    return float(tolerance)
 
 
 def _check_simplify(contours, tolerance, max_rounds, scratch):
@@ -331,31 +317,13 @@ def simplify_contours(contours: dict, *, tolerance: float, max_rounds: int = DEF
     check_on_device("simplify_contours", "vertices", v)
     if scratch is None:
         scratch = ContourSimplifyScratch(V, R, v.device)
-    vm, lm = scratch.max_vertices, scratch.max_lines
-    eps2 = eps_q(tolerance) ** 2
-    max_rounds = int(max_rounds)
     nbytes = LINE_DTYPE.itemsize * (1 + R)
     tin = scratch.host_in.numpy()[:nbytes].view(LINE_DTYPE)
     tin[:] = 0
     for f in ("level", "closed", "start", "count", "leader"):
         tin[f][1:] = ln[f]
-    out_v = torch.empty(V, 2, dtype=torch.int32, device=v.device)
-    out_k = torch.empty(V, dtype=torch.int32, device=v.device)
-    sp, tp, ip = ptr(scratch.scratch), ptr(scratch.table), ptr(scratch.table_in)
-    with torch.cuda.device(v.device):
-        s = _lib.stream_ptr()
-        scratch.table_in[:nbytes].copy_(scratch.host_in[:nbytes], non_blocking=True)
-        call("insar_contour_simplify_setup", ptr(v), V, ip, R, vm, lm, sp, s)
-        r, total = 0, max_rounds + 1                             # the last round is the probe
-        while r < total:
-            n = min(ROUNDS_PER_READ, total - r)
-            call("insar_contour_simplify_rounds", ptr(v), V, ip, R, eps2, r, n, max_rounds, vm, lm, sp, s)
-            r += n
-            if r < total:
-                if int(read_back(scratch.counter, scratch.scratch[4 * (r - 1):4 * r]).view(np.int32)[0]) == 0:
-                    break
-        call("insar_contour_simplify_finish", ptr(v), V, ip, R, max_rounds, vm, lm, sp, tp, ptr(out_v), ptr(out_k), s)
-        raw = read_back(scratch.host, scratch.table, nbytes).view(LINE_DTYPE)
+    raw, out_v, out_k = simplify_rounds("insar_contour_simplify", scratch, v, R, nbytes, eps_q(tolerance) ** 2, int(max_rounds))
+    raw = raw.view(LINE_DTYPE)
     head, rec = raw[0], raw[1:]
     kept = int(head["count"])
     lines = {"line": np.arange(R, dtype=np.int32)}

@@ -1,5 +1,5 @@
-// The work-group scans of the scene tools (regions.hip, split.hip, raster.hip, outline.hip, contour.hip, hysteresis.hip,
-// simplify.hip, contour_simplify.hip): one value per thread over a work-group of THREADS threads, by wave shuffles and one LDS
+// The work-group scans of the scene tools (regions.hip, split.hip, raster.hip, outline.hip, contour.hip, hysteresis.hip, and
+// dp_common.h for simplify.hip and contour_simplify.hip): one value per thread over a work-group of THREADS threads, by wave shuffles and one LDS
 // slot per wave, and the one-work-group scan of a whole array built on the same steps. Every thread of the work-group calls them
 // (they synchronise); w is THREADS / INSAR_WAVE ints of LDS, free again on return.
 #pragma once

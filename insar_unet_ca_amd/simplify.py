@@ -16,25 +16,18 @@ arcs never cross at a large tolerance. Douglas-Peucker does not give that, and n
 """
 from __future__ import annotations
 
-import math
 from typing import Optional
 
 import numpy as np
 import torch
 
-from . import _lib
 from ._lib import InsarError, call, ptr
-from ._scene import Scratch, check_int, check_map, check_on_device, pinned, query_bytes, read_back
+from ._scene import MAX_TOLERANCE, ROUNDS_PER_READ  # noqa: F401  (the tools read them from here)
+from ._scene import (DEFAULT_MAX_ROUNDS, MAX_ROUNDS, Scratch, check_int, check_map, check_on_device, check_tolerance, pinned,
+                     query_bytes, simplify_rounds)
 from .outlines import RING_DTYPE
 
-# A round is one level of the recursion. A segment of n vertices that splits evenly is done after log2 n rounds (17 for 10^5
-# vertices), one that sheds a vertex per level, like a spiral arm, needs as many rounds as vertices; 64 covers outlines as
-# detection produces them, and `converged` says when it did not.
-DEFAULT_MAX_ROUNDS = 64
-MAX_ROUNDS = 4095
-ROUNDS_PER_READ = 8                      # the host looks at a round's counter once per this many rounds
 MAX_DIM = 16384                          # the cap rasterise.py uses: cross^2 of two such vectors fits 64 bits
-MAX_TOLERANCE = 1024.0
 MAX_VERTICES = 1 << 28
 MAX_RINGS = 1 << 26
 _COPIED = ("label", "edges", "leader", "area2")
@@ -90,10 +83,7 @@ def _check_args(outlines, labels, tolerance, max_rounds):
     R = len(rings["start"])
     if any(len(np.asarray(rings[f])) != R for f in ("count",) + _COPIED):
         raise InsarError(f"{who}: the fields of outlines['rings'] differ in length")
-    if isinstance(tolerance, bool) or not isinstance(tolerance, (int, float, np.integer, np.floating)):
-        raise InsarError(f"{who}: tolerance={tolerance!r}: a number of pixels")
-    if not math.isfinite(float(tolerance)) or not 0.0 <= float(tolerance) <= MAX_TOLERANCE:
-        raise InsarError(f"{who}: tolerance={tolerance!r}: finite, 0 .. {MAX_TOLERANCE:g}")
+    check_tolerance(who, "tolerance", tolerance)
     check_int(who, "max_rounds", max_rounds, 1, MAX_ROUNDS, integral_floats=False)
     H = W = 0
     if labels is not None:
@@ -163,32 +153,14 @@ def simplify_outlines(outlines: dict, labels: Optional[torch.Tensor] = None, *, 
         raise InsarError(f"simplify_outlines: scratch for {scratch.max_vertices} vertices, {scratch.max_rings} rings of a "
                          f"{scratch.H} x {scratch.W} scene on {scratch.scratch.device}: the input has {V} vertices, {R} rings"
                          + (f" of a {H} x {W} scene" if labels is not None else "") + f" on {v.device}")
-    vm, rm = scratch.max_vertices, scratch.max_rings
-    q2 = eps2q(tolerance)
-    max_rounds = int(max_rounds)
     nbytes = RING_DTYPE.itemsize * (1 + R)
     tin = scratch.host_in.numpy()[:nbytes].view(RING_DTYPE)
     tin[:] = 0
     tin["start"][1:], tin["count"][1:] = rings["start"], rings["count"]
     for f in _COPIED:
         tin[f][1:] = rings[f]
-    out_v = torch.empty(V, 2, dtype=torch.int32, device=v.device)
-    out_k = torch.empty(V, dtype=torch.int32, device=v.device)
-    sp, tp, ip = ptr(scratch.scratch), ptr(scratch.table), ptr(scratch.table_in)
-    with torch.cuda.device(v.device):
-        s = _lib.stream_ptr()
-        scratch.table_in[:nbytes].copy_(scratch.host_in[:nbytes], non_blocking=True)
-        call("insar_simplify_setup", ptr(v), V, ip, R, ptr(labels), H, W, vm, rm, sp, s)
-        r, total = 0, max_rounds + 1                             # the last round is the probe
-        while r < total:
-            n = min(ROUNDS_PER_READ, total - r)
-            call("insar_simplify_rounds", ptr(v), V, ip, R, q2, r, n, max_rounds, vm, rm, sp, s)
-            r += n
-            if r < total:
-                if int(read_back(scratch.counter, scratch.scratch[4 * (r - 1):4 * r]).view(np.int32)[0]) == 0:
-                    break
-        call("insar_simplify_finish", ptr(v), V, ip, R, max_rounds, vm, rm, sp, tp, ptr(out_v), ptr(out_k), s)
-        raw = read_back(scratch.host, scratch.table, nbytes).view(RING_DTYPE)
+    raw, out_v, out_k = simplify_rounds("insar_simplify", scratch, v, R, nbytes, eps2q(tolerance), int(max_rounds), (ptr(labels), H, W))
+    raw = raw.view(RING_DTYPE)
     head, rec = raw[0], raw[1:]
     kept = int(head["count"])
     out = {"ring": np.arange(R, dtype=np.int32)}

@@ -182,6 +182,33 @@ def wobbly_ring(n, seed, cy=600000, cx=600000, radius=400000):
     return list(zip(np.rint(cy + r * np.sin(t)).astype(np.int64).tolist(), np.rint(cx + r * np.cos(t)).astype(np.int64).tolist()))
 
 
+SCAN_PASS_TOLERANCES = (0.25, 16)
+_SCAN_PASS = {}
+
+
+def scan_pass_lines():
+    """A short open line (so that no line starts on a block border), a ring of 69 000 vertices and an open line of 600: 69 677
+    positions, more than the 65 536 that one pass of the one-work-group carry and prefix scans takes, with the ring across that
+    boundary. Built once."""
+    if "lines" not in _SCAN_PASS:
+        _SCAN_PASS["lines"] = make_contours([(zigzag(77, 3), False), (wobbly_ring(69000, 2), True), (zigzag(600, 5), False)])
+    return _SCAN_PASS["lines"]
+
+
+def scan_pass_ring_kept(ref):
+    """(kept positions of the ring before position 65 536, at or after it) of an oracle result of `scan_pass_lines`."""
+    s, n = int(ref["lines"]["start"][1]), int(ref["lines"]["count"][1])
+    k = ref["kept"][s:s + n]
+    return int((k < 65536).sum()), int((k >= 65536).sum())
+
+
+def scan_pass_oracle(tolerance):
+    """The oracle of `scan_pass_lines` at one of SCAN_PASS_TOLERANCES, computed once per process and not to be written."""
+    if tolerance not in _SCAN_PASS:
+        _SCAN_PASS[tolerance] = simplify_contours_oracle(scan_pass_lines(), tolerance, 64)
+    return _SCAN_PASS[tolerance]
+
+
 def shedding_arc(n=40, step_deg=60.0, rho=0.7, radius=1 << 28, centre=1 << 29):
     """An open convex arc, an inward spiral of n vertices that turns by step_deg and shrinks by rho from vertex to vertex: the
     farthest vertex from every chord to its inner end is the one next to the chord's outer end, so every level of the

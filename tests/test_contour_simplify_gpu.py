@@ -159,6 +159,21 @@ def test_hand_made_polylines(dev):
         print(f"hand-made tol {tol}: {ref['input_n_vertices']} -> {ref['n_vertices']} vertices, {ref['rounds']} rounds")
 
 
+@pytest.mark.parametrize("tol", cr.SCAN_PASS_TOLERANCES)
+def test_a_ring_longer_than_one_scan_pass(dev, tol):
+    """69 677 positions, more than the 65 536 that one pass of the carry and prefix scans takes: a ring of 69 000 vertices
+    lies across that boundary, with kept vertices on both sides and its wrap over it, between two open lines. At 0.25 pixel
+    more than a tenth of the vertices survive, at 16 pixels fewer than a hundredth (tests/test_contour_simplify_host.py
+    asserts both of the oracle)."""
+    host = cr.scan_pass_lines()
+    start, count = host["lines"]["start"], host["lines"]["count"]
+    assert host["n_vertices"] > 65536 + 4096 and start[1] < 65536 - 4096 and start[1] + count[1] > 65536
+    ref = cr.scan_pass_oracle(tol)
+    assert ref["converged"] and min(cr.scan_pass_ring_kept(ref)) >= 2
+    _check(dev, _on_device(host, dev), host, tol, ROUNDS, f"scan pass tolerance {tol}", ref=ref)
+    print(f"scan pass tol {tol}: {ref['input_n_vertices']} -> {ref['n_vertices']} vertices, {ref['rounds']} rounds")
+
+
 def test_ties_duplicates_and_rings_of_one_point(dev):
     """What `contour_lines` never produces and the function is total on: equal distances on either side of a chord, repeated
     coordinates (the smallest position wins), a ring of one point (one seed, collapsed), a line that returns to its head."""

@@ -240,6 +240,30 @@ def test_launches_and_scratch_bytes_are_host_arithmetic():
     assert ct.eps_q(0.25) == 64 and ct.eps_q(1024) == 262144 and ct.eps_q(0.001953125) == 0 and ct.eps_q(0.005859375) == 2
 
 
+def test_scratch_bytes_are_what_they_were():
+    """The byte counts of the build before the scratch core moved into csrc/dp_common.h: callers size buffers by them."""
+    assert ct.contour_simplify_scratch_bytes(1, 1) == (16704, 96)
+    assert ct.contour_simplify_scratch_bytes(1000, 37) == (79040, 1824)
+    assert ct.contour_simplify_scratch_bytes(70001, 513) == (4312624, 24672)
+    assert ct.contour_simplify_scratch_bytes(1 << 22, 65536) == (258818064, 3145776)
+
+
+def test_the_long_ring_case_of_the_gpu_suite_is_what_it_claims():
+    """The hand-made lines of tests/test_contour_simplify_gpu.py that cross one pass of the one-work-group scans (256 blocks of
+    256 positions): sizes, where the ring lies, and how much survives at the two tolerances. The oracle runs here, without a
+    device, so that its cost at this size is seen in the host suite."""
+    host = cr.scan_pass_lines()
+    start, count, V = host["lines"]["start"], host["lines"]["count"], host["n_vertices"]
+    assert V > 65536 + 4096 and V <= 70000 and host["lines"]["closed"].tolist() == [False, True, False]
+    assert start[1] % 256 != 0 and start[1] < 65536 - 4096 and start[1] + count[1] > 65536 and start[2] % 256 != 0
+    for tol in cr.SCAN_PASS_TOLERANCES:
+        ref = cr.scan_pass_oracle(tol)
+        assert ref["converged"] and ref["input_n_vertices"] == V
+        assert min(cr.scan_pass_ring_kept(ref)) >= 2             # the ring keeps vertices on both sides of the boundary
+    assert cr.scan_pass_oracle(cr.SCAN_PASS_TOLERANCES[0])["n_vertices"] >= V // 10
+    assert cr.scan_pass_oracle(cr.SCAN_PASS_TOLERANCES[1])["n_vertices"] < V // 100
+
+
 # ---- the host helpers on simplified dicts -------------------------------------------------------------------------------------------
 def _square(y, x, side, hole=False):
     pts = [(y, x), (y, x + side), (y + side, x + side), (y + side, x)]

@@ -129,6 +129,77 @@ def test_reused_scratch_across_maps(dev):
         iu.simplify_outlines(raw, t, tolerance=1, scratch=iu.SimplifyScratch(100, 8192, 96, 160, dev))
 
 
+PAD = 4096
+
+
+def _guarded(nbytes, dev, fill=0xA5):
+    g = torch.full((PAD + nbytes + PAD,), fill, dtype=torch.uint8, device=dev)
+    return g, g[PAD:PAD + nbytes]
+
+
+def _intact(g, nbytes, fill=0xA5):
+    h = g.cpu().numpy()
+    return bool((h[:PAD] == fill).all() and (h[PAD + nbytes:] == fill).all())
+
+
+def _phases(dev, raw, labels, tolerance, max_rounds, vm, rm):
+    """setup, every round in one call and finish with scratch, both tables and both outputs inside guards; the result in the
+    shape of simplify_outlines, and whether every guard is intact."""
+    from insar_unet_ca_amd import _lib
+    from insar_unet_ca_amd import simplify as sm
+    from insar_unet_ca_amd._lib import call, ptr
+    from insar_unet_ca_amd.outlines import RING_DTYPE
+    v, rings = raw["vertices"], raw["rings"]
+    V, R = int(v.shape[0]), len(rings["start"])
+    H, W = labels.shape
+    sb, tb = sm.scratch_bytes(vm, rm)
+    used = RING_DTYPE.itemsize * (1 + R)
+    gs, scratch = _guarded(sb, dev)
+    gi, tin = _guarded(used, dev)
+    gt, table = _guarded(used, dev)
+    gv, out_v = _guarded(8 * V, dev)
+    gk, out_k = _guarded(4 * V, dev)
+    host = np.zeros(1 + R, dtype=RING_DTYPE)
+    for f in ("start", "count", "label", "edges", "leader", "area2"):
+        host[f][1:] = rings[f]
+    tin.copy_(torch.from_numpy(host.view(np.uint8)))
+    s = _lib.stream_ptr()
+    call("insar_simplify_setup", ptr(v), V, ptr(tin), R, ptr(labels), H, W, vm, rm, ptr(scratch), s)
+    call("insar_simplify_rounds", ptr(v), V, ptr(tin), R, sm.eps2q(tolerance), 0, max_rounds + 1, max_rounds, vm, rm, ptr(scratch), s)
+    call("insar_simplify_finish", ptr(v), V, ptr(tin), R, max_rounds, vm, rm, ptr(scratch), ptr(table), ptr(out_v), ptr(out_k), s)
+    torch.cuda.synchronize()
+    rec = table.cpu().numpy().view(RING_DTYPE)
+    head, rec = rec[0], rec[1:]
+    kept = int(head["count"])
+    assert int(head["label"]) == R and int(head["edges"]) == V
+    out = {"ring": np.arange(R, dtype=np.int32)}
+    for f in ("label", "start", "count", "edges", "area2", "y0", "x0", "y1", "x1", "leader"):
+        out[f] = rec[f].copy()
+    out["hole"] = np.asarray(rings["area2"]) < 0
+    out["collapsed"] = rec["_pad"] != 0
+    res = {"vertices": out_v.view(torch.int32).reshape(-1, 2)[:kept].clone(), "kept": out_k.view(torch.int32)[:kept].clone(),
+           "rings": out, "ring_count": R, "vertex_count": kept, "edge_count": int(raw["edge_count"]), "input_vertex_count": V,
+           "rounds": int(head["leader"]), "converged": bool(head["start"])}
+    # nothing behind the kept vertices is written either
+    tail_v, tail_k = out_v[8 * kept:].cpu().numpy(), out_k[4 * kept:].cpu().numpy()
+    ok = (_intact(gs, sb) and _intact(gi, used) and _intact(gt, used) and _intact(gv, 8 * V) and _intact(gk, 4 * V)
+          and bool((tail_v == 0xA5).all() and (tail_k == 0xA5).all()))
+    return res, ok
+
+
+@pytest.mark.parametrize("tol", [1, 8])
+def test_guarded_phase_calls_with_larger_capacities(dev, tol):
+    """The three entry points on `blobs` with capacities larger than the input, every buffer between guard patterns: no guard
+    and nothing behind the kept vertices is written, and the result is the oracle's. A section of the scratch carved at the
+    wrong offset or size shows here first."""
+    t, raw, verts = _raw(dev, "blobs")
+    V, R = raw["vertex_count"], raw["ring_count"]
+    ref = _oracle("blobs", verts, raw["rings"], MAPS["blobs"][0], tol, ROUNDS)
+    ph, ok = _phases(dev, raw, t, tol, ROUNDS, vm=V + 77, rm=R + 5)
+    assert ok, "a guard was written"
+    _compare(ph, ref, f"blobs tolerance {tol} (phases)")
+
+
 def test_rings_longer_than_one_scan_pass(dev):
     """Two hand-made circle outlines of 37 600 and 32 800 vertices: together more than the 65 536 positions one pass of the
     carry and prefix scans takes, with kept vertices on both sides of that boundary and segments of the second ring across it."""

@@ -280,6 +280,14 @@ def test_host_queries_and_abi():
     assert "SimplifyScratch" in iu.__all__ and "simplify_outlines" in iu.__all__
 
 
+def test_scratch_bytes_are_what_they_were():
+    """The byte counts of the build before the scratch core moved into csrc/dp_common.h: callers size buffers by them."""
+    assert sm.scratch_bytes(1, 1) == (16672, 96)
+    assert sm.scratch_bytes(1000, 37) == (62592, 1824)
+    assert sm.scratch_bytes(70001, 513) == (3186448, 24672)
+    assert sm.scratch_bytes(1 << 22, 65536) == (190922768, 3145776)
+
+
 def test_entry_points_validate_before_the_device():
     """Null pointers, counts against capacities, alignment, the label map's size, eps2q and the round numbers: every one is an
     error code, not a launch. The pointers are never dereferenced on the host."""
