@@ -540,8 +540,8 @@ extern "C" int insar_bn_relu_apply(const InsarAct* y, const float* scale, const 
 // ---------------------------------------------------------------------------------------------
 // z = relu(y*scale + shift) * gate AND its 2x2 max-pool in one pass (encoder blocks: :96-97 followed by
 // MaxPool2d(2) :106-109). A work-group takes two image rows; a thread a 2x2 window of one channel chunk:
-// four loads, four stores of z, one store of the window maximum. Rounding to the storage type is monotone,
-// so max-then-round equals the max-pool of the stored z bit for bit.
+// four loads, four stores of z, one store of the window maximum, which is taken over the values as stored and under
+// insar_maxpool2_fwd's rule, so it equals the max-pool of the stored z bit for bit (a NaN and the sign of a zero included).
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 __global__ void bn_relu_apply_pool_kernel(ActView y, const float* __restrict__ scale, const float* __restrict__ shift,
@@ -567,7 +567,7 @@ __global__ void bn_relu_apply_pool_kernel(ActView y, const float* __restrict__ s
       uint4 v[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) v[q] = *chunk_ptr<T>(y, n, 2 * h2 + (q >> 1), 2 * w2 + (q & 1), cc);
-      float m[CH], mr[CH];
+      float mr[CH];
       uint32_t best[CH];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -577,20 +577,19 @@ __global__ void bn_relu_apply_pool_kernel(ActView y, const float* __restrict__ s
         for (int j = 0; j < CH; ++j) {
           const float z = fmaf(f[j], sc[j], sh[j]);
           f[j] = (relu ? fmaxf(z, 0.f) : z) * gt[j];
-          m[j] = q == 0 ? f[j] : fmaxf(m[j], f[j]);
         }
         const uint4 packed = Chunk<T>::pack(f);
         *chunk_ptr_w<T>(dst, n, 2 * h2 + (q >> 1), 2 * w2 + (q & 1), cc) = packed;
-        if (arg) {           // arg-max of the STORED values, insar_maxpool2_bwd's rule: first maximum in scan order, NaN wins
-          Chunk<T>::unpack(packed, fr);
+        // maximum and arg-max of the STORED values, insar_maxpool2_fwd / _bwd's rule: first maximum in scan order, NaN wins
+        // (fmaxf would drop a NaN that the arg map and the unfused pool keep, and order -0 below +0)
+        Chunk<T>::unpack(packed, fr);
 #pragma unroll
-          for (int j = 0; j < CH; ++j) {
-            if (q == 0) { mr[j] = fr[j]; best[j] = 0; }
-            else if (fr[j] > mr[j] || fr[j] != fr[j]) { mr[j] = fr[j]; best[j] = q; }
-          }
+        for (int j = 0; j < CH; ++j) {
+          if (q == 0) { mr[j] = fr[j]; best[j] = 0; }
+          else if (fr[j] > mr[j] || fr[j] != fr[j]) { mr[j] = fr[j]; best[j] = q; }
         }
       }
-      *chunk_ptr_w<T>(pooled, n, h2, w2, cc) = Chunk<T>::pack(m);
+      *chunk_ptr_w<T>(pooled, n, h2, w2, cc) = Chunk<T>::pack(mr);
       if (arg) {
         uint8_t* ap = arg + (((int64_t)n * Hp + h2) * Wp2 + w2) * y.c_len + cc * CH;      // [B][H/2][W/2][C] bytes
         if constexpr (CH == 8) {
