@@ -1204,6 +1204,53 @@ int insar_focal_gradient(const float* raster, int32_t planes, int32_t H, int32_t
                          int32_t has_nodata, double nodata, const uint8_t* valid, int32_t keep_invalid, float* out, uint8_t* out_valid,
                          void* stream);
 
+/* ---- grey-scale reconstruction: fill sinks, h-domes, regional extrema (build-side addition; the reference has no
+ * post-processing): csrc/reconstruct.hip -----------------------------------------------------------------------------------------
+ * Reconstruction by dilation of a marker F under a mask G over a raster [planes][H][W] (layout, element types, limits and the
+ * valid / nodata arguments as for the focal operations above): the pointwise limit of J <- min(G, max of J over the pixel and its
+ * `connectivity` (4 or 8) neighbours) from J = min(F, G), on order-preserving 32-bit KEYS of the raw values: float32 u = bits;
+ * u & 2^31 ? ~u : u ^ 2^31; int32 with the sign bit flipped; uint8 as it is. flip = 1 complements the keys: reconstruction by
+ * erosion. A pixel is VALID iff it lies inside the raster, valid[y][x] != 0, its mask value is valid by the focal rule and its
+ * marker value (INSAR_RECONSTRUCT_PLAIN) is neither NaN nor `nodata` (a marker of +-inf is taken as it is). An invalid pixel has
+ * the mask key 0: it neither takes nor passes a value. `mode` names the marker:
+ *   INSAR_RECONSTRUCT_PLAIN    `marker`, the mask's type and layout (every other mode: marker = NULL)
+ *   INSAR_RECONSTRUCT_FILL     the mask at OUTLETS, key 0 elsewhere; an outlet is a valid pixel with a `connectivity` neighbour that
+ *                              is invalid or outside the raster. flip = 1 fills sinks, flip = 0 fills domes.
+ *   INSAR_RECONSTRUCT_HDOME    mask - h (flip = 0) or mask + h (flip = 1): one float32 operation, or a saturating integer one;
+ *                              h > 0, finite in float32, an integer <= 2^31 - 1 for integer rasters
+ *   INSAR_RECONSTRUCT_EXTREMA  the mask's key - 1, saturating at 0 (flip = 0: maxima, 1: minima)
+ * scratch: insar_reconstruct_bytes(...) bytes, 16-byte aligned: two key planes of J, one of G, two tile-activity maps and the
+ * (changed tiles, active tiles) int32 pair of every round, INSAR_RECONSTRUCT_MAX_ROUNDS + 1 of them, at the scratch's end. Nothing in
+ * it has to survive between calls; prepare, rounds and finish of one call share it. No atomics on pixel data, no work-group
+ * waits on another; the fixed point is unique, so the outputs and the number of rounds are bitwise defined
+ * (tests/reconstruct_ref.py restates both). */
+enum { INSAR_RECONSTRUCT_PLAIN = 0, INSAR_RECONSTRUCT_FILL = 1, INSAR_RECONSTRUCT_HDOME = 2, INSAR_RECONSTRUCT_EXTREMA = 3 };
+#define INSAR_RECONSTRUCT_MAX_ROUNDS 65535
+/* host only: the edge of the square tile one work-group of a round solves */
+int insar_reconstruct_tile(int32_t* edge);
+/* host only: the bytes of `scratch`; the counter pairs are its last 8 * (INSAR_RECONSTRUCT_MAX_ROUNDS + 1) bytes */
+int insar_reconstruct_bytes(int32_t planes, int32_t H, int32_t W, int64_t* scratch_bytes);
+/* ONE launch: the key planes G and J = min(F, G), every tile active, the counter pairs of rounds 0 .. max_rounds at 0; the rounds
+ * of this call stay below max_rounds (1 .. INSAR_RECONSTRUCT_MAX_ROUNDS) */
+int insar_reconstruct_prepare(const void* marker, const void* mask, int32_t elem_type, int32_t planes, int32_t H, int32_t W,
+                              int32_t mode, int32_t flip, int32_t connectivity, double h, int32_t max_rounds, int32_t has_nodata,
+                              double nodata, const uint8_t* valid, void* scratch, void* stream);
+/* n_rounds launches, rounds first_round .. first_round + n_rounds - 1 (in order, from 0, at most INSAR_RECONSTRUCT_MAX_ROUNDS in
+ * all). A round solves every ACTIVE tile to its local fixed point from the plane of the round before and writes the other
+ * plane; a tile is active in round 0, and in round r + 1 iff it or one of its 8 neighbours changed in round r. Round r adds
+ * to counter pair r. A round whose changed count is 0 has reached the fixed point; further rounds change nothing. */
+int insar_reconstruct_rounds(int32_t planes, int32_t H, int32_t W, int32_t connectivity, int32_t first_round, int32_t n_rounds,
+                             void* scratch, void* stream);
+/* ONE launch, after `rounds_run` rounds. Every output is nullable (at least one is given) and [planes][H][W]:
+ *   out        the mask's type: the reconstruction; an invalid pixel holds the quiet NaN 0x7fc00000 / `fill`; never marker or mask
+ *   residue    float32 for a float32 raster, else int32: mask - reconstruction (flip = 0) or reconstruction - mask (flip = 1),
+ *              never negative: one float32 subtraction, or an exact integer saturating at 2^31 - 1; invalid: NaN / 0
+ *   extrema    uint8: 1 where the pixel is valid and its mask key exceeds the reconstruction's
+ *   out_valid  uint8: 1 at valid pixels */
+int insar_reconstruct_finish(const void* marker, const void* mask, int32_t elem_type, int32_t planes, int32_t H, int32_t W,
+                             int32_t mode, int32_t flip, int32_t has_nodata, double nodata, const uint8_t* valid, int32_t rounds_run,
+                             int32_t fill, void* scratch, void* out, void* residue, uint8_t* extrema, uint8_t* out_valid, void* stream);
+
 /* ---- distance transform (build-side addition; the reference has no post-processing): csrc/distance.hip --------------------
  * The exact squared Euclidean distance from every pixel of a map m [B][H][W] (row-major; uint8 with INSAR_DIST_U8, int32 with
  * INSAR_DIST_I32; B, H, W >= 1, H, W <= 32767, B * H * W < 2^31, no tile-multiple requirement) to the nearest SITE of the same

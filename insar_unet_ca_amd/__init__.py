@@ -30,6 +30,7 @@ from .warp import WarpSpec, draw_warps, gather_warped, grid_matrix, multilook, w
 from .stack import DetectionStack, StackScratch, follow_sites, site_series  # noqa: F401
 from .sieve import SieveScratch, region_adjacency, sieve_regions  # noqa: F401
 from .hysteresis import HysteresisScratch, hysteresis_regions  # noqa: F401
+from .reconstruct import ReconstructScratch, fill_sinks, h_dome, reconstruct_raster, reconstruct_tile, regional_extrema  # noqa: F401
 
 __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "ChannelAttentionModule", "MaxPool2d", "CrossEntropyLoss", "DiceLoss", "DiceCELoss", "Adam", "GraphedTrainStep",
            "compute_metrics", "train_model", "validate_model", "save_history", "VOCSegDataset", "SyntheticTiles",
@@ -52,3 +53,4 @@ __all__ = ["UNet", "DeepLabV3_SingleChannel_Attn", "DoubleConv", "SELayer", "Cha
            "DetectionStack", "StackScratch", "site_series", "follow_sites",
            "SieveScratch", "region_adjacency", "sieve_regions"]
 __all__ += ["HysteresisScratch", "hysteresis_regions"]
+__all__ += ["ReconstructScratch", "reconstruct_raster", "fill_sinks", "h_dome", "regional_extrema", "reconstruct_tile"]

@@ -26,6 +26,8 @@ ZONAL_F32, ZONAL_U8, ZONAL_I32 = 0, 1, 2
 WARP_U8, WARP_I32, WARP_F32 = 0, 1, 2
 WARP_NEAREST, WARP_BILINEAR = 0, 1
 FOCAL_MIN, FOCAL_MAX, FOCAL_MEDIAN = 0, 1, 2
+RECONSTRUCT_PLAIN, RECONSTRUCT_FILL, RECONSTRUCT_HDOME, RECONSTRUCT_EXTREMA = 0, 1, 2, 3
+RECONSTRUCT_MAX_ROUNDS = 65535
 IGEMM_OOB_ZERO = 1
 IGEMM_PINGPONG = 2
 
@@ -284,6 +286,11 @@ _SIGNATURES = {
     "insar_focal_smooth": [_P, _I, _I, _I, _I, _P, _I, C.c_double, _I, C.c_double, _P, _L, _I, _I, _P, _P, _P],
     "insar_focal_rank": [_P, _I, _I, _I, _I, _I, _I, _I, C.c_double, _P, _I, _I, _I, _P, _P, _P],
     "insar_focal_gradient": [_P, _I, _I, _I, _F, _F, _F, _F, _I, C.c_double, _P, _I, _P, _P, _P],
+    "insar_reconstruct_tile": [_P],
+    "insar_reconstruct_bytes": [_I, _I, _I, _P],
+    "insar_reconstruct_prepare": [_P, _P, _I, _I, _I, _I, _I, _I, _I, C.c_double, _I, _I, C.c_double, _P, _P, _P],
+    "insar_reconstruct_rounds": [_I, _I, _I, _I, _I, _I, _P, _P],
+    "insar_reconstruct_finish": [_P, _P, _I, _I, _I, _I, _I, _I, _I, C.c_double, _P, _I, _I, _P, _P, _P, _P, _P, _P],
     "insar_dist_scratch_bytes": [_I, _I, _I, _P],
     "insar_dist_transform": [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "insar_dist_boundary_counts": [_P, _P, _P, _P, _I, _I, _L, _I, _I, _P, _P],

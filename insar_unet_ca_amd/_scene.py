@@ -1,5 +1,5 @@
 """What the scene tools (regions, score, distance, outlines, simplify, skeletons, zonal, split, rasterise, stack, warp, crops,
-contours, focal) share on the host: the byte queries, the argument checks, the scratch buffers and the read-back. The host counterpart
+contours, focal, reconstruct) share on the host: the byte queries, the argument checks, the scratch buffers and the read-back. The host counterpart
 of csrc/scene_common.h. Every refusal is an InsarError that names the tool (`who`) and the argument."""
 from __future__ import annotations
 

@@ -1,6 +1,6 @@
 // What the scene tools (scene.hip, scene_valid.hip, regions.hip, augment.hip, overlap.hip, distance.hip, crops.hip, outline.hip,
 // skeleton.hip, raster.hip, zonal.hip, simplify.hip, contour_simplify.hip, split.hip, warp.hip, stack.hip, sieve.hip,
-// hysteresis.hip, contour.hip), the focal loss of focal.hip and the dropout kernel of deeplab.hip share: the counter hash, the guarded four-element access,
+// hysteresis.hip, contour.hip, reconstruct.hip), the focal loss of focal.hip and the dropout kernel of deeplab.hip share: the counter hash, the guarded four-element access,
 // the wave primitives (runs of equal keys, scan, max), the image / label quads of the two gather kernels and the host side's
 // small change (scratch layout, grids, pointer checks). Each file's kernels, launch geometry and argument checks are its own.
 #pragma once
