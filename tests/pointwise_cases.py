@@ -149,3 +149,33 @@ def rand_act(shape, T, seed, offset=0.3):
 def trunc_bf16(x):
     """fp32 -> bf16 by truncation (the wrong store, for the sensitivity test)."""
     return (x.float().contiguous().view(torch.int32) & -65536).view(torch.float32).to(BF16)
+
+
+# ---------------------------------------------------------------------------------------------------- bilinear resizes
+# id -> ((Hi, Wi), (Ho, Wo)): the 2x and the ragged up-sampling, shrinking (scale above 1: the adjoint's window comes from
+# divisions), equal sizes (the identity, bit for bit), one-pixel sources and destinations, the decoder's one-pixel resizes
+RESIZE_CASES = {
+    "up8": ((8, 8), (64, 64)), "up-ragged": ((5, 7), (13, 30)), "up12x20": ((12, 20), (96, 160)),
+    "down-ragged": ((13, 30), (5, 7)), "down8": ((64, 64), (8, 8)), "same": ((6, 9), (6, 9)),
+    "src1x1": ((1, 1), (5, 7)), "src1xW": ((1, 6), (4, 9)), "srcHx1": ((6, 1), (9, 4)), "dst1x1": ((5, 7), (1, 1)),
+    "plus1": ((24, 46), (25, 47)), "plus1w": ((8, 8), (8, 9)),
+}
+
+# float32 floor of tests/pointwise_ref.resize_fwd / resize_bwd over these cases (tests/test_pointwise_ref_host.py asserts it),
+# rounded up, and the K of the resizes: twice the largest, as the floor is above 1
+RESIZE_FLOOR = {"resize_fwd": 91.19, "resize_bwd": 110.52}
+RESIZE_K = 221.04
+
+
+def resize_case(name, T, B=2, Cn=64, seed=300):
+    """x [B][Hi][Wi][C] and the upstream gradient g [B][Ho][Wo][C], stored in T: magnitudes in [0.5, 1.5) with random signs.
+    The bounded range is what makes the rule's unit meaningful here: a float32 src moves a tap's weight by about 2^-24 * src
+    whatever the weight's own size, an error of that times |x1 - x0|, while U = sum |w * x| can be as small as the smallest
+    |x| among the taps; with normal deviates the float32 floor itself is then heavy-tailed (100 and more on these cases)."""
+    (hi, wi), (ho, wo) = RESIZE_CASES[name]
+    g = gen(seed + sorted(RESIZE_CASES).index(name))
+
+    def draw(*shape):
+        sign = torch.randint(0, 2, shape, generator=g).float() * 2 - 1
+        return (sign * (0.5 + torch.rand(shape, generator=g))).to(T)
+    return {"x": draw(B, hi, wi, Cn), "g": draw(B, ho, wo, Cn), "in": (hi, wi), "out": (ho, wo)}

@@ -269,6 +269,110 @@ def conv7x7s2_wgrad(x, dy_stored, T, rpb=8, dt=F64):
     return torch.stack(vs), (torch.stack(us) if dt == F64 else None)
 
 
+# ------------------------------------------------------------------------------------------------ bilinear resizes
+# insar_bilinear_fwd / _bwd (csrc/deeplab.hip, NCHW fp32) and insar_resize_bilinear_fwd / _bwd (csrc/pointwise.hip, NHWC slices),
+# from the formula of the kernels' comment: src = max((o + 1/2) * in / out - 1/2, 0), i0 = floor(src) clamped to in - 1,
+# i1 = min(i0 + 1, in - 1), the weight of i1 is the fractional part src - i0. Tensors here are NHWC [B][H][W][C]; the NCHW
+# kernels are the same function of a permuted view. `plant` names one deliberate error (tests/test_pointwise_ref_host.py shows
+# that the acceptance rule rejects each).
+RESIZE_PLANTS = ("i1_unclamped", "scale_inverted", "weights_swapped", "window_short")
+
+
+def resize_taps(n_out, n_in, dt=F64, plant=None):
+    """(i0, i1, l1) of every output index; dt = float32: as the kernels compute them (scale = (float)in / (float)out)."""
+    o = torch.arange(n_out, dtype=dt)
+    a, b = (n_out, n_in) if plant == "scale_inverted" else (n_in, n_out)
+    scale = torch.tensor(float(a), dtype=dt) / torch.tensor(float(b), dtype=dt)
+    src = ((o + 0.5) * scale - 0.5).clamp_min(0)
+    i0 = src.floor().to(torch.int64).clamp_max(n_in - 1)
+    i1 = (i0 + 1) % n_in if plant == "i1_unclamped" else (i0 + 1).clamp_max(n_in - 1)
+    l1 = src - i0.to(dt)
+    return (i0, i1, 1 - l1) if plant == "weights_swapped" else (i0, i1, l1)
+
+
+def resize_matrix(n_out, n_in, dt=F64, plant=None):
+    """A [n_out][n_in]: row o holds 1 - l1 at i0 and l1 at i1 (their sum where the two coincide)."""
+    i0, i1, l1 = resize_taps(n_out, n_in, dt, plant)
+    A = torch.zeros(n_out, n_in, dtype=dt)
+    rows = torch.arange(n_out)
+    A.index_put_((rows, i0), 1 - l1, accumulate=True)
+    A.index_put_((rows, i1), l1, accumulate=True)
+    return A
+
+
+def resize_fwd(x, hw_out, dt=F64, plant=None):
+    """The resized x [B][Hi][Wi][C] -> [B][Ho][Wo][C], unrounded, and U = sum |w_i * x_i| over the four taps."""
+    xx = _d(x, dt)
+    h0, h1, lh = resize_taps(hw_out[0], x.shape[1], dt, plant)
+    w0, w1, lw = resize_taps(hw_out[1], x.shape[2], dt, plant)
+    lh, lw = lh[None, :, None, None], lw[None, None, :, None]
+
+    def blend(v):
+        top = (1 - lw) * v[:, h0][:, :, w0] + lw * v[:, h0][:, :, w1]
+        bot = (1 - lw) * v[:, h1][:, :, w0] + lw * v[:, h1][:, :, w1]
+        return (1 - lh) * top + lh * bot
+    if dt != F64:
+        return blend(xx), None
+    return blend(xx), blend(xx.abs())
+
+
+def resize_bwd(g, hw_in, dt=F64, plant=None):
+    """The adjoint, unrounded: dx[b][i][j][c] = sum_{o, p} Ah[o][i] * Aw[p][j] * g[b][o][p][c], the explicit transpose of
+    resize_fwd's weights (no autograd), and U = sqrt(n) * sum |w * g| over the n = (rows with Ah[o][i] != 0) * (columns with
+    Aw[p][j] != 0) contributing taps. dt = float32: accumulated tap by tap in raster order of the output."""
+    gg = _d(g, dt)
+    B, Ho, Wo, Cn = g.shape
+    if dt != F64:
+        h0, h1, lh = resize_taps(Ho, hw_in[0], dt)
+        w0, w1, lw = resize_taps(Wo, hw_in[1], dt)
+        dx = torch.zeros(B, hw_in[0], hw_in[1], Cn, dtype=dt)
+        for o in range(Ho):
+            for hi, wh in ((int(h0[o]), 1 - lh[o]), (int(h1[o]), lh[o])):
+                for wi, ww in ((w0, 1 - lw), (w1, lw)):
+                    dx[:, hi].index_add_(1, wi, (wh * ww)[None, :, None] * gg[:, o])
+        return dx, None
+    def fold(v, n_in, dim, taps, count=False):
+        """sum over the outputs along `dim` of weight * v into their source indices (the transpose of one resize matrix)."""
+        i0, i1, l1 = taps
+        shape = [1] * v.dim()
+        shape[dim] = -1
+        out = torch.zeros(v.shape[:dim] + (n_in,) + v.shape[dim + 1:], dtype=dt)
+        for idx, wgt in ((i0, 1 - l1), (i1, l1)):
+            out.index_add_(dim, idx, (wgt != 0).to(dt).reshape(shape) * v if count else wgt.reshape(shape) * v)
+        return out
+    th, tw = resize_taps(Ho, hw_in[0], dt, plant), resize_taps(Wo, hw_in[1], dt, plant)
+    if plant == "window_short":                                 # the last output row never reaches the last source row
+        i0, i1, l1 = th
+        th = (torch.where(i0 == hw_in[0] - 1, 0, i0), torch.where(i1 == hw_in[0] - 1, 0, i1), l1)
+        gg = gg.clone()
+        gg[:, Ho - 1] = 0
+    dx = fold(fold(gg, hw_in[0], 1, th), hw_in[1], 2, tw)
+    unit = fold(fold(gg.abs(), hw_in[0], 1, th), hw_in[1], 2, tw)
+    # taps per source element: an output whose i0 and i1 coincide counts once
+    def ntaps(n_out, n_in, taps):
+        i0, i1, l1 = taps
+        A = torch.zeros(n_in, dtype=F64)
+        A.index_add_(0, i0, ((1 - l1 != 0) | ((i1 == i0) & (l1 != 0))).to(F64))
+        A.index_add_(0, i1, ((l1 != 0) & (i1 != i0)).to(F64))
+        return A
+    n = ntaps(Ho, hw_in[0], th)[:, None] * ntaps(Wo, hw_in[1], tw)[None, :]
+    return dx, n.sqrt()[None, :, :, None] * unit
+
+
+def resize_window(i, n_in, n_out, last_row_clamp=True):
+    """[lo, hi]: the output indices the gather-form adjoint kernels visit for source index i, in the kernels' float32
+    arithmetic. last_row_clamp = False: without the `if (i == n_in - 1) hi = n_out - 1` line."""
+    f = lambda v: torch.tensor(v, dtype=torch.float32)
+    s = f(float(n_in)) / f(float(n_out))
+    lo = int(torch.floor((f(float(i)) - 0.5) / s - 0.5)) - 1
+    hi = int(torch.ceil((f(float(i)) + 1.5) / s - 0.5)) + 1
+    if i == 0:
+        lo = 0
+    if last_row_clamp and i == n_in - 1:
+        hi = n_out - 1
+    return max(lo, 0), min(hi, n_out - 1)
+
+
 # ----------------------------------------------------------------------------------------------- the acceptance rule
 def excess(got, ref, unit, K, bf16_out=False):
     """max over the elements of |got - ref| / (2^-24 * U) after the half bf16 ulp a bf16 store may add: accepted iff <= K."""

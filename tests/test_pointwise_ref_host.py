@@ -263,3 +263,91 @@ def test_stem_and_colsum_mutants_are_rejected():
         if 256 < c["rows"] <= 1000:     # (one row of 65 600 lies inside the bound of so long a sum: the shorter two-stage cases see it)
             hit += rejected(lo - c["part"][:, 128], ref, u)                     # the first row of the second split skipped
     assert hit == sum(1 for v in PC.COLSUM_CASES.values() if 256 < v[1] <= 1000) > 0
+
+
+# ------------------------------------------------------------------------------------------------- bilinear resizes
+# The resizes keep a K of their own, fixed the same way: the float32 floor of R.resize_fwd / R.resize_bwd over PC.RESIZE_CASES
+# (rounded up), K_RESIZE = max(2.76, twice the largest). The floor is above 1 where src is not exact in float32: the weight of
+# a tap then carries an absolute error of about 2^-24 * src, whatever its own size (shrinking 13 x 30 -> 5 x 7, the ragged
+# up-samplings), and an output whose float32 src rounds to the other side of an integer takes the neighbouring index pair.
+# Measured: forward 91.19 (24 x 46 -> 25 x 47, src up to 45), adjoint 110.52 (13 x 30 -> 5 x 7); 0 for equal sizes, at most 3.1
+# where the scale is a power of two. The floor exceeds 1, so K_RESIZE = 2 * 110.52 (tests/pointwise_cases.py).
+FLOOR_RESIZE, K_RESIZE = PC.RESIZE_FLOOR, PC.RESIZE_K
+
+
+def test_resize_reference_against_interpolate_and_autograd():
+    for name in PC.RESIZE_CASES:
+        c = PC.resize_case(name, F32, Cn=8)
+        xr = nchw(c["x"].double()).contiguous().requires_grad_(True)
+        want = F.interpolate(xr, size=c["out"], mode="bilinear", align_corners=False)
+        ref, u = R.resize_fwd(c["x"], c["out"])
+        assert rel(ref, nhwc(want.detach())) <= 1e-12, name
+        assert bool((u >= ref.abs() * (1 - 1e-12)).all())
+        want.backward(nchw(c["g"].double()))
+        dref, du = R.resize_bwd(c["g"], c["in"])
+        assert rel(dref, nhwc(xr.grad)) <= 1e-12, name
+        assert bool((du >= dref.abs() * (1 - 1e-12)).all())
+        # <A x, g> = <x, A^T g>: the adjoint is the transpose of the forward's weights
+        assert abs(float((ref * c["g"].double()).sum() - (c["x"].double() * dref).sum())) <= 1e-9
+    c = PC.resize_case("same", BF16)
+    assert R.bits_equal(R.resize_fwd(c["x"], c["out"])[0], c["x"].double())       # equal sizes: the identity
+    assert R.bits_equal(R.resize_bwd(c["g"], c["in"])[0], c["g"].double())
+
+
+def resize_floor():
+    out = {"resize_fwd": {}, "resize_bwd": {}}
+    for T in (F32, BF16):
+        for name in PC.RESIZE_CASES:
+            c = PC.resize_case(name, T, Cn=8)
+            ref, u = R.resize_fwd(c["x"], c["out"])
+            out["resize_fwd"][name, T] = R.ratio(R.resize_fwd(c["x"], c["out"], dt=F32)[0], ref, u)
+            ref, u = R.resize_bwd(c["g"], c["in"])
+            out["resize_bwd"][name, T] = R.ratio(R.resize_bwd(c["g"], c["in"], dt=F32)[0], ref, u)
+    return out
+
+
+def test_resize_float32_floor_fixes_k():
+    got = resize_floor()
+    for k, per_case in got.items():
+        print(f"float32 floor {k}:", "  ".join(f"{n}-{PC.tname(T)} {v:.2f}" for (n, T), v in per_case.items()))
+        assert max(per_case.values()) <= FLOOR_RESIZE[k], (k, max(per_case.values()))
+    assert K_RESIZE == max(2.76, 2 * max(FLOOR_RESIZE.values()))
+    for name in ("same",):                                       # exact cases: float32 gives the float64 result
+        assert got["resize_fwd"][name, F32] == 0 and got["resize_bwd"][name, F32] == 0
+
+
+def test_resize_mutants_are_rejected():
+    hits = dict.fromkeys(R.RESIZE_PLANTS, 0)
+    for T in (F32, BF16):
+        for name in PC.RESIZE_CASES:
+            c = PC.resize_case(name, T, Cn=8)
+            ref, u = R.resize_fwd(c["x"], c["out"])
+            dref, du = R.resize_bwd(c["g"], c["in"])
+            assert not rejected_resize(ref, ref, u, T) and not rejected_resize(dref, dref, du, T)
+            for plant in R.RESIZE_PLANTS:
+                bad = R.resize_bwd(c["g"], c["in"], plant=plant)[0]
+                hit = rejected_resize(bad, dref, du, T)
+                if plant != "window_short":
+                    hit = hit and rejected_resize(R.resize_fwd(c["x"], c["out"], plant=plant)[0], ref, u, T)
+                hits[plant] += hit
+    print("resize mutants rejected on (cases x dtypes):", hits)
+    assert all(v > 0 for v in hits.values()), hits
+
+
+def rejected_resize(got, ref, unit, T):
+    return R.excess(got, ref, unit, K_RESIZE, T == BF16) > K_RESIZE
+
+
+def test_resize_adjoint_window_covers_every_tap():
+    """The gather-form adjoint visits the outputs [lo, hi] that R.resize_window computes in the kernels' float32 arithmetic:
+    every output whose float32 taps touch source index i must lie inside, for every extent pair of the cases. Without the
+    clamp of hi at the last source index the window is the same on all of them: the generic bound already reaches
+    n_out - 1 there (src(n_out - 1) < n_in), so that line is a safeguard no test can tell from its absence."""
+    pairs = {(a[k], b[k]) for a, b in PC.RESIZE_CASES.values() for k in (0, 1)}
+    for n_in, n_out in sorted(pairs):
+        i0, i1, l1 = R.resize_taps(n_out, n_in, F32)
+        for i in range(n_in):
+            touching = [o for o in range(n_out) if (int(i0[o]) == i and l1[o] < 1) or (int(i1[o]) == i and l1[o] > 0)]
+            lo, hi = R.resize_window(i, n_in, n_out)
+            assert not touching or (lo <= touching[0] and touching[-1] <= hi), (n_in, n_out, i)
+            assert R.resize_window(i, n_in, n_out, last_row_clamp=False) == (lo, hi), (n_in, n_out, i)
