@@ -34,9 +34,13 @@ __device__ __forceinline__ float lw_block_sum(float v, float* red) {
   return s;
 }
 
-// q^g without 0 * inf: g == 0 gives 1 for every q, q == 0 gives 0 for g > 0
-__device__ __forceinline__ float lw_powg(float q, float g) {
-  return g == 0.f ? 1.f : (q > 0.f ? __expf(g * __logf(q)) : 0.f);
+// q^g without 0 * inf: g == 0 gives 1 for every q, q == 0 gives 0 for g > 0. g multiplies the ABSOLUTE error of log q, and on a
+// misclassified pixel (q near 1, where the focal factor is largest) log q is small: __logf is good to about 2^-21 absolute
+// there and q = so / se carries 1.2e-7 of its own, which made q^5 wrong by 4e-6 of its value. So log q comes from the
+// full-precision functions, and above 1/2 from p_t = 1 - q, which is the small, relatively accurate one of the two.
+__device__ __forceinline__ float lw_powg(float q, float pt, float g) {
+  const float lq = q > 0.5f ? log1pf(-pt) : logf(q);
+  return g == 0.f ? 1.f : (q > 0.f ? __expf(g * lq) : 0.f);
 }
 
 // -log p_t with p_t = e_t / (e_t + so), so = the other classes' exponentials. On a confident pixel e_t + so rounds to e_t and
@@ -63,7 +67,7 @@ __device__ __forceinline__ float lw_pixel_num(const float (&v)[KM], const float 
       et = hit ? e[k] : et;
       so += (k < K && !hit) ? e[k] : 0.f;
     }
-    return wy * lw_powg(so * rse, tm.gamma) * lw_nll(vt, et, so, mx, lg);
+    return wy * lw_powg(so * rse, et * rse, tm.gamma) * lw_nll(vt, et, so, mx, lg);
   } else {
     const float nll_t = (mx - vt) + lg;
     float sm = 0.f;
@@ -87,15 +91,22 @@ __device__ __forceinline__ void lw_pixel_grad(const float (&v)[KM], const float 
       et = hit ? e[k] : et;
       so += (k < K && !hit) ? e[k] : 0.f;
     }
-    const float q = so * rse, pt = et * rse, logpt = -lw_nll(vt, et, so, mx, lg);
-    const float qg = lw_powg(q, tm.gamma);
-    // g q^(g-1) p_t log p_t as one guarded quantity: 0 for g == 0 (q^g / q may overflow for a denormal-sized q) and for q == 0
-    const float lead = (tm.gamma == 0.f || !(q > 0.f)) ? 0.f : tm.gamma * (qg / q) * pt * logpt;
-    const float c = wy * (lead - qg) * inv;
+    // From the fp32 exponentials on, the coefficient is formed in double and rounded once per element. On a misclassified
+    // pixel it exceeds 1 (at g = 2, p_t = 0.006 the two elements are -+1.04), and in fp32 the roundings of q^g, of
+    // lead - q^g and of the product with q alone add up to 2 half-ulps of it: more than a gradient held to 4 x 2e-8 of a
+    // scaled O(1) value may carry. The kernel stays bound by its loads and stores; the branches of lw_nll are kept.
+    const double sed = (double)et + (double)so, rsed = 1.0 / sed;
+    const double q = (double)so * rsed, pt = (double)et * rsed, g = (double)tm.gamma;
+    // so / e_t < 1/64 makes t the arg-max, e_t = exp(0) = 1 and the ratio so itself
+    const double logpt = -((et == 1.f && so < 0.015625f) ? log1p((double)so) : ((double)mx - (double)vt) + log(sed));
+    const double qg = tm.gamma == 0.f ? 1.0 : (q > 0.0 ? exp(g * log(q)) : 0.0);
+    // g q^(g-1) p_t log p_t as one guarded quantity: 0 for g == 0 and for q == 0
+    const double lead = (tm.gamma == 0.f || !(q > 0.0)) ? 0.0 : g * (qg / q) * pt * logpt;
+    const double c = (double)wy * (lead - qg) * (double)inv;
     // d_{k,t} - p_k: for k == t that is q itself, not 1 - p_t (which cancels on exactly the pixels the focal factor is for)
 #pragma unroll
     for (int k = 0; k < KM; ++k)
-      if (k < K) o[k] = c * (k == t ? q : -(e[k] * rse));
+      if (k < K) o[k] = (float)(c * (k == t ? q : -((double)e[k] * rsed)));
   } else {
     const float a = tm.ome * wy;
 #pragma unroll

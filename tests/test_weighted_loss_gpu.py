@@ -1,6 +1,8 @@
 """GPU: the imbalance-aware losses (csrc/loss_weighted.hip behind insar_unet_ca_amd/loss.py) against float64 torch on the
 CPU: F.cross_entropy(weight=, ignore_index=255, label_smoothing=) for the CE forms, the written-out focal expression under
-autograd, plus the oracle's soft Dice for the fused objective.
+autograd, plus the oracle's soft Dice for the fused objective. This file goes through the nn.Module layer; the per-launch
+coverage of the four C entry points (every dispatch arm, the second grid trip, the workspaces, stray labels, non-finite logits
+under ignored pixels, per-element gradient bounds) is tests/test_weighted_loss_kernels_gpu.py.
 
 Gates are those of the unweighted kernels (tests/test_parity_gpu.py, test_fused_dice_ce_against_oracle): loss |d| <= 2e-6,
 gradient max-rel <= 1e-4, for every case, focal included. max-rel is relative to the largest gradient of the batch and so says
