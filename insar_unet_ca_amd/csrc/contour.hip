@@ -10,43 +10,34 @@
 //   edges   quantise  per pixel: q (zonal.hip's rule) and the valid flag; the only kernel that sees a float
 //           mark      per word of four pixels: which of its eight lattice edges are crossings, level by level (q is loaded once
 //                     for all levels); crossings per level and block of 1024 pixels
-//           scan      one work-group: exclusive prefix sum of the counts in (level, block) order; E and the crossings per level
-//                     go to the table header
+//           scan      trace_common.h: the prefix sum of the counts in (level, block) order; E goes to the table header, and
+//                     CtTool's first_header writes the rest of it: no line yet, V = E, the crossings per level
 //           offsets   per level and word: the compact index of its first crossing
 //           link      per crossing: vertex, id, successor (the turn rule below) or none, "no predecessor" flag; pair (succ, k),
 //                     a crossing without successor (a tail) pointing at itself
-//   lead    R rounds of pointer doubling on pairs (jump, min): afterwards an element of a ring knows the ring's smallest
-//           crossing, an element of an open line has jumped to its tail (the fixed point), and "my jump target has no successor"
-//           tells the two apart
+//   lead    trace_common.h: after R rounds of pointer doubling an element of a ring knows the ring's smallest crossing, an
+//           element of an open line has jumped to its tail (the fixed point), and "my jump target has no successor" tells the
+//           two apart
 //   rank    cut       rings are cut in front of their leader, open lines end at their tail anyway: pair (next, 1) or (-1, 0);
 //                     lead[k] = the ring's leader, or -1 - tail for an open line, whose head writes itself at its tail's slot
-//           R rounds of Wyllie list ranking: d[k] becomes the distance from k to the last crossing of its line
-//   lines   count     leaders (ring minima and heads) and their line lengths per block of 1024 crossings
-//           scan      one work-group: both prefix sums; the number of lines goes to the header
-//           number    per leader: line number and first position; the line's record is initialised
+//           trace_common.h: after R rounds of list ranking d[k] is the distance from k to the last crossing of its line
+//   lines   trace_common.h (count / scan / number) with CtTool: a leader is a ring's minimum or the head of an open line; the
+//           number of lines goes to the header
 //   write   scatter   per crossing: position = line start + rank; the vertex goes there (every crossing is kept: V = E)
-//           reduce    over the ordered array, where a line is one contiguous run: area2 of the rings and the box (combined over
-//                     the runs of a wave before the atomics)
+//           reduce    over the ordered array, where a line is one contiguous run: area2 of the rings and the box by
+//                     trace_common.h's trace_reduce
 //
-// 11 + 2 R launches, a function of E alone (5 when E = 0). One launch per step and no work-group ever waits on another: every
-// round reads one pair buffer and writes the other. Integers only behind `quantise`; the atomics add int64 / take int32 minima
-// and maxima at agent scope, so their arrival order changes nothing. A round moves 24 bytes per crossing (8 read in index order,
+// 11 + 2 R launches, a function of E alone (5 when E = 0); how the steps are ordered and why the atomics' arrival order changes
+// nothing: trace_common.h. Integers only behind `quantise`. A round moves 24 bytes per crossing (8 read in index order,
 // 8 gathered, 8 written). Capacity: no kernel writes a crossing slot or a vertex >= max_vertices or a record > max_lines.
 //
 // The turn rule of `link`. The line runs with the above side on its right. Through a crossing it travels in direction d with the
 // above end A of the lattice edge on the right and the below end B on the left; the cell ahead has A' = A + d and B' = B + d. A'
 // below: turn right (leave through A - A'), unless B' is above and the saddle is joined (the four q sum to >= 4 q_l), then turn left
 // (leave through B - B'); A' above: left if B' is above too, else straight on (leave through A' - B').
-#include "scene_common.h"
-#include "block_scan.h"
-#include "list_rank.h"
-#include <limits.h>
+#include "trace_common.h"
 
-#define CT_THREADS 256
-#define CT_NB 1024                        // pixels / crossings per numbering block (256 threads x 4)
-#define CT_SCAN_THREADS 1024
 #define CT_MAX_LEVELS 32
-#define CT_MAX_CROSSINGS (1 << 30)
 #define CT_MAX_SIDE (1 << 22)             // 256 * side + 128 fits an int32
 #define CT_LIMIT 2147483647.0
 #define CT_HDR 4                          // records of the table header: 48 int32 slots
@@ -56,10 +47,37 @@
 #define CT_HDR_VERTS 5
 #define CT_HDR_LEVELS 16                  // .. 47: crossings per level
 
-static_assert(sizeof(InsarContourLine) == 48, "InsarContourLine is three 16-byte stores");
 static_assert(CT_HDR_LEVELS + CT_MAX_LEVELS == CT_HDR * (int)sizeof(InsarContourLine) / 4, "the level counts end the header");
 
 struct CtLevels { int q[CT_MAX_LEVELS]; };
+
+// what trace_common.h asks of its tool
+struct CtTool {
+  const int *lead, *eid;
+  const uint8_t* head;
+  InsarContourLine* lines;
+  int npix2;
+  __device__ __forceinline__ bool is_leader(int k) const {       // a ring's smallest crossing, or the head of an open line
+    return lead[k] == k || head[k];
+  }
+  __device__ __forceinline__ void init_record(int r, int k, int start, int len) const {     // area2 0, an empty box
+    const int e = eid[k];
+    int4* t4 = reinterpret_cast<int4*>(lines + CT_HDR + r);
+    t4[0] = make_int4(0, 0, (int)((uint32_t)e / (uint32_t)npix2), e);
+    t4[1] = make_int4(start, len, lead[k] >= 0, INT_MAX);
+    t4[2] = make_int4(INT_MAX, 0, 0, 0);
+  }
+  // behind the first scan of a call (a[] is L levels of nblk / L counts each; E in its slot): no line yet, V = E, the crossings
+  // per level, zero for the levels that are not there
+  __device__ __forceinline__ static void first_header(int* hdr, int t, int slot, int carry, const int* a, int nblk, int L) {
+    if (t < CT_HDR_LEVELS) {
+      hdr[t] = (t == slot || t == CT_HDR_VERTS) ? carry : 0;
+    } else if (t < CT_HDR_LEVELS + CT_MAX_LEVELS) {
+      const int l = t - CT_HDR_LEVELS, per = nblk / L;
+      hdr[t] = l < L ? (l + 1 < L ? a[(l + 1) * per] : carry) - a[l * per] : 0;
+    }
+  }
+};
 
 // ---------------------------------------------------------------------------------------------
 // edges: quantise / mark / scan / offsets / link
@@ -95,10 +113,10 @@ template <> struct CtRaster<uint8_t> {
 };
 
 template <typename T>
-__global__ void __launch_bounds__(CT_THREADS)
+__global__ void __launch_bounds__(TR_THREADS)
 contour_quantise_kernel(const T* __restrict__ raster, const uint8_t* __restrict__ valid, int npix, int rvec, int vvec, int vec,
                         double scale, int has_nodata, double nodata, int* __restrict__ q, uint8_t* __restrict__ ok) {
-  const int i = (blockIdx.x * CT_THREADS + threadIdx.x) * 4;
+  const int i = (blockIdx.x * TR_THREADS + threadIdx.x) * 4;
   if (i >= npix) return;
   typename CtRaster<T>::V v[4];
   CtRaster<T>::load(raster, i, npix, rvec, v);
@@ -123,13 +141,13 @@ contour_quantise_kernel(const T* __restrict__ raster, const uint8_t* __restrict_
   }
 }
 
-__global__ void __launch_bounds__(CT_THREADS)
+__global__ void __launch_bounds__(TR_THREADS)
 contour_mark_kernel(const int* __restrict__ q, const uint8_t* __restrict__ ok, int H, int W, int npix, int nq, int nblk, int L,
                     CtLevels lv, uint32_t* __restrict__ mask, int* __restrict__ counts) {
   __shared__ int cnt[CT_MAX_LEVELS];
   if (threadIdx.x < CT_MAX_LEVELS) cnt[threadIdx.x] = 0;
   __syncthreads();
-  const int t = blockIdx.x * CT_THREADS + threadIdx.x;
+  const int t = blockIdx.x * TR_THREADS + threadIdx.x;
   if (t < nq) {
     const int i = 4 * t;
     int qp[4], qr[4], qb[4];
@@ -172,36 +190,13 @@ contour_mark_kernel(const int* __restrict__ q, const uint8_t* __restrict__ ok, i
   if ((int)threadIdx.x < L) counts[threadIdx.x * nblk + blockIdx.x] = cnt[threadIdx.x];
 }
 
-// One work-group: a[] (and b[], nullable) become their exclusive prefix sums; the totals go to the header's int32 slots. With
-// L > 0 (the first scan of a call: a[] is L levels of nblk / L counts each) the rest of the header is written too: no line yet,
-// V = E, the crossings per level, zero for the levels that are not there.
-__global__ void __launch_bounds__(CT_SCAN_THREADS)
-contour_scan_kernel(int* __restrict__ a, int* __restrict__ b, int nblk, int* __restrict__ hdr, int slot_a, int slot_b, int L) {
-  __shared__ int w[CT_SCAN_THREADS / INSAR_WAVE];
-  const int carry_a = block_scan_array<CT_SCAN_THREADS>(a, nblk, w);                 // the new a[] is visible to every thread
-  const int carry_b = b ? block_scan_array<CT_SCAN_THREADS>(b, nblk, w) : 0;
-  const int t = threadIdx.x;
-  if (L > 0) {
-    if (t < CT_HDR_LEVELS) {
-      hdr[t] = (t == slot_a || t == CT_HDR_VERTS) ? carry_a : 0;
-    } else if (t < CT_HDR_LEVELS + CT_MAX_LEVELS) {
-      const int l = t - CT_HDR_LEVELS, per = nblk / L;
-      hdr[t] = l < L ? (l + 1 < L ? a[(l + 1) * per] : carry_a) - a[l * per] : 0;
-    }
-  } else if (t == slot_a) {
-    hdr[t] = carry_a;
-  } else if (b && t == slot_b) {
-    hdr[t] = carry_b;
-  }
-}
-
-__global__ void __launch_bounds__(CT_THREADS)
+__global__ void __launch_bounds__(TR_THREADS)
 contour_offsets_kernel(const uint32_t* __restrict__ mask, int nq, int nblk, const int* __restrict__ counts, int* __restrict__ off4) {
-  __shared__ int wsum[CT_THREADS / INSAR_WAVE];
-  const int l = blockIdx.y, t = blockIdx.x * CT_THREADS + threadIdx.x;
+  __shared__ int wsum[TR_THREADS / INSAR_WAVE];
+  const int l = blockIdx.y, t = blockIdx.x * TR_THREADS + threadIdx.x;
   const uint32_t w = t < nq ? mask[l * nq + t] : 0u;
   int total;
-  const int o = counts[l * nblk + blockIdx.x] + block_prefix_sum<CT_THREADS>(__popc(w), wsum, &total);
+  const int o = counts[l * nblk + blockIdx.x] + block_prefix_sum<TR_THREADS>(__popc(w), wsum, &total);
   if (t < nq) off4[l * nq + t] = o;
 }
 
@@ -211,11 +206,11 @@ __device__ __forceinline__ int ct_index(const uint32_t* __restrict__ mask, const
   return off4[w] + __popc(mask[w] & ((1u << (8 * (p & 3) + o)) - 1u));
 }
 
-__global__ void __launch_bounds__(CT_THREADS)
+__global__ void __launch_bounds__(TR_THREADS)
 contour_link_kernel(const int* __restrict__ q, const uint8_t* __restrict__ ok, const uint32_t* __restrict__ mask,
                     const int* __restrict__ off4, int H, int W, int npix, int nq, CtLevels lv, int cap, int* __restrict__ succ0,
                     int* __restrict__ eid, int2* __restrict__ vert, uint8_t* __restrict__ head, int2* __restrict__ pair) {
-  const int l = blockIdx.y, t = blockIdx.x * CT_THREADS + threadIdx.x;
+  const int l = blockIdx.y, t = blockIdx.x * TR_THREADS + threadIdx.x;
   if (t >= nq) return;
   const int base = l * nq;
   const uint32_t m4 = mask[base + t];
@@ -273,10 +268,10 @@ contour_link_kernel(const int* __restrict__ q, const uint8_t* __restrict__ ok, c
 // ---------------------------------------------------------------------------------------------
 // lead / rank: the rounds are list_rank.h's; `cut` between them
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(CT_THREADS)
+__global__ void __launch_bounds__(TR_THREADS)
 contour_cut_kernel(const int2* __restrict__ in, const int* __restrict__ succ0, const uint8_t* __restrict__ head,
                    int* __restrict__ lead, int* __restrict__ headof, int2* __restrict__ out, int n) {
-  const int k = blockIdx.x * CT_THREADS + threadIdx.x;
+  const int k = blockIdx.x * TR_THREADS + threadIdx.x;
   if (k >= n) return;
   const int2 a = in[k];
   const int s = succ0[k];
@@ -291,71 +286,13 @@ contour_cut_kernel(const int2* __restrict__ in, const int* __restrict__ succ0, c
 }
 
 // ---------------------------------------------------------------------------------------------
-// lines: count / scan / number
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool ct_is_leader(const int* __restrict__ lead, const uint8_t* __restrict__ head, int k) {
-  return lead[k] == k || head[k];                                // a ring's smallest crossing, or the head of an open line
-}
-
-__global__ void __launch_bounds__(CT_THREADS)
-contour_line_count_kernel(const int* __restrict__ lead, const uint8_t* __restrict__ head, const int2* __restrict__ dist, int n,
-                          int* __restrict__ lcnt, int* __restrict__ llen) {
-  __shared__ int wsum[CT_THREADS / INSAR_WAVE];
-  const int k0 = blockIdx.x * CT_NB + threadIdx.x * 4;
-  int c = 0, l = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int k = k0 + j;
-    if (k < n && ct_is_leader(lead, head, k)) { ++c; l += dist[k].y + 1; }
-  }
-  int tc, tl;
-  block_prefix_sum<CT_THREADS>(c, wsum, &tc);
-  block_prefix_sum<CT_THREADS>(l, wsum, &tl);
-  if (threadIdx.x == 0) { lcnt[blockIdx.x] = tc; llen[blockIdx.x] = tl; }
-}
-
-__global__ void __launch_bounds__(CT_THREADS)
-contour_line_number_kernel(const int* __restrict__ lead, const uint8_t* __restrict__ head, const int2* __restrict__ dist,
-                           const int* __restrict__ eid, int n, int npix2, const int* __restrict__ lcnt, const int* __restrict__ llen,
-                           int2* __restrict__ info, InsarContourLine* __restrict__ lines, int max_lines) {
-  __shared__ int wsum[CT_THREADS / INSAR_WAVE];
-  const int k0 = blockIdx.x * CT_NB + threadIdx.x * 4;
-  bool is[4];
-  int len[4], c = 0, l = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int k = k0 + j;
-    is[j] = k < n && ct_is_leader(lead, head, k);
-    len[j] = is[j] ? dist[k].y + 1 : 0;
-    c += is[j]; l += len[j];
-  }
-  int tc, tl;
-  int r = lcnt[blockIdx.x] + block_prefix_sum<CT_THREADS>(c, wsum, &tc);
-  int st = llen[blockIdx.x] + block_prefix_sum<CT_THREADS>(l, wsum, &tl);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (!is[j]) continue;
-    const int k = k0 + j;
-    info[k] = make_int2(r, st);
-    if (r < max_lines) {                                         // area2 0, an empty box
-      const int e = eid[k];
-      int4* t4 = reinterpret_cast<int4*>(lines + CT_HDR + r);
-      t4[0] = make_int4(0, 0, (int)((uint32_t)e / (uint32_t)npix2), e);
-      t4[1] = make_int4(st, len[j], lead[k] >= 0, INT_MAX);
-      t4[2] = make_int4(INT_MAX, 0, 0, 0);
-    }
-    ++r; st += len[j];
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
 // write: scatter / reduce
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(CT_THREADS)
+__global__ void __launch_bounds__(TR_THREADS)
 contour_scatter_kernel(const int* __restrict__ lead, const int* __restrict__ headof, const int2* __restrict__ dist,
                        const int2* __restrict__ info, const int2* __restrict__ vert, int n, int* __restrict__ ometa,
                        int2* __restrict__ vertices) {
-  const int k = blockIdx.x * CT_THREADS + threadIdx.x;
+  const int k = blockIdx.x * TR_THREADS + threadIdx.x;
   if (k >= n) return;
   const int l = lead[k];
   const int m = l >= 0 ? l : headof[-1 - l];
@@ -367,10 +304,10 @@ contour_scatter_kernel(const int* __restrict__ lead, const int* __restrict__ hea
   vertices[pos] = vert[k];
 }
 
-__global__ void __launch_bounds__(CT_THREADS)
+__global__ void __launch_bounds__(TR_THREADS)
 contour_reduce_kernel(const int2* __restrict__ vertices, const int* __restrict__ ometa, int n,
                       InsarContourLine* __restrict__ lines, int max_lines) {
-  const int i = blockIdx.x * CT_THREADS + threadIdx.x;
+  const int i = blockIdx.x * TR_THREADS + threadIdx.x;
   int key = -1, vy = 0, vx = 0;
   long long a2 = 0;
   if (i < n) {
@@ -386,19 +323,7 @@ contour_reduce_kernel(const int2* __restrict__ vertices, const int* __restrict__
       }
     }
   }
-  const WaveRuns runs = wave_runs(key);
-  const long long ta = wave_run_reduce(runs, a2, WaveAdd());
-  const int y0 = wave_run_reduce(runs, vy, WaveMin()), y1 = wave_run_reduce(runs, vy + 1, WaveMax());
-  const int x0 = wave_run_reduce(runs, vx, WaveMin()), x1 = wave_run_reduce(runs, vx + 1, WaveMax());
-  if (runs.head && key >= 0) {
-    InsarContourLine* r = lines + CT_HDR + key;
-    if (ta) atomicAdd(reinterpret_cast<unsigned long long*>(&r->area2), (unsigned long long)ta);
-    // the box only tightens: a stale read can cost a redundant atomic, never lose an update
-    if (y0 < __hip_atomic_load(&r->y0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&r->y0, y0);
-    if (x0 < __hip_atomic_load(&r->x0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&r->x0, x0);
-    if (y1 > __hip_atomic_load(&r->y1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&r->y1, y1);
-    if (x1 > __hip_atomic_load(&r->x1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&r->x1, x1);
-  }
+  trace_reduce(wave_runs(key), reinterpret_cast<TraceRecord*>(lines + CT_HDR), key, max_lines, a2, vy, vx);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -415,14 +340,13 @@ static int contour_layout(const char* who, int32_t H, int32_t W, int32_t n_level
   const int64_t npix = (int64_t)H * W;
   if (npix * n_levels >= ((int64_t)1 << 30))
     INSAR_FAIL(INSAR_E_SHAPE, "%s: n_levels * H * W = %d * %d * %d is 2^30 or more", who, n_levels, H, W);
-  if (max_vertices < 1 || max_vertices > CT_MAX_CROSSINGS)
-    INSAR_FAIL(INSAR_E_SHAPE, "%s: max_vertices %d outside 1 .. 2^30", who, max_vertices);
+  if (int rc = trace_check_capacity(who, "max_vertices", max_vertices)) return rc;
   L->npix = (int)npix;
   L->nq = (int)((npix + 3) / 4);
-  L->nblk = (L->nq + CT_THREADS - 1) / CT_THREADS;
+  L->nblk = (L->nq + TR_THREADS - 1) / TR_THREADS;
   L->L = n_levels;
   L->cap = max_vertices;
-  L->eblk = (max_vertices + CT_NB - 1) / CT_NB;
+  L->eblk = (max_vertices + TR_NB - 1) / TR_NB;
   ScratchTake take;
   const int64_t cap = max_vertices, words = (int64_t)n_levels * L->nq;
   L->q = take(npix * 4);       L->ok = take(npix);         L->mask = take(words * 4);   L->off4 = take(words * 4);
@@ -434,13 +358,8 @@ static int contour_layout(const char* who, int32_t H, int32_t W, int32_t n_level
   L->bytes = take.at;
   return INSAR_OK;
 }
-static int contour_check_lines(const char* who, const void* table, int32_t max_lines) {
-  if (max_lines < 1 || max_lines > CT_MAX_CROSSINGS) INSAR_FAIL(INSAR_E_SHAPE, "%s: max_lines %d outside 1 .. 2^30", who, max_lines);
-  return scene_check_buffer(who, "table", table);
-}
 static int contour_check_count(const char* who, int32_t n, const CtLayout& L) {
-  if (n < 0 || n > L.cap) INSAR_FAIL(INSAR_E_SHAPE, "%s: n_crossings %d outside 0 .. max_vertices=%d", who, n, L.cap);
-  return INSAR_OK;
+  return trace_check_count(who, "n_crossings", n, "max_vertices", L.cap);
 }
 
 extern "C" int insar_contour_scratch_bytes(int32_t H, int32_t W, int32_t n_levels, int32_t max_lines, int32_t max_vertices,
@@ -449,7 +368,7 @@ extern "C" int insar_contour_scratch_bytes(int32_t H, int32_t W, int32_t n_level
   if (!scratch_bytes || !table_bytes) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer", who);
   CtLayout L;
   if (int rc = contour_layout(who, H, W, n_levels, max_vertices, &L)) return rc;
-  if (max_lines < 1 || max_lines > CT_MAX_CROSSINGS) INSAR_FAIL(INSAR_E_SHAPE, "%s: max_lines %d outside 1 .. 2^30", who, max_lines);
+  if (int rc = trace_check_capacity(who, "max_lines", max_lines)) return rc;
   *scratch_bytes = L.bytes;
   *table_bytes = (int64_t)sizeof(InsarContourLine) * ((int64_t)max_lines + CT_HDR);
   return INSAR_OK;
@@ -464,7 +383,7 @@ static void contour_launch_quantise(const void* raster, const uint8_t* valid, co
                                     double nodata, void* scratch, hipStream_t s) {
   const int vec = L.npix % 4 == 0;
   const int rvec = vec && insar_aligned16(raster), vvec = vec && valid && ((((uintptr_t)valid) & 3u) == 0);
-  hipLaunchKernelGGL(contour_quantise_kernel<T>, dim3(scene_blocks(L.nq, CT_THREADS)), dim3(CT_THREADS), 0, s, (const T*)raster, valid,
+  hipLaunchKernelGGL(contour_quantise_kernel<T>, dim3(scene_blocks(L.nq, TR_THREADS)), dim3(TR_THREADS), 0, s, (const T*)raster, valid,
                      L.npix, rvec, vvec, vec, scale, has_nodata, nodata, scratch_at<int>(scratch, L.q), scratch_at<uint8_t>(scratch, L.ok));
 }
 
@@ -495,24 +414,22 @@ extern "C" int insar_contour_edges(const void* raster, int32_t elem_type, int32_
   const uint8_t* ok = scratch_at<uint8_t>(scratch, L.ok);
   uint32_t* mask = scratch_at<uint32_t>(scratch, L.mask);
   int *off4 = scratch_at<int>(scratch, L.off4), *counts = scratch_at<int>(scratch, L.counts);
-  hipLaunchKernelGGL(contour_mark_kernel, dim3((unsigned)L.nblk), dim3(CT_THREADS), 0, s, q, ok, H, W, L.npix, L.nq, L.nblk, L.L, lv,
+  hipLaunchKernelGGL(contour_mark_kernel, dim3((unsigned)L.nblk), dim3(TR_THREADS), 0, s, q, ok, H, W, L.npix, L.nq, L.nblk, L.L, lv,
                      mask, counts);
   INSAR_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(contour_scan_kernel, dim3(1), dim3(CT_SCAN_THREADS), 0, s, counts, (int*)nullptr, L.L * L.nblk, (int*)table,
-                     CT_HDR_CROSSINGS, -1, L.L);
+  hipLaunchKernelGGL(trace_scan_kernel<CtTool>, dim3(1), dim3(TR_SCAN_THREADS), 0, s, counts, (int*)nullptr, L.L * L.nblk, (int*)table,
+                     CT_HDR_CROSSINGS, L.L);
   INSAR_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(contour_offsets_kernel, dim3((unsigned)L.nblk, (unsigned)L.L), dim3(CT_THREADS), 0, s, (const uint32_t*)mask,
+  hipLaunchKernelGGL(contour_offsets_kernel, dim3((unsigned)L.nblk, (unsigned)L.L), dim3(TR_THREADS), 0, s, (const uint32_t*)mask,
                      L.nq, L.nblk, (const int*)counts, off4);
   INSAR_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(contour_link_kernel, dim3((unsigned)L.nblk, (unsigned)L.L), dim3(CT_THREADS), 0, s, q, ok, (const uint32_t*)mask,
+  hipLaunchKernelGGL(contour_link_kernel, dim3((unsigned)L.nblk, (unsigned)L.L), dim3(TR_THREADS), 0, s, q, ok, (const uint32_t*)mask,
                      (const int*)off4, H, W, L.npix, L.nq, lv, L.cap, scratch_at<int>(scratch, L.succ0), scratch_at<int>(scratch, L.eid),
                      scratch_at<int2>(scratch, L.vert), scratch_at<uint8_t>(scratch, L.head), scratch_at<int2>(scratch, L.p0));
   INSAR_CHECK_LAUNCH(who);
   return INSAR_OK;
 }
 
-// The pair buffers: `link` fills p0, `lead` runs from there, `cut` reads its result and writes the other buffer, `rank` goes on from
-// there: the final distances are in p1 whatever R is, and p0 is free for `lines` (list_rank.h).
 extern "C" int insar_contour_lead(int32_t H, int32_t W, int32_t n_levels, int32_t n_crossings, int32_t max_vertices, void* scratch,
                                   void* stream) {
   const char* who = "insar_contour_lead";
@@ -521,8 +438,7 @@ extern "C" int insar_contour_lead(int32_t H, int32_t W, int32_t n_levels, int32_
   if (int rc = contour_check_count(who, n_crossings, L)) return rc;
   if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   if (n_crossings == 0) return INSAR_OK;
-  int2* const p[2] = {scratch_at<int2>(scratch, L.p0), scratch_at<int2>(scratch, L.p1)};
-  return list_lead<CT_THREADS>(p, 0, n_crossings, (hipStream_t)stream, who);
+  return trace_lead(scratch_at<int2>(scratch, L.p0), scratch_at<int2>(scratch, L.p1), n_crossings, (hipStream_t)stream, who);
 }
 
 extern "C" int insar_contour_rank(int32_t H, int32_t W, int32_t n_levels, int32_t n_crossings, int32_t max_vertices, void* scratch,
@@ -533,14 +449,13 @@ extern "C" int insar_contour_rank(int32_t H, int32_t W, int32_t n_levels, int32_
   if (int rc = contour_check_count(who, n_crossings, L)) return rc;
   if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   if (n_crossings == 0) return INSAR_OK;
-  int2* const p[2] = {scratch_at<int2>(scratch, L.p0), scratch_at<int2>(scratch, L.p1)};
-  const int led = list_rounds(n_crossings) & 1;                  // where `lead` ended
-  hipLaunchKernelGGL(contour_cut_kernel, dim3(scene_blocks(n_crossings, CT_THREADS)), dim3(CT_THREADS), 0, (hipStream_t)stream,
-                     (const int2*)p[led], (const int*)scratch_at<int>(scratch, L.succ0),
-                     (const uint8_t*)scratch_at<uint8_t>(scratch, L.head), scratch_at<int>(scratch, L.lead),
-                     scratch_at<int>(scratch, L.headof), p[led ^ 1], n_crossings);
-  INSAR_CHECK_LAUNCH(who);
-  return list_rank<CT_THREADS>(p, led ^ 1, n_crossings, (hipStream_t)stream, who);
+  hipStream_t s = (hipStream_t)stream;
+  auto cut = [&](const int2* in, int2* out) {
+    hipLaunchKernelGGL(contour_cut_kernel, dim3(scene_blocks(n_crossings, TR_THREADS)), dim3(TR_THREADS), 0, s, in,
+                       (const int*)scratch_at<int>(scratch, L.succ0), (const uint8_t*)scratch_at<uint8_t>(scratch, L.head),
+                       scratch_at<int>(scratch, L.lead), scratch_at<int>(scratch, L.headof), out, n_crossings);
+  };
+  return trace_cut_and_rank(cut, scratch_at<int2>(scratch, L.p0), scratch_at<int2>(scratch, L.p1), n_crossings, s, who);
 }
 
 extern "C" int insar_contour_lines(int32_t H, int32_t W, int32_t n_levels, int32_t n_crossings, int32_t max_lines,
@@ -549,27 +464,12 @@ extern "C" int insar_contour_lines(int32_t H, int32_t W, int32_t n_levels, int32
   CtLayout L;
   if (int rc = contour_layout(who, H, W, n_levels, max_vertices, &L)) return rc;
   if (int rc = contour_check_count(who, n_crossings, L)) return rc;
-  if (int rc = contour_check_lines(who, table, max_lines)) return rc;
+  if (int rc = trace_check_table(who, "max_lines", max_lines, table)) return rc;
   if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const int nblk = (int)scene_blocks(n_crossings, CT_NB);
-  int *lead = scratch_at<int>(scratch, L.lead), *lcnt = scratch_at<int>(scratch, L.lcnt), *llen = scratch_at<int>(scratch, L.llen);
-  const uint8_t* head = scratch_at<uint8_t>(scratch, L.head);
-  const int2* dist = scratch_at<int2>(scratch, L.p1);
-  if (nblk > 0) {
-    hipLaunchKernelGGL(contour_line_count_kernel, dim3((unsigned)nblk), dim3(CT_THREADS), 0, s, (const int*)lead, head, dist,
-                       n_crossings, lcnt, llen);
-    INSAR_CHECK_LAUNCH(who);
-  }
-  hipLaunchKernelGGL(contour_scan_kernel, dim3(1), dim3(CT_SCAN_THREADS), 0, s, lcnt, llen, nblk, (int*)table, CT_HDR_LINES, -1, 0);
-  INSAR_CHECK_LAUNCH(who);
-  if (nblk > 0) {
-    hipLaunchKernelGGL(contour_line_number_kernel, dim3((unsigned)nblk), dim3(CT_THREADS), 0, s, (const int*)lead, head, dist,
-                       (const int*)scratch_at<int>(scratch, L.eid), n_crossings, 2 * L.npix, (const int*)lcnt, (const int*)llen,
-                       scratch_at<int2>(scratch, L.p0), (InsarContourLine*)table, max_lines);
-    INSAR_CHECK_LAUNCH(who);
-  }
-  return INSAR_OK;
+  const CtTool tool = {scratch_at<int>(scratch, L.lead), scratch_at<int>(scratch, L.eid), scratch_at<uint8_t>(scratch, L.head),
+                       (InsarContourLine*)table, 2 * L.npix};
+  return trace_number(tool, scratch_at<int2>(scratch, L.p1), n_crossings, scratch_at<int>(scratch, L.lcnt), scratch_at<int>(scratch, L.llen),
+                      scratch_at<int2>(scratch, L.p0), table, CT_HDR_LINES, max_lines, (hipStream_t)stream, who);
 }
 
 extern "C" int insar_contour_write(int32_t H, int32_t W, int32_t n_levels, int32_t n_crossings, int32_t max_lines,
@@ -578,20 +478,20 @@ extern "C" int insar_contour_write(int32_t H, int32_t W, int32_t n_levels, int32
   CtLayout L;
   if (int rc = contour_layout(who, H, W, n_levels, max_vertices, &L)) return rc;
   if (int rc = contour_check_count(who, n_crossings, L)) return rc;
-  if (int rc = contour_check_lines(who, table, max_lines)) return rc;
+  if (int rc = trace_check_table(who, "max_lines", max_lines, table)) return rc;
   if (!vertices) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer (vertices)", who);
   if (((uintptr_t)vertices) & 7u) INSAR_FAIL(INSAR_E_ALIGN, "%s: vertices not 8-byte aligned", who);
   if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   if (n_crossings == 0) return INSAR_OK;
   hipStream_t s = (hipStream_t)stream;
-  const unsigned grid = scene_blocks(n_crossings, CT_THREADS);
+  const unsigned grid = scene_blocks(n_crossings, TR_THREADS);
   int* ometa = scratch_at<int>(scratch, L.ometa);
-  hipLaunchKernelGGL(contour_scatter_kernel, dim3(grid), dim3(CT_THREADS), 0, s, (const int*)scratch_at<int>(scratch, L.lead),
+  hipLaunchKernelGGL(contour_scatter_kernel, dim3(grid), dim3(TR_THREADS), 0, s, (const int*)scratch_at<int>(scratch, L.lead),
                      (const int*)scratch_at<int>(scratch, L.headof), (const int2*)scratch_at<int2>(scratch, L.p1),
                      (const int2*)scratch_at<int2>(scratch, L.p0), (const int2*)scratch_at<int2>(scratch, L.vert), n_crossings, ometa,
                      reinterpret_cast<int2*>(vertices));
   INSAR_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(contour_reduce_kernel, dim3(grid), dim3(CT_THREADS), 0, s, (const int2*)reinterpret_cast<int2*>(vertices),
+  hipLaunchKernelGGL(contour_reduce_kernel, dim3(grid), dim3(TR_THREADS), 0, s, (const int2*)reinterpret_cast<int2*>(vertices),
                      (const int*)ometa, n_crossings, (InsarContourLine*)table, max_lines);
   INSAR_CHECK_LAUNCH(who);
   return INSAR_OK;

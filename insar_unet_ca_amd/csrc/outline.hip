@@ -5,41 +5,28 @@
 // index" are the same thing and every array below is indexed by k. With E edges and L = ceil(log2 E):
 //
 //   edges   mark     per pixel: the 4-bit side mask; boundary edges per block of 1024 pixels
-//           scan     one work-group: exclusive prefix sum of the block counts; E goes to the table header
+//           scan     trace_common.h: the prefix sum of the block counts; E goes to the table header, the rest of it is cleared
 //           offsets  per pixel: the compact index of its first edge
 //           link     per edge: successor (the turn rule), id, "the successor turns" flag; pair (succ, k) for `lead`
-//   lead    L rounds of pointer doubling on pairs (jump, min): (j, m)[k] <- (j[j[k]], min(m[k], m[j[k]])); after them m[k]
-//           is the smallest edge of k's ring, its leader
+//   lead    trace_common.h: after L rounds of pointer doubling every edge knows the smallest edge of its ring, its leader
 //   rank    cut      every ring is cut in front of its leader: pair (next, d) = (succ, 1), or (-1, 0) for the last edge
-//           L rounds of Wyllie list ranking on the pairs: d[k] becomes the distance from k to the last edge of its ring
-//   rings   count    leaders and their ring lengths per block of 1024 edges
-//           scan     one work-group: both prefix sums; R goes to the header
-//           number   per leader: ring number and first position in the ordered array; the ring's record is initialised
+//           trace_common.h: after L rounds of list ranking d[k] is the distance from k to the last edge of its ring
+//   rings   trace_common.h (count / scan / number) with OlTool: a leader is lead[k] == k; R goes to the header
 //   write   scatter  per edge: position = ring start + rank; tail vertex, ring number and side go there, the corner flag of
 //                    the SUCCESSOR goes to the successor's position
-//           reduce   over the ordered array, where a ring is one contiguous run: area2, box and kept-vertex count (combined
-//                    over the runs of a wave before the atomics); kept vertices per block of 256 positions
-//           scan     one work-group: prefix sum of the kept counts; V goes to the header
+//           reduce   over the ordered array, where a ring is one contiguous run: area2 and box by trace_common.h's
+//                    trace_reduce, the kept-vertex count with them; kept vertices per block of 256 positions
+//           scan     trace_common.h: prefix sum of the kept counts; V goes to the header
 //           compact  kept vertices to their final place; every ring's `start`
 //
-// 12 + 2 L launches, a function of E alone. One launch per step and no work-group ever waits on another: every round reads one
-// buffer and writes the other, ordered by kernel boundaries on the caller's stream. Integers only: the atomics add int64 /
-// take int32 minima and maxima, so their arrival order changes nothing. A round moves 24 bytes per edge: 8 read in index
-// order, 8 gathered, 8 written; the pair packing makes the gather one 8-byte access instead of two 4-byte ones.
+// 12 + 2 L launches, a function of E alone; how the steps are ordered and why the atomics' arrival order changes nothing:
+// trace_common.h. Integers only. A round moves 24 bytes per edge: 8 read in index order, 8 gathered, 8 written; the pair
+// packing makes the gather one 8-byte access instead of two 4-byte ones.
 // Capacity: no kernel writes an edge slot >= max_edges, a record > max_rings or a vertex >= max_vertices; lead / rank / rings /
 // write take the edge count read back from the header and refuse one above max_edges.
-#include "scene_common.h"
-#include "block_scan.h"
-#include "list_rank.h"
-#include <limits.h>
+#include "trace_common.h"
 
-#define OL_THREADS 256
-#define OL_NB 1024                        // pixels / edges per numbering block (256 threads x 4)
-#define OL_SCAN_THREADS 1024
-#define OL_MAX_EDGES (1 << 30)
 #define OL_MAX_PIX ((int64_t)1 << 29)
-
-static_assert(sizeof(InsarRing) == 48, "InsarRing is three 16-byte stores");
 // int32 slots of the header record (InsarRing: area2 0-1, label 2, leader 3, start 4, count 5, edges 6, ...)
 #define OL_HDR_RINGS 2
 #define OL_HDR_VERTS 5
@@ -47,14 +34,32 @@ static_assert(sizeof(InsarRing) == 48, "InsarRing is three 16-byte stores");
 
 __device__ __forceinline__ int ol_below(int mask, int s) { return __popc(mask & ((1 << s) - 1)); }
 
+// what trace_common.h asks of its tool
+struct OlTool {
+  const int *lead, *eid, *labels;
+  InsarRing* rings;
+  __device__ __forceinline__ bool is_leader(int k) const { return lead[k] == k; }
+  __device__ __forceinline__ void init_record(int r, int k, int, int len) const {      // area2 0, start / count by `write`, an empty box
+    const int e = eid[k];
+    int4* t4 = reinterpret_cast<int4*>(rings + 1 + r);
+    t4[0] = make_int4(0, 0, labels[e >> 2], e);
+    t4[1] = make_int4(0, 0, len, INT_MAX);
+    t4[2] = make_int4(INT_MAX, 0, 0, 0);
+  }
+  // behind the first scan of a call E stands in its slot and the rest of the header record is cleared
+  __device__ __forceinline__ static void first_header(int* hdr, int t, int slot, int carry, const int*, int, int) {
+    if (t < (int)(sizeof(InsarRing) / 4)) hdr[t] = t == slot ? carry : 0;
+  }
+};
+
 // ---------------------------------------------------------------------------------------------
 // edges: mark / scan / offsets / link
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(OL_THREADS)
+__global__ void __launch_bounds__(TR_THREADS)
 outline_mark_kernel(const int* __restrict__ labels, int H, int W, int npix, int vec, uint8_t* __restrict__ mask,
                     int* __restrict__ counts) {
-  __shared__ int wsum[OL_THREADS / INSAR_WAVE];
-  const int i = blockIdx.x * OL_NB + threadIdx.x * 4;
+  __shared__ int wsum[TR_THREADS / INSAR_WAVE];
+  const int i = blockIdx.x * TR_NB + threadIdx.x * 4;
   int v[4];
   quad_load(labels, i, npix, vec && i < npix, 0, v);
   uint32_t m4 = 0;
@@ -81,34 +86,19 @@ outline_mark_kernel(const int* __restrict__ labels, int H, int W, int npix, int 
     }
   }
   int total;
-  block_prefix_sum<OL_THREADS>(__popc(m4), wsum, &total);
+  block_prefix_sum<TR_THREADS>(__popc(m4), wsum, &total);
   if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
-// One work-group: a[] (and b[], nullable) become their exclusive prefix sums; the totals go to the header's int32 slots.
-// `clear`: the other slots of the header are zeroed first (the first scan of a call).
-__global__ void __launch_bounds__(OL_SCAN_THREADS)
-outline_scan_kernel(int* __restrict__ a, int* __restrict__ b, int nblk, int* __restrict__ hdr, int slot_a, int slot_b, int clear) {
-  __shared__ int w[OL_SCAN_THREADS / INSAR_WAVE];
-  const int carry_a = block_scan_array<OL_SCAN_THREADS>(a, nblk, w);
-  const int carry_b = b ? block_scan_array<OL_SCAN_THREADS>(b, nblk, w) : 0;
-  if (threadIdx.x < (int)(sizeof(InsarRing) / 4)) {
-    const int t = threadIdx.x;
-    if (t == slot_a) hdr[t] = carry_a;
-    else if (b && t == slot_b) hdr[t] = carry_b;
-    else if (clear) hdr[t] = 0;
-  }
-}
-
-__global__ void __launch_bounds__(OL_THREADS)
+__global__ void __launch_bounds__(TR_THREADS)
 outline_offsets_kernel(const uint8_t* __restrict__ mask, int npix, int vec, const int* __restrict__ counts, int* __restrict__ off) {
-  __shared__ int wsum[OL_THREADS / INSAR_WAVE];
-  const int i = blockIdx.x * OL_NB + threadIdx.x * 4;
+  __shared__ int wsum[TR_THREADS / INSAR_WAVE];
+  const int i = blockIdx.x * TR_NB + threadIdx.x * 4;
   int m[4];
   quad_load_u8(mask, i, npix, vec && i < npix, 0, m);
   const int c = __popc(m[0]) + __popc(m[1]) + __popc(m[2]) + __popc(m[3]);
   int total;
-  int o = counts[blockIdx.x] + block_prefix_sum<OL_THREADS>(c, wsum, &total);
+  int o = counts[blockIdx.x] + block_prefix_sum<TR_THREADS>(c, wsum, &total);
   int out[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) { out[j] = o; o += __popc(m[j]); }
@@ -119,11 +109,11 @@ __device__ __forceinline__ int ol_label_at(const int* __restrict__ labels, int y
   return ((unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W) ? labels[y * W + x] : 0;
 }
 
-__global__ void __launch_bounds__(OL_THREADS)
+__global__ void __launch_bounds__(TR_THREADS)
 outline_link_kernel(const int* __restrict__ labels, const uint8_t* __restrict__ mask, const int* __restrict__ off, int H, int W,
                     int npix, int conn8, int cap, int* __restrict__ succ0, int* __restrict__ eid, uint8_t* __restrict__ turn,
                     int2* __restrict__ pair) {
-  const int p = blockIdx.x * OL_THREADS + threadIdx.x;           // one pixel per thread: neighbouring lanes, neighbouring edges
+  const int p = blockIdx.x * TR_THREADS + threadIdx.x;           // one pixel per thread: neighbouring lanes, neighbouring edges
   if (p >= npix) return;
   const int m = mask[p];
   if (!m) return;
@@ -156,9 +146,9 @@ outline_link_kernel(const int* __restrict__ labels, const uint8_t* __restrict__ 
 // ---------------------------------------------------------------------------------------------
 // lead / rank: the rounds are list_rank.h's; `cut` between them
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(OL_THREADS)
+__global__ void __launch_bounds__(TR_THREADS)
 outline_cut_kernel(const int2* __restrict__ in, const int* __restrict__ succ0, int* __restrict__ lead, int2* __restrict__ out, int n) {
-  const int k = blockIdx.x * OL_THREADS + threadIdx.x;
+  const int k = blockIdx.x * TR_THREADS + threadIdx.x;
   if (k >= n) return;
   const int m = in[k].y, s = succ0[k];
   lead[k] = m;
@@ -166,67 +156,13 @@ outline_cut_kernel(const int2* __restrict__ in, const int* __restrict__ succ0, i
 }
 
 // ---------------------------------------------------------------------------------------------
-// rings: count / scan / number
-// ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(OL_THREADS)
-outline_ring_count_kernel(const int* __restrict__ lead, const int2* __restrict__ dist, int n, int* __restrict__ rcnt,
-                          int* __restrict__ rlen) {
-  __shared__ int wsum[OL_THREADS / INSAR_WAVE];
-  const int k0 = blockIdx.x * OL_NB + threadIdx.x * 4;
-  int c = 0, l = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int k = k0 + j;
-    if (k < n && lead[k] == k) { ++c; l += dist[k].y + 1; }
-  }
-  int tc, tl;
-  block_prefix_sum<OL_THREADS>(c, wsum, &tc);
-  block_prefix_sum<OL_THREADS>(l, wsum, &tl);
-  if (threadIdx.x == 0) { rcnt[blockIdx.x] = tc; rlen[blockIdx.x] = tl; }
-}
-
-__global__ void __launch_bounds__(OL_THREADS)
-outline_ring_number_kernel(const int* __restrict__ lead, const int2* __restrict__ dist, const int* __restrict__ eid,
-                           const int* __restrict__ labels, int n, const int* __restrict__ rcnt, const int* __restrict__ rlen,
-                           int2* __restrict__ info, InsarRing* __restrict__ rings, int max_rings) {
-  __shared__ int wsum[OL_THREADS / INSAR_WAVE];
-  const int k0 = blockIdx.x * OL_NB + threadIdx.x * 4;
-  bool is[4];
-  int len[4], c = 0, l = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int k = k0 + j;
-    is[j] = k < n && lead[k] == k;
-    len[j] = is[j] ? dist[k].y + 1 : 0;
-    c += is[j]; l += len[j];
-  }
-  int tc, tl;
-  int r = rcnt[blockIdx.x] + block_prefix_sum<OL_THREADS>(c, wsum, &tc);
-  int st = rlen[blockIdx.x] + block_prefix_sum<OL_THREADS>(l, wsum, &tl);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (!is[j]) continue;
-    const int k = k0 + j;
-    info[k] = make_int2(r, st);
-    if (r < max_rings) {                                         // area2 0, start / count by `write`, an empty box
-      const int e = eid[k];
-      int4* t4 = reinterpret_cast<int4*>(rings + 1 + r);
-      t4[0] = make_int4(0, 0, labels[e >> 2], e);
-      t4[1] = make_int4(0, 0, len[j], INT_MAX);
-      t4[2] = make_int4(INT_MAX, 0, 0, 0);
-    }
-    ++r; st += len[j];
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
 // write: scatter / reduce / scan / compact
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(OL_THREADS)
+__global__ void __launch_bounds__(TR_THREADS)
 outline_scatter_kernel(const int* __restrict__ lead, const int2* __restrict__ dist, const int2* __restrict__ info,
                        const int* __restrict__ succ0, const int* __restrict__ eid, const uint8_t* __restrict__ turn, int n, int W,
                        int corners_only, int2* __restrict__ overt, int* __restrict__ ometa, uint8_t* __restrict__ ocorner) {
-  const int k = blockIdx.x * OL_THREADS + threadIdx.x;
+  const int k = blockIdx.x * TR_THREADS + threadIdx.x;
   if (k >= n) return;
   const int m = lead[k];
   const int2 ri = info[m];
@@ -240,11 +176,11 @@ outline_scatter_kernel(const int* __restrict__ lead, const int2* __restrict__ di
   if ((unsigned)ps < (unsigned)n) ocorner[ps] = corners_only ? turn[k] : (uint8_t)1;
 }
 
-__global__ void __launch_bounds__(OL_THREADS)
+__global__ void __launch_bounds__(TR_THREADS)
 outline_reduce_kernel(const int2* __restrict__ overt, const int* __restrict__ ometa, const uint8_t* __restrict__ ocorner, int n,
                       InsarRing* __restrict__ rings, int max_rings, int* __restrict__ ccnt) {
-  __shared__ int wsum[OL_THREADS / INSAR_WAVE];
-  const int i = blockIdx.x * OL_THREADS + threadIdx.x;
+  __shared__ int wsum[TR_THREADS / INSAR_WAVE];
+  const int i = blockIdx.x * TR_THREADS + threadIdx.x;
   int key = -1, vy = 0, vx = 0, flag = 0;
   long long a2 = 0;
   if (i < n) {
@@ -254,34 +190,22 @@ outline_reduce_kernel(const int2* __restrict__ overt, const int* __restrict__ om
     a2 = s == 0 ? -vy : s == 1 ? vx : s == 2 ? vy : -vx;         // x_i * y_{i+1} - x_{i+1} * y_i with the head one step along d(s)
   }
   const WaveRuns runs = wave_runs(key);
-  const long long ta = wave_run_reduce(runs, a2, WaveAdd());
   const int tc = wave_run_reduce(runs, flag, WaveAdd());
-  const int y0 = wave_run_reduce(runs, vy, WaveMin()), y1 = wave_run_reduce(runs, vy + 1, WaveMax());
-  const int x0 = wave_run_reduce(runs, vx, WaveMin()), x1 = wave_run_reduce(runs, vx + 1, WaveMax());
-  if (runs.head && key >= 0 && key < max_rings) {
-    InsarRing* r = rings + 1 + key;
-    atomicAdd(reinterpret_cast<unsigned long long*>(&r->area2), (unsigned long long)ta);
-    atomicAdd(&r->count, tc);
-    // the box only tightens: a stale read can cost a redundant atomic, never lose an update
-    if (y0 < __hip_atomic_load(&r->y0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&r->y0, y0);
-    if (x0 < __hip_atomic_load(&r->x0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&r->x0, x0);
-    if (y1 > __hip_atomic_load(&r->y1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&r->y1, y1);
-    if (x1 > __hip_atomic_load(&r->x1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&r->x1, x1);
-  }
+  if (trace_reduce(runs, reinterpret_cast<TraceRecord*>(rings + 1), key, max_rings, a2, vy, vx)) atomicAdd(&rings[1 + key].count, tc);
   int total;
-  block_prefix_sum<OL_THREADS>(flag, wsum, &total);
+  block_prefix_sum<TR_THREADS>(flag, wsum, &total);
   if (threadIdx.x == 0) ccnt[blockIdx.x] = total;
 }
 
-__global__ void __launch_bounds__(OL_THREADS)
+__global__ void __launch_bounds__(TR_THREADS)
 outline_compact_kernel(const int2* __restrict__ overt, const int* __restrict__ ometa, const uint8_t* __restrict__ ocorner, int n,
                        const int* __restrict__ ccnt, InsarRing* __restrict__ rings, int max_rings, int2* __restrict__ vertices,
                        int max_vertices) {
-  __shared__ int wsum[OL_THREADS / INSAR_WAVE];
-  const int i = blockIdx.x * OL_THREADS + threadIdx.x;
+  __shared__ int wsum[TR_THREADS / INSAR_WAVE];
+  const int i = blockIdx.x * TR_THREADS + threadIdx.x;
   const int flag = i < n ? ocorner[i] : 0;
   int total;
-  const int o = ccnt[blockIdx.x] + block_prefix_sum<OL_THREADS>(flag, wsum, &total);
+  const int o = ccnt[blockIdx.x] + block_prefix_sum<TR_THREADS>(flag, wsum, &total);
   if (i >= n) return;
   const int key = ometa[i] >> 2;
   if ((i == 0 || (ometa[i - 1] >> 2) != key) && key < max_rings) rings[1 + key].start = o;
@@ -300,12 +224,12 @@ static int outline_layout(const char* who, int32_t H, int32_t W, int32_t max_edg
   if (H < 1 || W < 1) INSAR_FAIL(INSAR_E_SHAPE, "%s: empty scene %d x %d", who, H, W);
   const int64_t npix = (int64_t)H * W;
   if (npix >= OL_MAX_PIX) INSAR_FAIL(INSAR_E_SHAPE, "%s: scene %d x %d has 2^29 pixels or more", who, H, W);
-  if (max_edges < 1 || max_edges > OL_MAX_EDGES) INSAR_FAIL(INSAR_E_SHAPE, "%s: max_edges %d outside 1 .. 2^30", who, max_edges);
+  if (int rc = trace_check_capacity(who, "max_edges", max_edges)) return rc;
   L->npix = (int)npix;
-  L->nblk = (int)((npix + OL_NB - 1) / OL_NB);
+  L->nblk = (int)((npix + TR_NB - 1) / TR_NB);
   L->cap = max_edges;
-  L->eblk = (max_edges + OL_NB - 1) / OL_NB;
-  L->cblk = (max_edges + OL_THREADS - 1) / OL_THREADS;
+  L->eblk = (max_edges + TR_NB - 1) / TR_NB;
+  L->cblk = (max_edges + TR_THREADS - 1) / TR_THREADS;
   ScratchTake take;
   const int64_t cap = max_edges;
   L->mask = take(npix);        L->off = take(npix * 4);    L->counts = take((int64_t)L->nblk * 4);
@@ -316,18 +240,8 @@ static int outline_layout(const char* who, int32_t H, int32_t W, int32_t max_edg
   L->bytes = take.at;
   return INSAR_OK;
 }
-static int outline_check_buf(const char* who, const void* p, const char* what) {
-  if (!p) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer", who);
-  if (!insar_aligned16(p)) INSAR_FAIL(INSAR_E_ALIGN, "%s: %s not 16-byte aligned", who, what);
-  return INSAR_OK;
-}
-static int outline_check_rings(const char* who, const void* table, int32_t max_rings) {
-  if (max_rings < 1 || max_rings > OL_MAX_EDGES) INSAR_FAIL(INSAR_E_SHAPE, "%s: max_rings %d outside 1 .. 2^30", who, max_rings);
-  return outline_check_buf(who, table, "table");
-}
 static int outline_check_count(const char* who, int32_t n_edges, const OlLayout& L) {
-  if (n_edges < 0 || n_edges > L.cap) INSAR_FAIL(INSAR_E_SHAPE, "%s: n_edges %d outside 0 .. max_edges=%d", who, n_edges, L.cap);
-  return INSAR_OK;
+  return trace_check_count(who, "n_edges", n_edges, "max_edges", L.cap);
 }
 
 extern "C" int insar_outline_scratch_bytes(int32_t H, int32_t W, int32_t max_rings, int32_t max_edges, int64_t* scratch_bytes,
@@ -336,7 +250,7 @@ extern "C" int insar_outline_scratch_bytes(int32_t H, int32_t W, int32_t max_rin
   if (!scratch_bytes || !table_bytes) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer", who);
   OlLayout L;
   if (int rc = outline_layout(who, H, W, max_edges, &L)) return rc;
-  if (max_rings < 1 || max_rings > OL_MAX_EDGES) INSAR_FAIL(INSAR_E_SHAPE, "%s: max_rings %d outside 1 .. 2^30", who, max_rings);
+  if (int rc = trace_check_capacity(who, "max_rings", max_rings)) return rc;
   *scratch_bytes = L.bytes;
   *table_bytes = (int64_t)sizeof(InsarRing) * ((int64_t)max_rings + 1);
   return INSAR_OK;
@@ -353,39 +267,36 @@ extern "C" int insar_outline_edges(const int32_t* labels, int32_t H, int32_t W, 
   OlLayout L;
   if (int rc = outline_layout(who, H, W, max_edges, &L)) return rc;
   if (connectivity != 4 && connectivity != 8) INSAR_FAIL(INSAR_E_ARG, "%s: connectivity %d (4 or 8)", who, connectivity);
-  if (int rc = outline_check_buf(who, scratch, "scratch")) return rc;
-  if (int rc = outline_check_buf(who, table, "table")) return rc;
+  if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
+  if (int rc = scene_check_buffer(who, "table", table)) return rc;
   if (((uintptr_t)labels) & 3u) INSAR_FAIL(INSAR_E_ALIGN, "%s: labels not 4-byte aligned", who);
   hipStream_t s = (hipStream_t)stream;
   const int vec = L.npix % 4 == 0;
   const int lvec = vec && insar_aligned16(labels);
   uint8_t* mask = scratch_at<uint8_t>(scratch, L.mask);
   int *off = scratch_at<int>(scratch, L.off), *counts = scratch_at<int>(scratch, L.counts);
-  hipLaunchKernelGGL(outline_mark_kernel, dim3((unsigned)L.nblk), dim3(OL_THREADS), 0, s, labels, H, W, L.npix, lvec, mask, counts);
+  hipLaunchKernelGGL(outline_mark_kernel, dim3((unsigned)L.nblk), dim3(TR_THREADS), 0, s, labels, H, W, L.npix, lvec, mask, counts);
   INSAR_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(outline_scan_kernel, dim3(1), dim3(OL_SCAN_THREADS), 0, s, counts, (int*)nullptr, L.nblk, (int*)table,
-                     OL_HDR_EDGES, -1, 1);
+  hipLaunchKernelGGL(trace_scan_kernel<OlTool>, dim3(1), dim3(TR_SCAN_THREADS), 0, s, counts, (int*)nullptr, L.nblk, (int*)table,
+                     OL_HDR_EDGES, 1);
   INSAR_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(outline_offsets_kernel, dim3((unsigned)L.nblk), dim3(OL_THREADS), 0, s, mask, L.npix, vec, counts, off);
+  hipLaunchKernelGGL(outline_offsets_kernel, dim3((unsigned)L.nblk), dim3(TR_THREADS), 0, s, mask, L.npix, vec, counts, off);
   INSAR_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(outline_link_kernel, dim3(scene_blocks(L.npix, OL_THREADS)), dim3(OL_THREADS), 0, s, labels, mask, off, H, W,
+  hipLaunchKernelGGL(outline_link_kernel, dim3(scene_blocks(L.npix, TR_THREADS)), dim3(TR_THREADS), 0, s, labels, mask, off, H, W,
                      L.npix, connectivity == 8, L.cap, scratch_at<int>(scratch, L.succ0), scratch_at<int>(scratch, L.eid),
                      scratch_at<uint8_t>(scratch, L.turn), scratch_at<int2>(scratch, L.p0));
   INSAR_CHECK_LAUNCH(who);
   return INSAR_OK;
 }
 
-// The pair buffers: `link` fills p0, `lead` runs from there, `cut` reads its result and writes the other buffer, `rank` goes on from
-// there: the final distances are in p1 whatever L is, and p0 is free for `rings` (list_rank.h).
 extern "C" int insar_outline_lead(int32_t H, int32_t W, int32_t n_edges, int32_t max_edges, void* scratch, void* stream) {
   const char* who = "insar_outline_lead";
   OlLayout L;
   if (int rc = outline_layout(who, H, W, max_edges, &L)) return rc;
   if (int rc = outline_check_count(who, n_edges, L)) return rc;
-  if (int rc = outline_check_buf(who, scratch, "scratch")) return rc;
+  if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   if (n_edges == 0) return INSAR_OK;
-  int2* const p[2] = {scratch_at<int2>(scratch, L.p0), scratch_at<int2>(scratch, L.p1)};
-  return list_lead<OL_THREADS>(p, 0, n_edges, (hipStream_t)stream, who);
+  return trace_lead(scratch_at<int2>(scratch, L.p0), scratch_at<int2>(scratch, L.p1), n_edges, (hipStream_t)stream, who);
 }
 
 extern "C" int insar_outline_rank(int32_t H, int32_t W, int32_t n_edges, int32_t max_edges, void* scratch, void* stream) {
@@ -393,15 +304,14 @@ extern "C" int insar_outline_rank(int32_t H, int32_t W, int32_t n_edges, int32_t
   OlLayout L;
   if (int rc = outline_layout(who, H, W, max_edges, &L)) return rc;
   if (int rc = outline_check_count(who, n_edges, L)) return rc;
-  if (int rc = outline_check_buf(who, scratch, "scratch")) return rc;
+  if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   if (n_edges == 0) return INSAR_OK;
-  int2* const p[2] = {scratch_at<int2>(scratch, L.p0), scratch_at<int2>(scratch, L.p1)};
-  const int led = list_rounds(n_edges) & 1;                      // where `lead` ended
-  hipLaunchKernelGGL(outline_cut_kernel, dim3(scene_blocks(n_edges, OL_THREADS)), dim3(OL_THREADS), 0, (hipStream_t)stream,
-                     (const int2*)p[led], (const int*)scratch_at<int>(scratch, L.succ0), scratch_at<int>(scratch, L.lead), p[led ^ 1],
-                     n_edges);
-  INSAR_CHECK_LAUNCH(who);
-  return list_rank<OL_THREADS>(p, led ^ 1, n_edges, (hipStream_t)stream, who);
+  hipStream_t s = (hipStream_t)stream;
+  auto cut = [&](const int2* in, int2* out) {
+    hipLaunchKernelGGL(outline_cut_kernel, dim3(scene_blocks(n_edges, TR_THREADS)), dim3(TR_THREADS), 0, s, in,
+                       (const int*)scratch_at<int>(scratch, L.succ0), scratch_at<int>(scratch, L.lead), out, n_edges);
+  };
+  return trace_cut_and_rank(cut, scratch_at<int2>(scratch, L.p0), scratch_at<int2>(scratch, L.p1), n_edges, s, who);
 }
 
 extern "C" int insar_outline_rings(const int32_t* labels, int32_t H, int32_t W, int32_t n_edges, int32_t max_rings,
@@ -411,27 +321,12 @@ extern "C" int insar_outline_rings(const int32_t* labels, int32_t H, int32_t W, 
   OlLayout L;
   if (int rc = outline_layout(who, H, W, max_edges, &L)) return rc;
   if (int rc = outline_check_count(who, n_edges, L)) return rc;
-  if (int rc = outline_check_rings(who, table, max_rings)) return rc;
-  if (int rc = outline_check_buf(who, scratch, "scratch")) return rc;
+  if (int rc = trace_check_table(who, "max_rings", max_rings, table)) return rc;
+  if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   if (((uintptr_t)labels) & 3u) INSAR_FAIL(INSAR_E_ALIGN, "%s: labels not 4-byte aligned", who);
-  hipStream_t s = (hipStream_t)stream;
-  const int nblk = (int)scene_blocks(n_edges, OL_NB);
-  int *lead = scratch_at<int>(scratch, L.lead), *rcnt = scratch_at<int>(scratch, L.rcnt), *rlen = scratch_at<int>(scratch, L.rlen);
-  const int2* dist = scratch_at<int2>(scratch, L.p1);
-  if (nblk > 0) {
-    hipLaunchKernelGGL(outline_ring_count_kernel, dim3((unsigned)nblk), dim3(OL_THREADS), 0, s, (const int*)lead, dist, n_edges,
-                       rcnt, rlen);
-    INSAR_CHECK_LAUNCH(who);
-  }
-  hipLaunchKernelGGL(outline_scan_kernel, dim3(1), dim3(OL_SCAN_THREADS), 0, s, rcnt, rlen, nblk, (int*)table, OL_HDR_RINGS, -1, 0);
-  INSAR_CHECK_LAUNCH(who);
-  if (nblk > 0) {
-    hipLaunchKernelGGL(outline_ring_number_kernel, dim3((unsigned)nblk), dim3(OL_THREADS), 0, s, (const int*)lead, dist,
-                       (const int*)scratch_at<int>(scratch, L.eid), labels, n_edges, (const int*)rcnt, (const int*)rlen,
-                       scratch_at<int2>(scratch, L.p0), (InsarRing*)table, max_rings);
-    INSAR_CHECK_LAUNCH(who);
-  }
-  return INSAR_OK;
+  const OlTool tool = {scratch_at<int>(scratch, L.lead), scratch_at<int>(scratch, L.eid), labels, (InsarRing*)table};
+  return trace_number(tool, scratch_at<int2>(scratch, L.p1), n_edges, scratch_at<int>(scratch, L.rcnt), scratch_at<int>(scratch, L.rlen),
+                      scratch_at<int2>(scratch, L.p0), table, OL_HDR_RINGS, max_rings, (hipStream_t)stream, who);
 }
 
 extern "C" int insar_outline_write(int32_t H, int32_t W, int32_t n_edges, int32_t corners_only, int32_t max_rings,
@@ -441,31 +336,31 @@ extern "C" int insar_outline_write(int32_t H, int32_t W, int32_t n_edges, int32_
   OlLayout L;
   if (int rc = outline_layout(who, H, W, max_edges, &L)) return rc;
   if (int rc = outline_check_count(who, n_edges, L)) return rc;
-  if (int rc = outline_check_rings(who, table, max_rings)) return rc;
+  if (int rc = trace_check_table(who, "max_rings", max_rings, table)) return rc;
   if (max_vertices < 1) INSAR_FAIL(INSAR_E_SHAPE, "%s: max_vertices %d < 1", who, max_vertices);
   if (!vertices) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer", who);
   if (((uintptr_t)vertices) & 7u) INSAR_FAIL(INSAR_E_ALIGN, "%s: vertices not 8-byte aligned", who);
-  if (int rc = outline_check_buf(who, scratch, "scratch")) return rc;
+  if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const int nblk = (int)scene_blocks(n_edges, OL_THREADS);
+  const int nblk = (int)scene_blocks(n_edges, TR_THREADS);
   int2* overt = scratch_at<int2>(scratch, L.overt);
   int *ometa = scratch_at<int>(scratch, L.ometa), *ccnt = scratch_at<int>(scratch, L.ccnt);
   uint8_t* ocorner = scratch_at<uint8_t>(scratch, L.ocorner);
   if (nblk > 0) {
-    hipLaunchKernelGGL(outline_scatter_kernel, dim3((unsigned)nblk), dim3(OL_THREADS), 0, s, (const int*)scratch_at<int>(scratch, L.lead),
+    hipLaunchKernelGGL(outline_scatter_kernel, dim3((unsigned)nblk), dim3(TR_THREADS), 0, s, (const int*)scratch_at<int>(scratch, L.lead),
                        (const int2*)scratch_at<int2>(scratch, L.p1), (const int2*)scratch_at<int2>(scratch, L.p0),
                        (const int*)scratch_at<int>(scratch, L.succ0), (const int*)scratch_at<int>(scratch, L.eid),
                        (const uint8_t*)scratch_at<uint8_t>(scratch, L.turn), n_edges, W, corners_only != 0, overt, ometa, ocorner);
     INSAR_CHECK_LAUNCH(who);
-    hipLaunchKernelGGL(outline_reduce_kernel, dim3((unsigned)nblk), dim3(OL_THREADS), 0, s, (const int2*)overt, (const int*)ometa,
+    hipLaunchKernelGGL(outline_reduce_kernel, dim3((unsigned)nblk), dim3(TR_THREADS), 0, s, (const int2*)overt, (const int*)ometa,
                        (const uint8_t*)ocorner, n_edges, (InsarRing*)table, max_rings, ccnt);
     INSAR_CHECK_LAUNCH(who);
   }
-  hipLaunchKernelGGL(outline_scan_kernel, dim3(1), dim3(OL_SCAN_THREADS), 0, s, ccnt, (int*)nullptr, nblk, (int*)table,
-                     OL_HDR_VERTS, -1, 0);
+  hipLaunchKernelGGL(trace_scan_kernel<OlTool>, dim3(1), dim3(TR_SCAN_THREADS), 0, s, ccnt, (int*)nullptr, nblk, (int*)table,
+                     OL_HDR_VERTS, 0);
   INSAR_CHECK_LAUNCH(who);
   if (nblk > 0) {
-    hipLaunchKernelGGL(outline_compact_kernel, dim3((unsigned)nblk), dim3(OL_THREADS), 0, s, (const int2*)overt, (const int*)ometa,
+    hipLaunchKernelGGL(outline_compact_kernel, dim3((unsigned)nblk), dim3(TR_THREADS), 0, s, (const int2*)overt, (const int*)ometa,
                        (const uint8_t*)ocorner, n_edges, (const int*)ccnt, (InsarRing*)table, max_rings,
                        reinterpret_cast<int2*>(vertices), max_vertices);
     INSAR_CHECK_LAUNCH(who);

@@ -264,6 +264,17 @@ def test_isolated_pixels_fill_more_than_one_scan_pass(dev):
     _compare(out, ref, "isolated pixels")
 
 
+@pytest.mark.parametrize("W,E", [(33, 1024), (35, 1088)])
+def test_rings_end_on_the_numbering_block_boundary(dev, W, E):
+    """A float raster that is 1 at every odd (y, x) of 33 x W and 0 elsewhere, at level 0.5: closed lines of four crossings.
+    33 x 33 gives E = 1024, exactly one numbering block of the count / number kernels, and the last leader's line ends on its
+    last slot; 33 x 35 gives 1088 and runs into a second block."""
+    m = np.zeros((33, W), dtype=np.float32)
+    m[1::2, 1::2] = 1.0
+    ref, _ = _check(dev, f"odd pixels 33x{W}", m, [0.5])
+    assert ref["n_vertices"] == E and ref["n_lines"] == E // 4 and ref["lines"]["closed"].all() and (ref["lines"]["count"] == 4).all()
+
+
 def test_vector_and_scalar_paths_agree(dev):
     """33 x 67 is off the 4-pixel vector width; 32 x 68 is on it, and a view one element into a buffer is misaligned."""
     import insar_unet_ca_amd as iu

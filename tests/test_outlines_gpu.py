@@ -160,6 +160,18 @@ def test_isolated_pixels_fill_more_than_one_scan_pass(dev, H, W):
     _compare(out, ref, f"isolated pixels {H} x {W}")
 
 
+@pytest.mark.parametrize("W,E", [(32, 1024), (34, 1088)])
+def test_rings_end_on_the_numbering_block_boundary(dev, W, E):
+    """A distinct label at every even (y, x) of a 32 x W map: one-pixel rings of four edges. 32 x 32 gives E = 1024, exactly one
+    numbering block of the count / number kernels, and the last leader's ring ends on its last slot; 32 x 34 gives 1088 and runs
+    into a second block."""
+    labels = np.zeros((32, W), dtype=np.int32)
+    labels[0::2, 0::2] = 1 + np.arange(16 * (W // 2)).reshape(16, W // 2)
+    ref = _oracle(f"even pixels 32x{W}", labels, 4, True)
+    assert ref["edge_count"] == E and ref["ring_count"] == E // 4 and (ref["rings"]["edges"] == 4).all()
+    _check_all(dev, f"even pixels 32x{W}", labels)
+
+
 # ---- maps labelled by label_regions -------------------------------------------------------------------------------------------------
 SPECKLE = {"96x160 at 50 %": (96, 160, 0.5, 11), "70x130 at 30 %": (70, 130, 0.3, 12), "70x130 at 70 %": (70, 130, 0.7, 13)}
 
