@@ -148,6 +148,33 @@ def simplify_rounds(prefix: str, scratch, v: torch.Tensor, n_records: int, nbyte
         return read_back(scratch.host, scratch.table, nbytes), out_v, out_k
 
 
+# ---- what sieve.py and split.py share: pieces that merge in synchronous rounds until a round merges nothing ----------------------
+MERGE_ROUNDS_PER_READ = 4                # the host looks at the rounds' counters once per this many rounds
+# int32 control words of the tool's own, then one merge counter per round: SV_CTRL_WORDS of csrc/sieve.hip and SP_CTRL_WORDS of
+# csrc/split.hip, which lay their words out separately, must both equal it
+MERGE_CTRL_WORDS = 8
+
+
+def merge_rounds(run, ctrl_host: torch.Tensor, ctrl: torch.Tensor, max_rounds: int, first_read):
+    """Batches of MERGE_ROUNDS_PER_READ rounds, `run(first_round, n_rounds)` launching a batch, with ONE read-back of the
+    control words `ctrl` (into the pinned `ctrl_host`) behind each, until a round's counter reads 0 or `max_rounds` rounds
+    have run. `first_read(words)` sees the first read-back: the tool's capacity checks. Returns (rounds that merged
+    something, whether an idle round was reached, the int32 control words as last read). Call it inside the caller's
+    `torch.cuda.device(...)` block."""
+    done, rounds, converged = 0, max_rounds, False
+    while done < max_rounds and not converged:
+        n = min(MERGE_ROUNDS_PER_READ, max_rounds - done)
+        run(done, n)
+        words = read_back(ctrl_host, ctrl).view(np.int32)
+        if done == 0:
+            first_read(words)
+        done += n
+        idle = np.flatnonzero(words[MERGE_CTRL_WORDS:MERGE_CTRL_WORDS + done] == 0)
+        if len(idle):                                             # rounds after the first idle one changed nothing
+            rounds, converged = int(idle[0]), True
+    return rounds, converged, words
+
+
 class Scratch:
     """The buffers of one tool for one key (a scene size, capacities) on one device. A subclass names its key in KEY (the
     names become attributes), says where `device` stands among its constructor's arguments, and hands its byte counts to

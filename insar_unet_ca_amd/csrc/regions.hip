@@ -132,10 +132,9 @@ regions_tile_kernel(const uint8_t* __restrict__ mask, const float* __restrict__ 
 // first row of every tile row but the top one (neighbours up, up-left, up-right), then the pixels either side of every
 // vertical tile border (left; up-left and up-right where the row above belongs to the same tile row).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int rg_ag_load(int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ int rg_ag_find(int* P, int a) {
   for (;;) {
-    const int p = rg_ag_load(P + a);
+    const int p = agent_load(P + a);
     if (p >= a) return a;
     a = p;
   }
@@ -155,7 +154,7 @@ __device__ __forceinline__ void rg_ag_union(int* P, int a, int b) {
 // was applied by `tiles`)
 __device__ __forceinline__ void rg_try_union(const uint8_t* __restrict__ mask, int* P, int a, int b) {
   if (mask[a] != mask[b]) return;
-  if (rg_ag_load(P + a) < 0 || rg_ag_load(P + b) < 0) return;
+  if (agent_load(P + a) < 0 || agent_load(P + b) < 0) return;
   rg_ag_union(P, a, b);
 }
 

@@ -1,8 +1,10 @@
 // What the scene tools (scene.hip, scene_valid.hip, regions.hip, augment.hip, overlap.hip, distance.hip, crops.hip, outline.hip,
 // skeleton.hip, raster.hip, zonal.hip, simplify.hip, contour_simplify.hip, split.hip, warp.hip, stack.hip, sieve.hip,
 // hysteresis.hip, contour.hip, reconstruct.hip), the focal loss of focal.hip and the dropout kernel of deeplab.hip share: the counter hash, the guarded four-element access,
-// the wave primitives (runs of equal keys, scan, max), the image / label quads of the two gather kernels and the host side's
-// small change (scratch layout, grids, pointer checks). Each file's kernels, launch geometry and argument checks are its own.
+// the wave primitives (runs of equal keys, scan, max), the relaxed agent-scope word accessors and the one-add-per-wave counters,
+// the image / label quads of the two gather kernels and the host side's small change (scratch layout, grids, pointer checks).
+// Each file's kernels, launch geometry and argument checks are its own. pair_table.h builds the pair table of overlap.hip,
+// sieve.hip and split.hip on top of this header.
 #pragma once
 #include "common.h"
 
@@ -121,6 +123,22 @@ __device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
     v = u > v ? u : v;
   }
   return v;
+}
+
+// a word that work-groups of one launch share (they may sit on different XCDs): relaxed, agent scope
+__device__ __forceinline__ int agent_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void agent_store(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// one add per wave on such a word: of the lanes that raise `flag`, or of the lanes' counts `c`
+__device__ __forceinline__ void wave_count(int* word, bool flag) {
+  const unsigned long long b = __ballot(flag);
+  if (b && (int)__lane_id() == __ffsll((long long)b) - 1)
+    __hip_atomic_fetch_add(word, __popcll(b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void wave_tally(int* word, int c) {
+  if (__ballot(c != 0) == 0) return;
+#pragma unroll
+  for (int o = INSAR_WAVE / 2; o > 0; o >>= 1) c += __shfl_xor(c, o, INSAR_WAVE);
+  if ((int)__lane_id() == 0) __hip_atomic_fetch_add(word, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ---- image and label quads of the gather kernels (insar_scene_gather, insar_crops_gather) ---------------------------------------

@@ -18,41 +18,23 @@
 // `compress` follows nxt, along which the key (area, -id) strictly rises except inside a mutual pair, which `decide` has
 // resolved: it ends. Visibility: the pair table, the overflow word, the best words, the round counters and (in compress) the
 // areas are shared between work-groups of one launch, so every access to them in those launches is an agent-scope atomic.
-// Aggregation before atomics: a thread folds those of its eight neighbour pairs that share a key, the lanes of a wave fold over
-// runs of equal keys, and only the first lane of a run probes the table (overlap_count_kernel's pattern). A wave that sees no
-// border at all leaves after one ballot.
+// The pair table, its clear and compact launches and the aggregation of a thread's eight neighbour pairs before the atomics
+// (pair_fold_insert: a wave that sees no border at all leaves after one ballot) are pair_table.h's.
 // Reproducibility: integer sums and maxima commute; which slot a pair lands in, and the order of the pair list, depend on
 // arrival order, but every result taken from them is a sum or a maximum under a total order.
-#include "scene_common.h"
+#include "pair_table.h"
 #include <limits.h>
 
 #define SV_THREADS 256
-#define SV_MAX_PAIRS ((int64_t)1 << 24)
 #define SV_MAX_ROUNDS 4096
 #define SV_MAX_REGIONS (1 << 30)
 #define SV_CTRL_WORDS 8                   // n_pairs, overflow, regions, bad classes, changed pixels, absorbed, 2 spare; then one per round
 
-struct SvSlot { unsigned long long key; long long val; };
 struct SvPair { int a, b; long long edges; };
-static_assert(sizeof(SvSlot) == 16 && sizeof(SvPair) == 16, "16-byte slots and pairs");
+static_assert(sizeof(SvPair) == 16, "a pair is one record of pair_table_compact_kernel");
 static_assert(sizeof(InsarRegion) == 64, "InsarRegion is four 16-byte stores");
 
 enum { SV_NPAIRS = 0, SV_OVERFLOW = 1, SV_REGIONS = 2, SV_BADCLS = 3, SV_CHANGED = 4, SV_ABSORBED = 5 };
-
-__device__ __forceinline__ int sv_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// one add per wave for a per-lane flag
-__device__ __forceinline__ void sv_count(int* word, bool flag) {
-  const unsigned long long b = __ballot(flag);
-  if (b && (int)__lane_id() == __ffsll((long long)b) - 1)
-    __hip_atomic_fetch_add(word, __popcll(b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// one add per wave for a per-lane count
-__device__ __forceinline__ void sv_add(int* word, int c) {
-  if (__ballot(c != 0) == 0) return;
-#pragma unroll
-  for (int o = INSAR_WAVE / 2; o > 0; o >>= 1) c += __shfl_xor(c, o, INSAR_WAVE);
-  if ((int)__lane_id() == 0) __hip_atomic_fetch_add(word, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // ---------------------------------------------------------------------------------------------
 // remap
@@ -73,13 +55,7 @@ sieve_remap_kernel(const uint8_t* __restrict__ mask, int64_t npix, int vec, int 
       if (m[j] == void_value) m[j] = 0;
       else if (void_value < 0 || m[j] < void_value) m[j] = (m[j] + 1) & 255;      // class 255 without a void value: no code left
     }
-    if (vec) {
-      *reinterpret_cast<uint32_t*>(remap + i) = (uint32_t)m[0] | ((uint32_t)m[1] << 8) | ((uint32_t)m[2] << 16) | ((uint32_t)m[3] << 24);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (i + j < npix) remap[i + j] = (uint8_t)m[j];
-    }
+    quad_store_u8(remap, i, npix, vec, m);
   }
 }
 
@@ -89,37 +65,13 @@ __global__ void __launch_bounds__(SV_THREADS)
 sieve_badcls_kernel(const uint8_t* __restrict__ mask, int64_t npix, int* ctrl) {
   for (int64_t i0 = blockIdx.x * (int64_t)SV_THREADS; i0 < npix; i0 += (int64_t)gridDim.x * SV_THREADS) {
     const int64_t i = i0 + threadIdx.x;
-    sv_count(ctrl + SV_BADCLS, i < npix && mask[i] == 255);
+    wave_count(ctrl + SV_BADCLS, i < npix && mask[i] == 255);
   }
 }
 
 // ---------------------------------------------------------------------------------------------
 // pairs
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(SV_THREADS)
-sieve_clear_kernel(int4* __restrict__ slots, int64_t slot_chunks, int4* __restrict__ hdr) {
-  const int4 z = make_int4(0, 0, 0, 0);
-  for (int64_t i = blockIdx.x * (int64_t)SV_THREADS + threadIdx.x; i < slot_chunks; i += (int64_t)gridDim.x * SV_THREADS) slots[i] = z;
-  if (blockIdx.x == 0 && threadIdx.x == 0) hdr[0] = z;
-}
-
-// table[key] += n: at most `mask + 1` probe steps, every access an agent-scope atomic (ov_insert's scheme)
-__device__ __forceinline__ void sv_insert(int* hdr, SvSlot* slots, unsigned int mask, unsigned long long key, int n) {
-  unsigned int s = (unsigned int)insar_mix64(key) & mask;
-  for (unsigned int step = 0; step <= mask; ++step) {
-    unsigned long long cur = __hip_atomic_load(&slots[s].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == 0ull)
-      __hip_atomic_compare_exchange_strong(&slots[s].key, &cur, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == 0ull || cur == key) {
-      __hip_atomic_fetch_add(&slots[s].val, (long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return;
-    }
-    s = (s + 1u) & mask;
-    if ((step & 63u) == 63u && sv_ld(hdr + SV_OVERFLOW)) return;
-  }
-  __hip_atomic_fetch_or(hdr + SV_OVERFLOW, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // (min, max) of two different region labels in 1..max_label, else 0 (the empty slot: max >= 2 keeps a key off it)
 __device__ __forceinline__ unsigned long long sv_key(int a, int b, int max_label) {
   if (a == b || a <= 0 || b <= 0 || a > max_label || b > max_label) return 0ull;
@@ -128,7 +80,7 @@ __device__ __forceinline__ unsigned long long sv_key(int a, int b, int max_label
 
 template <bool VEC>
 __global__ void __launch_bounds__(SV_THREADS)
-sieve_pairs_kernel(const int* __restrict__ labels, int H, int W, int max_label, int* hdr, SvSlot* slots, unsigned int mask) {
+sieve_pairs_kernel(const int* __restrict__ labels, int H, int W, int max_label, int* hdr, PairSlot* slots, unsigned int mask) {
   const int64_t npix = (int64_t)H * W, nquads = (npix + 3) >> 2;
   for (int64_t q0 = blockIdx.x * (int64_t)SV_THREADS; q0 < nquads; q0 += (int64_t)gridDim.x * SV_THREADS) {
     const int64_t q = q0 + threadIdx.x;                            // the loop bound is uniform over the block: shuffles below
@@ -159,51 +111,10 @@ sieve_pairs_kernel(const int* __restrict__ labels, int H, int W, int max_label, 
         }
       }
     }
-    const bool any = (k[0] | k[1] | k[2] | k[3] | k[4] | k[5] | k[6] | k[7]) != 0ull;
-    if (__ballot(any) == 0) continue;                              // no border under this wave: most waves leave here
     int c[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) c[j] = k[j] != 0ull;
-    if (any) {
-#pragma unroll
-      for (int j = 1; j < 8; ++j)
-#pragma unroll
-        for (int m = 0; m < j; ++m)
-          if (k[j] != 0ull && k[j] == k[m]) { c[m] += c[j]; k[j] = 0ull; }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (__ballot(k[j] != 0ull) == 0) continue;
-      const WaveRuns runs = wave_runs(k[j]);
-      const int n = wave_run_reduce(runs, c[j], WaveAdd());
-      if (runs.head && k[j] != 0ull) sv_insert(hdr, slots, mask, k[j], n);
-    }
-  }
-}
-
-// one slot per thread and pass; a work-group claims the positions of its non-empty slots with ONE add on the cursor
-__global__ void __launch_bounds__(SV_THREADS)
-sieve_compact_kernel(const SvSlot* __restrict__ slots, int64_t capacity, int64_t max_pairs, int* hdr, SvPair* __restrict__ pairs) {
-  __shared__ int wcount[SV_THREADS / INSAR_WAVE];
-  __shared__ int base_s;
-  const int lane = (int)__lane_id(), wave = threadIdx.x / INSAR_WAVE;
-  for (int64_t s0 = blockIdx.x * (int64_t)SV_THREADS; s0 < capacity; s0 += (int64_t)gridDim.x * SV_THREADS) {
-    const int64_t s = s0 + threadIdx.x;
-    int4 v = make_int4(0, 0, 0, 0);                                // {key lo = b, key hi = a, edges lo, edges hi}
-    if (s < capacity) v = *reinterpret_cast<const int4*>(slots + s);
-    const bool full = (v.x | v.y) != 0;
-    const unsigned long long b = __ballot(full);
-    if (lane == 0) wcount[wave] = __popcll(b);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const int n = wcount[0] + wcount[1] + wcount[2] + wcount[3];
-      base_s = n ? atomicAdd(hdr + SV_NPAIRS, n) : 0;              // <= capacity <= 2^25
-    }
-    __syncthreads();
-    int64_t pos = (int64_t)base_s + __popcll(b & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) pos += wcount[w];
-    if (full && pos < max_pairs) *reinterpret_cast<int4*>(pairs + pos) = make_int4(v.y, v.x, v.z, v.w);
-    __syncthreads();                                               // wcount and base_s are rewritten by the next pass
+    pair_fold_insert<8, WaveAdd>(hdr + SV_OVERFLOW, slots, mask, k, c);
   }
 }
 
@@ -275,7 +186,7 @@ sieve_decide_kernel(int* ctrl, int max_regions, const int* __restrict__ up, cons
         if (!stays) { nxt[r] = v; merged = true; }
       }
     }
-    sv_count(ctrl + SV_CTRL_WORDS + round, merged);
+    wave_count(ctrl + SV_CTRL_WORDS + round, merged);
   }
 }
 
@@ -304,7 +215,7 @@ sieve_apply_kernel(const int* __restrict__ labels, const uint8_t* __restrict__ m
   const int n = sv_region_count(ctrl, max_regions);
   for (int r0 = blockIdx.x * SV_THREADS; r0 <= n; r0 += gridDim.x * SV_THREADS) {
     const int r = r0 + threadIdx.x;
-    sv_count(ctrl + SV_ABSORBED, r >= 1 && r <= n && up[r] != r);
+    wave_count(ctrl + SV_ABSORBED, r >= 1 && r <= n && up[r] != r);
   }
   const int64_t nquads = (npix + 3) >> 2;
   for (int64_t q0 = blockIdx.x * (int64_t)SV_THREADS; q0 < nquads; q0 += (int64_t)gridDim.x * SV_THREADS) {
@@ -321,6 +232,9 @@ sieve_apply_kernel(const int* __restrict__ labels, const uint8_t* __restrict__ m
         else o[j] = l[j] > 0 && l[j] <= n ? cls[up[l[j]]] : m[j];
         diff += o[j] != m[j];                                      // past npix l, m and o are 0
       }
+      // The two stores stay packed by hand. As two quad_store_u8 calls the `changed` map gets a branch of its own: the kernel
+      // is 23 instructions longer and was measured at 30 us instead of 26 us on a 4096 x 4096 map of large regions
+      // (profiles/pair_table_refactor_ab.txt, part 3).
       if (vec) {
         *reinterpret_cast<uint32_t*>(out + i) = (uint32_t)o[0] | ((uint32_t)o[1] << 8) | ((uint32_t)o[2] << 16) | ((uint32_t)o[3] << 24);
         if (changed)
@@ -335,7 +249,7 @@ sieve_apply_kernel(const int* __restrict__ labels, const uint8_t* __restrict__ m
           }
       }
     }
-    sv_add(ctrl + SV_CHANGED, diff);
+    wave_tally(ctrl + SV_CHANGED, diff);
   }
 }
 
@@ -352,14 +266,10 @@ static int sieve_layout(const char* who, int32_t H, int32_t W, int32_t max_regio
   const int64_t npix = (int64_t)H * W;
   if (npix >= ((int64_t)1 << 31)) INSAR_FAIL(INSAR_E_SHAPE, "%s: scene %d x %d has 2^31 pixels or more", who, H, W);
   if (max_regions < 1 || max_regions > SV_MAX_REGIONS) INSAR_FAIL(INSAR_E_SHAPE, "%s: max_regions %d outside 1..%d", who, max_regions, SV_MAX_REGIONS);
-  if (max_pairs < 1 || max_pairs > SV_MAX_PAIRS)
-    INSAR_FAIL(INSAR_E_SHAPE, "%s: max_pairs %lld outside 1..%lld", who, (long long)max_pairs, (long long)SV_MAX_PAIRS);
+  if (int rc = pair_table_capacity(who, max_pairs, &L->cap)) return rc;
   if (max_rounds < 1 || max_rounds > SV_MAX_ROUNDS)
     INSAR_FAIL(INSAR_E_SHAPE, "%s: max_rounds %d outside 1..%d", who, max_rounds, SV_MAX_ROUNDS);
   L->npix = npix;
-  int64_t c = 2;
-  while (c < 2 * max_pairs) c <<= 1;
-  L->cap = c;
   L->ctrl_words = insar_align16((SV_CTRL_WORDS + (int64_t)max_rounds) * 4) / 4;
   L->regions = (int64_t)max_regions + 1;
   const int64_t seg = insar_align16(L->regions * 4);
@@ -372,7 +282,7 @@ static int sieve_layout(const char* who, int32_t H, int32_t W, int32_t max_regio
   L->off_hdr = L->off_best + 2 * seg;
   L->off_pairs = L->off_hdr + 16;
   L->off_slots = L->off_pairs + max_pairs * (int64_t)sizeof(SvPair);
-  L->bytes = L->off_slots + L->cap * (int64_t)sizeof(SvSlot);
+  L->bytes = L->off_slots + L->cap * (int64_t)sizeof(PairSlot);
   return INSAR_OK;
 }
 
@@ -420,18 +330,17 @@ extern "C" int insar_sieve_pairs(const int32_t* labels, int32_t H, int32_t W, in
   if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   hipStream_t s = (hipStream_t)stream;
   int* hdr = scratch_at<int>(scratch, L.off_hdr);
-  SvSlot* slots = scratch_at<SvSlot>(scratch, L.off_slots);
+  PairSlot* slots = scratch_at<PairSlot>(scratch, L.off_slots);
   const dim3 block(SV_THREADS), grid = scene_grid((L.npix + 3) / 4, SV_THREADS);
   const unsigned int mask = (unsigned int)(L.cap - 1);
-  hipLaunchKernelGGL(sieve_clear_kernel, scene_grid(L.cap, SV_THREADS), block, 0, s, (int4*)slots, L.cap, (int4*)hdr);
+  pair_table_clear(s, slots, L.cap, hdr, 1);
   INSAR_CHECK_LAUNCH(who);
   if (W % 4 == 0 && insar_aligned16(labels))
     hipLaunchKernelGGL(sieve_pairs_kernel<true>, grid, block, 0, s, (const int*)labels, H, W, max_label, hdr, slots, mask);
   else
     hipLaunchKernelGGL(sieve_pairs_kernel<false>, grid, block, 0, s, (const int*)labels, H, W, max_label, hdr, slots, mask);
   INSAR_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(sieve_compact_kernel, scene_grid(L.cap, SV_THREADS), block, 0, s, (const SvSlot*)slots, L.cap, max_pairs, hdr,
-                     scratch_at<SvPair>(scratch, L.off_pairs));
+  pair_table_compact(s, slots, L.cap, max_pairs, hdr + SV_NPAIRS, scratch_at<SvPair>(scratch, L.off_pairs));
   INSAR_CHECK_LAUNCH(who);
   return INSAR_OK;
 }

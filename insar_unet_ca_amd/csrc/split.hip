@@ -20,49 +20,32 @@
 // of its chain while other threads may still read it: either value leads to the same end (regions_flatten_kernel's argument).
 // Visibility: the saddle table, the best words, the control words and (in compress) `up` are shared between work-groups of
 // one launch, so every access to them in those launches is an agent-scope atomic.
-// Aggregation before atomics: a thread folds those of its four neighbour pairs that share a key, the lanes of a wave fold over
-// runs of equal keys, and only the first lane of a run touches memory (overlap_count_kernel's pattern).
+// The saddle table, its clear and compact launches and the aggregation of a thread's four neighbour pairs before the atomics
+// (pair_fold_insert) are pair_table.h's.
 // Reproducibility: max, min and integer sums commute; which slot a pair lands in, and the order of the edge list, depend on
 // arrival order, but every result taken from them is a maximum or minimum under a total order.
-#include "scene_common.h"
+#include "pair_table.h"
 #include "block_scan.h"
 #include <limits.h>
 
 #define SP_THREADS 256
 #define SP_NB 1024                        // pixels per numbering block (256 threads x 4 pixels)
 #define SP_SCAN_THREADS 1024
-#define SP_MAX_PAIRS ((int64_t)1 << 24)
 #define SP_MAX_ROUNDS 4096
 #define SP_CTRL_WORDS 8                   // n_pairs, overflow, bad_height, raw_basins, pieces, 3 spare; then one word per round
 #define SP_MAX_T (1 << 20)
 
-struct SpSlot { unsigned long long key; long long val; };
+// a record of pair_table_compact_kernel. pad, the high half of the slot's value, is 0: a value starts at 0 and only ever takes
+// the maximum with an int32, so it stays in 0..2^31-1
 struct SpEdge { int a, b, s, pad; };
-static_assert(sizeof(SpSlot) == 16 && sizeof(SpEdge) == 16, "16-byte slots and edges");
+static_assert(sizeof(SpEdge) == 16, "an edge is one record of pair_table_compact_kernel");
 static_assert(sizeof(InsarSplitRegion) == 80, "InsarSplitRegion is five 16-byte stores");
 
 enum { SP_NPAIRS = 0, SP_OVERFLOW = 1, SP_BADH = 2, SP_BASINS = 3, SP_PIECES = 4 };
 
-__device__ __forceinline__ int sp_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void sp_st(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// one add per wave for a per-lane flag
-__device__ __forceinline__ void sp_count(int* word, bool flag) {
-  const unsigned long long b = __ballot(flag);
-  if (b && (int)__lane_id() == __ffsll((long long)b) - 1)
-    __hip_atomic_fetch_add(word, __popcll(b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // ---------------------------------------------------------------------------------------------
 // basins
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(SP_THREADS)
-split_clear_kernel(int4* __restrict__ slots, int64_t slot_chunks, int4* __restrict__ ctrl, int ctrl_chunks) {
-  const int4 z = make_int4(0, 0, 0, 0);
-  for (int64_t i = blockIdx.x * (int64_t)SP_THREADS + threadIdx.x; i < slot_chunks; i += (int64_t)gridDim.x * SP_THREADS) slots[i] = z;
-  if (blockIdx.x == 0)
-    for (int i = threadIdx.x; i < ctrl_chunks; i += SP_THREADS) ctrl[i] = z;
-}
-
 __global__ void __launch_bounds__(SP_THREADS)
 split_ascent_kernel(const int* __restrict__ labels, const int* __restrict__ h, int H, int W, int* __restrict__ ptr, int* ctrl) {
   const int64_t npix = (int64_t)H * W;
@@ -92,7 +75,7 @@ split_ascent_kernel(const int* __restrict__ labels, const int* __restrict__ h, i
       }
       ptr[i] = best;
     }
-    sp_count(ctrl + SP_BADH, bad);
+    wave_count(ctrl + SP_BADH, bad);
   }
 }
 
@@ -106,27 +89,10 @@ split_resolve_kernel(int* ptr, int64_t npix) {
   }
 }
 
-// raise table[key] to v: at most `mask + 1` probe steps, every access an agent-scope atomic (ov_insert's scheme)
-__device__ __forceinline__ void sp_insert(int* ctrl, SpSlot* slots, unsigned int mask, unsigned long long key, int v) {
-  unsigned int s = (unsigned int)insar_mix64(key) & mask;
-  for (unsigned int step = 0; step <= mask; ++step) {
-    unsigned long long cur = __hip_atomic_load(&slots[s].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == 0ull)
-      __hip_atomic_compare_exchange_strong(&slots[s].key, &cur, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == 0ull || cur == key) {
-      __hip_atomic_fetch_max(&slots[s].val, (long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return;
-    }
-    s = (s + 1u) & mask;
-    if ((step & 63u) == 63u && sp_ld(ctrl + SP_OVERFLOW)) return;
-  }
-  __hip_atomic_fetch_or(ctrl + SP_OVERFLOW, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 __global__ void __launch_bounds__(SP_THREADS)
 split_saddles_kernel(const int* __restrict__ labels, const int* __restrict__ h, const int* __restrict__ basin, int H, int W,
                      int* __restrict__ up, int* __restrict__ nxt, int* __restrict__ bidx, unsigned long long* __restrict__ best,
-                     int* ctrl, SpSlot* slots, unsigned int mask) {
+                     int* ctrl, PairSlot* slots, unsigned int mask) {
   const int64_t npix = (int64_t)H * W;
   for (int64_t i0 = blockIdx.x * (int64_t)SP_THREADS; i0 < npix; i0 += (int64_t)gridDim.x * SP_THREADS) {
     const int64_t i = i0 + threadIdx.x;                            // the loop bound is uniform over the block: shuffles below
@@ -152,47 +118,10 @@ split_saddles_kernel(const int* __restrict__ labels, const int* __restrict__ h, 
           k[j] = ((unsigned long long)(uint32_t)lo << 32) | (unsigned long long)(uint32_t)hi2;
           v[j] = min(hi, h[q]);
         }
-#pragma unroll
-        for (int j = 1; j < 4; ++j)
-#pragma unroll
-          for (int m = 0; m < j; ++m)
-            if (k[j] != 0ull && k[j] == k[m]) { v[m] = max(v[m], v[j]); k[j] = 0ull; }
       }
     }
-    sp_count(ctrl + SP_BASINS, root);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (__ballot(k[j] != 0ull) == 0) continue;
-      const WaveRuns runs = wave_runs(k[j]);
-      const int top = wave_run_reduce(runs, v[j], WaveMax());
-      if (runs.head && k[j] != 0ull) sp_insert(ctrl, slots, mask, k[j], top);
-    }
-  }
-}
-
-// one slot per thread and pass; a work-group claims the positions of its non-empty slots with ONE add on the cursor
-__global__ void __launch_bounds__(SP_THREADS)
-split_compact_kernel(const SpSlot* __restrict__ slots, int64_t capacity, int64_t max_pairs, int* ctrl, SpEdge* __restrict__ edges) {
-  __shared__ int wcount[SP_THREADS / INSAR_WAVE];
-  __shared__ int base_s;
-  const int lane = (int)__lane_id(), wave = threadIdx.x / INSAR_WAVE;
-  for (int64_t s0 = blockIdx.x * (int64_t)SP_THREADS; s0 < capacity; s0 += (int64_t)gridDim.x * SP_THREADS) {
-    const int64_t s = s0 + threadIdx.x;
-    int4 v = make_int4(0, 0, 0, 0);                                // {key lo = b, key hi = a, saddle lo, saddle hi}
-    if (s < capacity) v = *reinterpret_cast<const int4*>(slots + s);
-    const bool full = (v.x | v.y) != 0;
-    const unsigned long long b = __ballot(full);
-    if (lane == 0) wcount[wave] = __popcll(b);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const int n = wcount[0] + wcount[1] + wcount[2] + wcount[3];
-      base_s = n ? atomicAdd(ctrl + SP_NPAIRS, n) : 0;             // <= capacity <= 2^25
-    }
-    __syncthreads();
-    int64_t pos = (int64_t)base_s + __popcll(b & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) pos += wcount[w];
-    if (full && pos < max_pairs) *reinterpret_cast<int4*>(edges + pos) = make_int4(v.y, v.x, v.z, 0);
-    __syncthreads();                                               // wcount and base_s are rewritten by the next pass
+    wave_count(ctrl + SP_BASINS, root);
+    pair_fold_insert<4, WaveMax>(ctrl + SP_OVERFLOW, slots, mask, k, v);
   }
 }
 
@@ -270,7 +199,7 @@ split_decide_kernel(const SpEdge* __restrict__ edges, int* ctrl, int64_t max_pai
         merged |= sp_decide(v, u, e.s, h, best, bidx, squared, T, nxt);
       }
     }
-    sp_count(ctrl + SP_CTRL_WORDS + round, merged);
+    wave_count(ctrl + SP_CTRL_WORDS + round, merged);
   }
 }
 
@@ -283,9 +212,9 @@ split_compress_kernel(const SpEdge* __restrict__ edges, const int* __restrict__ 
 #pragma unroll
     for (int side = 0; side < 2; ++side) {
       const int x = side ? e.b : e.a;
-      int r = sp_ld(up + x);                                       // the old root or, from another edge of x, already the new one
+      int r = agent_load(up + x);                                  // the old root or, from another edge of x, already the new one
       for (;;) { const int m = nxt[r]; if (m == r) break; r = m; }
-      sp_st(up + x, r);
+      agent_store(up + x, r);
       bidx[r] = INT_MAX;                                           // every writer of these two stores the same values
       best[r] = 0ull;
     }
@@ -431,16 +360,12 @@ static int split_layout(const char* who, int32_t H, int32_t W, int64_t max_pairs
   if (H < 1 || W < 1) INSAR_FAIL(INSAR_E_SHAPE, "%s: empty scene %d x %d", who, H, W);
   const int64_t npix = (int64_t)H * W;
   if (npix >= ((int64_t)1 << 31)) INSAR_FAIL(INSAR_E_SHAPE, "%s: scene %d x %d has 2^31 pixels or more", who, H, W);
-  if (max_pairs < 1 || max_pairs > SP_MAX_PAIRS)
-    INSAR_FAIL(INSAR_E_SHAPE, "%s: max_pairs %lld outside 1..%lld", who, (long long)max_pairs, (long long)SP_MAX_PAIRS);
+  if (int rc = pair_table_capacity(who, max_pairs, &L->cap)) return rc;
   if (max_rounds < 1 || max_rounds > SP_MAX_ROUNDS)
     INSAR_FAIL(INSAR_E_SHAPE, "%s: max_rounds %d outside 1..%d", who, max_rounds, SP_MAX_ROUNDS);
   L->npix = npix;
   L->seg = insar_align16(npix * 4);
   L->nblk = (npix + SP_NB - 1) / SP_NB;
-  int64_t c = 2;
-  while (c < 2 * max_pairs) c <<= 1;
-  L->cap = c;
   L->ctrl_words = insar_align16((SP_CTRL_WORDS + (int64_t)max_rounds) * 4) / 4;
   L->off_up = L->seg;
   L->off_nxt = 2 * L->seg;
@@ -449,13 +374,8 @@ static int split_layout(const char* who, int32_t H, int32_t W, int64_t max_pairs
   L->off_counts = 6 * L->seg;
   L->off_ctrl = L->off_counts + insar_align16(L->nblk * 4);
   L->off_slots = L->off_ctrl + L->ctrl_words * 4;
-  L->off_edges = L->off_slots + L->cap * (int64_t)sizeof(SpSlot);
+  L->off_edges = L->off_slots + L->cap * (int64_t)sizeof(PairSlot);
   L->bytes = L->off_edges + max_pairs * (int64_t)sizeof(SpEdge);
-  return INSAR_OK;
-}
-static int split_check_map(const char* who, const char* what, const void* p) {
-  if (!p) INSAR_FAIL(INSAR_E_ARG, "%s: null pointer (%s)", who, what);
-  if (((uintptr_t)p) & 3u) INSAR_FAIL(INSAR_E_ALIGN, "%s: %s not 4-byte aligned", who, what);
   return INSAR_OK;
 }
 
@@ -476,16 +396,15 @@ extern "C" int insar_split_scratch_bytes(int32_t H, int32_t W, int32_t max_regio
 extern "C" int insar_split_basins(const int32_t* labels, const int32_t* height, int32_t H, int32_t W, int64_t max_pairs,
                                   int32_t max_rounds, void* scratch, void* stream) {
   const char* who = "insar_split_basins";
-  if (int rc = split_check_map(who, "labels", labels)) return rc;
-  if (int rc = split_check_map(who, "height", height)) return rc;
+  if (int rc = scene_check_map(who, "labels", labels, 4)) return rc;
+  if (int rc = scene_check_map(who, "height", height, 4)) return rc;
   SpLayout L;
   if (int rc = split_layout(who, H, W, max_pairs, max_rounds, &L)) return rc;
   if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
   hipStream_t s = (hipStream_t)stream;
   int *basin = scratch_at<int>(scratch, 0), *ctrl = scratch_at<int>(scratch, L.off_ctrl);
-  SpSlot* slots = scratch_at<SpSlot>(scratch, L.off_slots);
-  hipLaunchKernelGGL(split_clear_kernel, scene_grid(L.cap, SP_THREADS), dim3(SP_THREADS), 0, s, (int4*)slots, L.cap, (int4*)ctrl,
-                     (int)(L.ctrl_words / 4));
+  PairSlot* slots = scratch_at<PairSlot>(scratch, L.off_slots);
+  pair_table_clear(s, slots, L.cap, ctrl, (int)(L.ctrl_words / 4));
   INSAR_CHECK_LAUNCH(who);
   hipLaunchKernelGGL(split_ascent_kernel, scene_grid(L.npix, SP_THREADS), dim3(SP_THREADS), 0, s, (const int*)labels, (const int*)height, H, W,
                      basin, ctrl);
@@ -497,8 +416,7 @@ extern "C" int insar_split_basins(const int32_t* labels, const int32_t* height, 
                      scratch_at<int>(scratch, L.off_bidx), scratch_at<unsigned long long>(scratch, L.off_best), ctrl, slots,
                      (unsigned int)(L.cap - 1));
   INSAR_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(split_compact_kernel, scene_grid(L.cap, SP_THREADS), dim3(SP_THREADS), 0, s, (const SpSlot*)slots, L.cap, max_pairs, ctrl,
-                     scratch_at<SpEdge>(scratch, L.off_edges));
+  pair_table_compact(s, slots, L.cap, max_pairs, ctrl + SP_NPAIRS, scratch_at<SpEdge>(scratch, L.off_edges));
   INSAR_CHECK_LAUNCH(who);
   return INSAR_OK;
 }
@@ -507,7 +425,7 @@ extern "C" int insar_split_rounds(const int32_t* height, int32_t H, int32_t W, i
                                   int32_t first_round, int32_t n_rounds, int64_t max_pairs, int32_t max_rounds, void* scratch,
                                   void* stream) {
   const char* who = "insar_split_rounds";
-  if (int rc = split_check_map(who, "height", height)) return rc;
+  if (int rc = scene_check_map(who, "height", height, 4)) return rc;
   SpLayout L;
   if (int rc = split_layout(who, H, W, max_pairs, max_rounds, &L)) return rc;
   if (int rc = scene_check_buffer(who, "scratch", scratch)) return rc;
@@ -539,9 +457,9 @@ extern "C" int insar_split_finish(const int32_t* labels, const int32_t* height, 
                                   int32_t W, int32_t max_regions, int64_t max_pairs, int32_t max_rounds, void* scratch, void* table,
                                   int32_t* labels_out, void* stream) {
   const char* who = "insar_split_finish";
-  if (int rc = split_check_map(who, "labels", labels)) return rc;
-  if (int rc = split_check_map(who, "height", height)) return rc;
-  if (int rc = split_check_map(who, "labels_out", labels_out)) return rc;
+  if (int rc = scene_check_map(who, "labels", labels, 4)) return rc;
+  if (int rc = scene_check_map(who, "height", height, 4)) return rc;
+  if (int rc = scene_check_map(who, "labels_out", labels_out, 4)) return rc;
   if (((uintptr_t)conf) & 3u) INSAR_FAIL(INSAR_E_ALIGN, "%s: conf not 4-byte aligned", who);
   SpLayout L;
   if (int rc = split_layout(who, H, W, max_pairs, max_rounds, &L)) return rc;

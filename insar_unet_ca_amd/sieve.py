@@ -25,7 +25,9 @@ import torch
 
 from . import _lib
 from ._lib import InsarError, call, ptr
-from ._scene import Scratch, check_int, check_map, check_on_device, pinned, query_bytes, read_back
+from ._scene import MERGE_CTRL_WORDS as CTRL_WORDS  # noqa: F401  pairs, overflow, regions, class-255 pixels, changed pixels, absorbed, 2 spare
+from ._scene import MERGE_ROUNDS_PER_READ as ROUNDS_PER_READ  # noqa: F401  (the tools read them from here)
+from ._scene import Scratch, check_int, check_map, check_on_device, merge_rounds, pinned, query_bytes, read_back
 from .regions import DEFAULT_MAX_REGIONS, RegionScratch
 from .regions import _launch as _label_launch
 
@@ -34,8 +36,6 @@ MAX_PAIRS = 1 << 24
 MAX_ROUNDS = 4096
 MAX_REGIONS = 1 << 30
 MAX_LABEL = (1 << 31) - 1
-ROUNDS_PER_READ = 4                      # the host looks at the rounds' counters once per this many rounds
-CTRL_WORDS = 8                           # pairs, overflow, regions, class-255 pixels, changed pixels, absorbed, 2 spare; then one per round
 
 # a record of the pair list; the 16-byte header in front of it is {n_pairs, overflow, 0, 0} as int32
 PAIR_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("edges", "<i8")])
@@ -200,24 +200,20 @@ def sieve_regions(mask: torch.Tensor, *, min_area, connectivity: int = 8, void_v
         # the labelling of regions.py over the remapped map: every class is foreground; `out` takes its cleaned-mask output
         _label_launch(scratch.remap, None, int(connectivity), 1, 0.0, max_regions, scratch.regions.scratch, table, labels, out)
         call("insar_sieve_pairs", ptr(labels), H, W, max_regions, *args, s)
-        done, rounds, converged = 0, max_rounds, False
-        while done < max_rounds and not converged:
-            n = min(ROUNDS_PER_READ, max_rounds - done)
-            call("insar_sieve_rounds", ptr(table), ptr(mask), ptr(scratch.thresholds), H, W, done, n, *args, s)
-            ctrl = read_back(scratch.ctrl_host, scratch.ctrl).view(np.int32)
-            if done == 0:
-                N = int(ctrl[2])
-                if ctrl[3]:
-                    raise InsarError(f"{who}: {int(ctrl[3])} pixels of class 255 with void_value=None: 255 classes at most")
-                if N > max_regions:
-                    raise InsarError(f"{who}: {N} regions exceed max_regions={max_regions}: raise max_regions")
-                if ctrl[1] or ctrl[0] > max_pairs:
-                    raise InsarError(f"{who}: {'more than ' if ctrl[1] else ''}{int(ctrl[0])} adjacent region pairs exceed "
-                                     f"max_pairs={max_pairs}: raise max_pairs")
-            done += n
-            idle = np.flatnonzero(ctrl[CTRL_WORDS:CTRL_WORDS + done] == 0)
-            if len(idle):                                         # rounds after the first idle one changed nothing
-                rounds, converged = int(idle[0]), True
+
+        def first_read(ctrl):
+            if ctrl[3]:
+                raise InsarError(f"{who}: {int(ctrl[3])} pixels of class 255 with void_value=None: 255 classes at most")
+            if ctrl[2] > max_regions:
+                raise InsarError(f"{who}: {int(ctrl[2])} regions exceed max_regions={max_regions}: raise max_regions")
+            if ctrl[1] or ctrl[0] > max_pairs:
+                raise InsarError(f"{who}: {'more than ' if ctrl[1] else ''}{int(ctrl[0])} adjacent region pairs exceed "
+                                 f"max_pairs={max_pairs}: raise max_pairs")
+
+        rounds, converged, ctrl = merge_rounds(
+            lambda first, n: call("insar_sieve_rounds", ptr(table), ptr(mask), ptr(scratch.thresholds), H, W, first, n, *args, s),
+            scratch.ctrl_host, scratch.ctrl, max_rounds, first_read)
+        N = int(ctrl[2])
         call("insar_sieve_apply", ptr(labels), ptr(mask), H, W, *args, ptr(out), ptr(changed), s)
         nbytes = scratch.ctrl.numel() + 4 * (N + 1)
         raw = read_back(scratch.state_host, scratch.state, nbytes)

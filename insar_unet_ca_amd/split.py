@@ -28,7 +28,9 @@ import torch
 
 from . import _lib
 from ._lib import InsarError, call, ptr
-from ._scene import Scratch, check_int, check_map, check_on_device, pinned, query_bytes, read_back
+from ._scene import MERGE_CTRL_WORDS as CTRL_WORDS  # noqa: F401  pairs, overflow, negative heights, basins, pieces, 3 spare
+from ._scene import MERGE_ROUNDS_PER_READ as ROUNDS_PER_READ  # noqa: F401  (the tools read them from here)
+from ._scene import Scratch, check_int, check_map, check_on_device, merge_rounds, pinned, query_bytes, read_back
 from .distance import MAX_DIM, DistanceScratch, distance_transform
 from .regions import CONF_SCALE, DEFAULT_MAX_REGIONS
 
@@ -36,8 +38,6 @@ DEFAULT_MAX_PAIRS = 1 << 20
 MAX_PAIRS = 1 << 24
 MAX_ROUNDS = 4096
 MAX_THRESHOLD = 1 << 20
-ROUNDS_PER_READ = 4                      # the host looks at the rounds' counters once per this many rounds
-CTRL_WORDS = 8                           # pairs, overflow, negative heights, basins, pieces, 3 spare; then one word per round
 
 # the C struct InsarSplitRegion (include/insar_hip.h); record 0 of a table is the header
 SPLIT_DTYPE = np.dtype([("area", "<i8"), ("sum_y", "<i8"), ("sum_x", "<i8"), ("sum_conf", "<i8"),
@@ -164,21 +164,18 @@ def split_regions(labels: torch.Tensor, *, mask: Optional[torch.Tensor] = None, 
     with torch.cuda.device(labels.device):
         s = _lib.stream_ptr()
         call("insar_split_basins", ptr(labels), ptr(height), H, W, max_pairs, max_rounds, ptr(scratch.scratch), s)
-        done, rounds, converged = 0, max_rounds, False
-        while done < max_rounds and not converged:
-            n = min(ROUNDS_PER_READ, max_rounds - done)
-            call("insar_split_rounds", ptr(height), H, W, int(squared), T, done, n, max_pairs, max_rounds, ptr(scratch.scratch), s)
-            ctrl = read_back(scratch.ctrl_host, scratch.ctrl).view(np.int32)
-            if done == 0:
-                if ctrl[2]:
-                    raise InsarError(f"{who}: height is negative on {int(ctrl[2])} foreground pixels")
-                if ctrl[1] or ctrl[0] > max_pairs:
-                    raise InsarError(f"{who}: {'more than ' if ctrl[1] else ''}{int(ctrl[0])} adjacent basin pairs exceed "
-                                     f"max_pairs={max_pairs}: raise max_pairs, or smooth the height map")
-            done += n
-            idle = np.flatnonzero(ctrl[CTRL_WORDS:CTRL_WORDS + done] == 0)
-            if len(idle):                                         # rounds after the first idle one changed nothing
-                rounds, converged = int(idle[0]), True
+
+        def first_read(ctrl):
+            if ctrl[2]:
+                raise InsarError(f"{who}: height is negative on {int(ctrl[2])} foreground pixels")
+            if ctrl[1] or ctrl[0] > max_pairs:
+                raise InsarError(f"{who}: {'more than ' if ctrl[1] else ''}{int(ctrl[0])} adjacent basin pairs exceed "
+                                 f"max_pairs={max_pairs}: raise max_pairs, or smooth the height map")
+
+        rounds, converged, _ = merge_rounds(
+            lambda first, n: call("insar_split_rounds", ptr(height), H, W, int(squared), T, first, n, max_pairs, max_rounds,
+                                  ptr(scratch.scratch), s),
+            scratch.ctrl_host, scratch.ctrl, max_rounds, first_read)
         call("insar_split_finish", ptr(labels), ptr(height), ptr(mask), ptr(conf), H, W, max_regions, max_pairs, max_rounds,
              ptr(scratch.scratch), ptr(scratch.table), ptr(out), s)
         raw = read_back(scratch.host, scratch.table)
